@@ -15,6 +15,12 @@ clips per GPU.  The line also carries
   roofline_step — the whole step against the HBM peak: algorithmic bytes from the layer table below, the committed PMC
                  total of a step, and this run's ms_per_step;
   other_configs — BASELINE configs 1 / 3 / 4 / 5 (per GPU) through the same engine, 10 hipGraph steps each (N=1 only).
+
+``--dump-outputs DIR`` (rank 0) writes what the LAST timed step computed, before anything else runs, as DIR/<name>.npy:
+the step's log scalars (loss, loss_cls, top1_acc, top5_acc; float64), and in ``model.named_parameters()`` /
+``named_buffers()`` order the parameters after its update (params.npy), its gradient after the exchange (grads.npy)
+and the BatchNorm running statistics (buffers.npy; float32).  Model, clips and labels are seeded: the same arguments
+give the same inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -648,6 +654,29 @@ def self_launch(n_gpus, argv):
         raise
 
 
+def snapshot_outputs(engine, logs):
+    """name -> host array of what the engine's last step computed (see the module docstring: --dump-outputs)."""
+    flat = engine.flat
+    out = {k: np.asarray(v.item(), dtype=np.float64) for k, v in sorted(logs.items())}
+    out['params'] = torch.cat([p.detach().reshape(-1) for p in flat.params]).cpu().numpy()
+    out['grads'] = torch.cat([flat.flat_g[off:off + n] for off, n in flat.slices]).cpu().numpy()
+    out['buffers'] = torch.cat([b.detach().reshape(-1).float() for _, b in engine.model.named_buffers()
+                                if b.is_floating_point()]).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f'--dump-outputs: {total} bytes exceed the 64 MiB budget'
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    ignore = os.path.join(out_dir, '.gitignore')
+    if not os.path.exists(ignore):
+        with open(ignore, 'w') as f:         # a run's outputs, not sources: the directory keeps itself out of git
+            f.write('*\n')
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
@@ -660,11 +689,16 @@ def main(argv=None):
     ap.add_argument('--no-other-configs', action='store_true', help='skip the BASELINE configs 1 / 3 / 4 / 5 step times')
     ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying captured hipGraphs')
     ap.add_argument('--cpu-budget', type=float, default=12.0)
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if 'WORLD_SIZE' not in os.environ and (args.gpus > 1 or os.environ.get('DSGCN_BENCH_SELF_LAUNCH') == '1'):
         # the driver's N = 1 form (`python bench.py --gpus N`) asked for N > 1: become the launcher's parent — BEFORE any
         # GPU call — and hand back the children's line and exit code
+        if args.dump_outputs:       # the ranks run from the repository root: hand them the directory as an absolute path
+            argv += ['--dump-outputs', os.path.abspath(args.dump_outputs)]
         raise SystemExit(self_launch(args.gpus, argv))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -706,7 +740,8 @@ def main(argv=None):
     state = {}
 
     def step():
-        state['loss'] = engine.step(keypoint, label)['loss']
+        state['logs'] = engine.step(keypoint, label)
+        state['loss'] = state['logs']['loss']
 
     # untimed warm-up: the first steps run eagerly (caches: edge-class lists, allocator pools, pinned tables), then the
     # engine captures the launch-bound inner loop (~800 kernels per step) into its two hipGraphs and replays them
@@ -753,6 +788,8 @@ def main(argv=None):
         elapsed = tmax.item()
     loss_val = float(state['loss'].item())
     assert flat.check_views(), 'a parameter gradient left the flat buffer'
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, snapshot_outputs(engine, state['logs']))      # before any further step
     assert np.isfinite(loss_val), loss_val
 
     result = None

@@ -10,9 +10,9 @@ for the hot path, written from the math in SURVEY.md Appendix A and functional o
 reference lines it restates (paths relative to the reference root).
 
 Parity pin: ``tests/test_oracle_golden.py`` (``*_live`` tests) checks every unit here against the
-imported reference in the build container (skipped where /root/reference is absent), and
-``tests/golden/*.npz`` (written by ``tests/golden/gen_golden.py`` from the imported
-reference) pin it on the GPU box.  The reference itself ships no tests/golden vectors
+reference modules' own fp64 outputs (``tests/golden/reference_fp64.npz``, 1e-11 absolute or tighter), and the other
+``tests/golden/*.npz`` (written by ``tests/golden/gen_golden*.py`` from the imported reference) pin the
+rest.  The reference itself ships no tests/golden vectors
 (SURVEY.md §4), so these fixtures are the pin.
 """
 from math import ceil

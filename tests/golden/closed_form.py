@@ -241,3 +241,74 @@ def step_input(step, N, T, V, classes):
     x = (torch.sin(0.0137 * i) + 0.3 * torch.cos(0.00071 * i * i % 6.283185307179586)).reshape(N, 1, 2, T, V, 3).float()
     y = ((torch.arange(N) * 7 + 3 * step) % classes).reshape(N, 1)
     return x, y
+
+
+# The fp64 oracle-vs-reference cases (gen_golden_fp64.py, the *_vs_reference_live tests): group -> the cases it builds
+REF64_GROUPS = ('aagcn', 'dgphgcn1', 'dggcn', 'temporal')
+
+
+def make_ref64_group(ns, graph_cls, group):
+    """Build the cases of `group` from namespace `ns` (the reference's gcns.utils or this package) with the graph class of
+    the same side: seeded default init, live alpha / beta / add_coeff, then an fp64 input drawn from the same global RNG
+    stream; -> [(name, module fp64 in train mode, input fp64)].  Weights and inputs are rebuilt, never stored: the
+    fixture keeps their digests (sd_digest, array_digest)."""
+    import numpy as np
+    out = []
+    if group == 'aagcn':
+        torch.manual_seed(4)
+        A = torch.tensor(graph_cls(layout='coco', mode='spatial').A, dtype=torch.float32)
+        for i, (ci, co) in enumerate(((48, 48), (32, 64))):
+            m = ns.unit_aagcn(ci, co, A.clone())
+            m.init_weights()
+            with torch.no_grad():
+                m.alpha.normal_(0, .5)
+                m.conv_ta.weight.normal_(0, .1)
+                m.fc2c.weight.normal_(0, .05)
+                m.bn.weight.fill_(1.0)
+            m = m.double()
+            out.append((f'aagcn{i}', m, torch.randn(2, ci, 10, 17, dtype=torch.float64)))
+    elif group == 'dgphgcn1':
+        torch.manual_seed(1)
+        np.random.seed(1)
+        G = graph_cls(layout='coco', mode='random', num_filter=3, init_off=.04, init_std=.02)
+        m = ns.dgphgcn1(64, 64, torch.tensor(G.A, dtype=torch.float32), torch.tensor(G.edge_type, dtype=torch.float32),
+                        torch.tensor(G.node_type), ratio=0.125, decompose=True, node_attention=True, edge_attention=True,
+                        subset_wise=True, ctr='T', ada='T').double()
+        with torch.no_grad():
+            m.alpha.normal_(0, .5)
+            m.beta.normal_(0, .5)
+        out.append(('dgphgcn1', m, torch.randn(2, 64, 10, 17, dtype=torch.float64)))
+    elif group == 'dggcn':
+        torch.manual_seed(2)
+        np.random.seed(2)
+        G = graph_cls(layout='coco', mode='random', num_filter=3, init_off=.04, init_std=.02)
+        A = torch.tensor(G.A, dtype=torch.float32)
+        for i, (ci, co, sw) in enumerate(((48, 48, False), (32, 64, True))):
+            m = ns.dggcn(ci, co, A, ratio=0.25, subset_wise=sw).double()
+            with torch.no_grad():
+                m.alpha.normal_(0, .5)
+                m.beta.normal_(0, .5)
+            out.append((f'dggcn{i}', m, torch.randn(2, ci, 10, 17, dtype=torch.float64)))
+    elif group == 'temporal':
+        for cls, stride in (('dgmstcn', 1), ('dgmstcn', 2), ('mstcn', 1), ('mstcn', 2)):
+            torch.manual_seed(5)
+            m = getattr(ns, cls)(64, 64, stride=stride).double()
+            with torch.no_grad():
+                if hasattr(m, 'add_coeff'):
+                    m.add_coeff.normal_(0, .5)
+            out.append((f'temporal_{cls}_s{stride}', m, torch.randn(2, 64, 10, 25, dtype=torch.float64)))
+    else:
+        raise KeyError(group)
+    return [(name, m.train(), x) for name, m, x in out]
+
+
+def array_digest(t):
+    import hashlib
+    return hashlib.sha256(t.detach().cpu().numpy().tobytes()).hexdigest()
+
+
+def ref64_sample(n, count=512):
+    """Fixed, spread-out flat positions (multiplicative hashing, no RNG) at which the fp64 fixture keeps an output's
+    values; every element is also covered by the fixture's per-(channel, frame) sums."""
+    import numpy as np
+    return np.unique((np.arange(count, dtype=np.int64) * 2654435761) % n)

@@ -1,8 +1,7 @@
 """Import the read-only reference (/root/reference) with stub third-party modules.
 
-Build-container only: the GPU box has no /root/reference.  Used by
-``tests/golden/gen_golden.py`` (fixture generation) and by the optional
-the ``*_live`` tests of ``tests/test_oracle_golden.py`` (skipped when the reference is absent).
+Used by the fixture generators ``tests/golden/gen_golden*.py`` only: the tests read
+the fixtures they wrote and never import the reference.
 
 Nothing from the reference is copied: the real modules are imported in place
 (``sys.dont_write_bytecode`` so no __pycache__ lands in the read-only tree).

@@ -1,5 +1,7 @@
 """CPU: the oracle (oracle/dsgcn_oracle.py) against the committed golden vectors (tests/golden/*.npz, generated from the
-imported reference by tests/golden/gen_golden.py) and, where /root/reference exists, against the reference itself."""
+imported reference by tests/golden/gen_golden*.py).  The *_vs_reference_live tests hold the oracle to the reference
+module's own fp64 output at 1e-11 .. 1e-12 absolute (tests/golden/reference_fp64.npz, gen_golden_fp64.py): at fixed
+positions and in the per-(channel, frame) sums that every element enters."""
 import json
 import os
 
@@ -103,25 +105,40 @@ def test_unit_aagcn(i):
         assert rel(sd[k].grad, z[tag + 'grad_' + k]) < 1e-6, k
 
 
+def max_abs(a, b):
+    return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
+
+
+def ref64_group(group):
+    """-> [(name, state_dict fp64, input fp64)] of a reference_fp64.npz group, rebuilt from the shared seeded recipe with
+    this package's modules and checked against the digests of the reference build."""
+    import sys
+    sys.path.insert(0, GOLD)
+    from closed_form import array_digest, make_ref64_group, sd_digest
+    import dsgcn_amd as D
+    z = load('reference_fp64.npz')
+    out = []
+    for name, m, x in make_ref64_group(D, D.Graph, group):
+        assert sd_digest(m) == str(z[f'{name}_sd_digest']), f'{name}: seeded weights differ from the reference build'
+        assert array_digest(x) == str(z[f'{name}_x_digest']), f'{name}: seeded input differs from the reference build'
+        out.append((name, {k: v.detach().clone() for k, v in m.state_dict().items()}, x))
+    return z, out
+
+
+def assert_ref64(z, name, got, tol):
+    """The oracle's fp64 output against the reference module's: at the stored positions and in the per-(channel, frame)
+    sums over samples and joints (every element enters one), both within `tol` absolute."""
+    got = got.detach().numpy()
+    assert got.shape == tuple(z[f'{name}_shape']), name
+    assert max_abs(got.reshape(-1)[z[f'{name}_idx']], z[f'{name}_y_at']) < tol, name
+    assert max_abs(got.sum((0, 3)), z[f'{name}_y_sums']) < tol, name
+
+
 def test_unit_aagcn_vs_reference_live():
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip('reference tree not present (GPU box)')
-    R = ref_shim.load()
-    torch.manual_seed(4)
-    A = torch.tensor(R.graph.Graph(layout='coco', mode='spatial').A, dtype=torch.float32)
-    for ci, co in ((48, 48), (32, 64)):
-        m = R.gutils.unit_aagcn(ci, co, A.clone())
-        m.init_weights()
-        with torch.no_grad():
-            m.alpha.normal_(0, .5)
-            m.conv_ta.weight.normal_(0, .1)
-            m.fc2c.weight.normal_(0, .05)
-            m.bn.weight.fill_(1.0)
-        m = m.double()
-        x = torch.randn(2, ci, 10, 17, dtype=torch.float64)
-        sd = {k: v.detach() for k, v in m.state_dict().items()}
-        assert (m(x) - O.unit_aagcn_forward(x, sd)).abs().max().item() < 1e-11
+    """unit_aagcn on the coco graph (48 -> 48, 32 -> 64) against the reference module's fp64 output."""
+    z, cases = ref64_group('aagcn')
+    for name, sd, x in cases:
+        assert_ref64(z, name, O.unit_aagcn_forward(x, sd), 1e-11)
 
 
 def test_reduced_dggcn_model():
@@ -227,44 +244,17 @@ def test_full_size_closed_form_ds():
 
 
 def test_oracle_vs_reference_live():
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip('reference tree not present (GPU box)')
-    R = ref_shim.load()
-    torch.manual_seed(1)
-    np.random.seed(1)
-    G = R.graph.Graph(layout='coco', mode='random', num_filter=3, init_off=.04, init_std=.02)
-    A = torch.tensor(G.A, dtype=torch.float32)
-    m = R.gutils.dgphgcn1(64, 64, A, torch.tensor(G.edge_type, dtype=torch.float32), torch.tensor(G.node_type),
-                          ratio=0.125, decompose=True, node_attention=True, edge_attention=True, subset_wise=True,
-                          ctr='T', ada='T').double()
-    with torch.no_grad():
-        m.alpha.normal_(0, .5)
-        m.beta.normal_(0, .5)
-    x = torch.randn(2, 64, 10, 17, dtype=torch.float64)
+    """dgphgcn1 64 -> 64 on the coco random graph against the reference module's fp64 output."""
+    z, [(name, sd, x)] = ref64_group('dgphgcn1')
     gc = O.graph_constants('coco')
-    sd = {k: v.detach() for k, v in m.state_dict().items()}
-    assert (m(x) - O.dgphgcn1_forward(x, sd, gc['node_type'], gc['edge_type'])).abs().max().item() < 1e-12
+    assert_ref64(z, name, O.dgphgcn1_forward(x, sd, gc['node_type'], gc['edge_type']), 1e-12)
 
 
 def test_dggcn_vs_reference_live():
-    """dggcn restatement against the imported reference class, fp64, other widths / joints than the fixture's."""
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip('reference tree not present (GPU box)')
-    R = ref_shim.load()
-    torch.manual_seed(2)
-    np.random.seed(2)
-    G = R.graph.Graph(layout='coco', mode='random', num_filter=3, init_off=.04, init_std=.02)
-    A = torch.tensor(G.A, dtype=torch.float32)
-    for ci, co, sw in ((48, 48, False), (32, 64, True)):
-        m = R.gutils.dggcn(ci, co, A, ratio=0.25, subset_wise=sw).double()
-        with torch.no_grad():
-            m.alpha.normal_(0, .5)
-            m.beta.normal_(0, .5)
-        x = torch.randn(2, ci, 10, 17, dtype=torch.float64)
-        sd = {k: v.detach() for k, v in m.state_dict().items()}
-        assert (m(x) - O.dggcn_forward(x, sd, subset_wise=sw)).abs().max().item() < 1e-12
+    """dggcn restatement against the reference module's fp64 output, other widths / joints than the fixture's."""
+    z, cases = ref64_group('dggcn')
+    for name, sd, x in cases:
+        assert_ref64(z, name, O.dggcn_forward(x, sd, subset_wise=bool(z[f'{name}_subset_wise'])), 1e-12)
 
 
 # ---- round-2 fixtures (tests/golden/gen_golden_r2.py) ------------------------------------------------------------
@@ -382,42 +372,29 @@ def test_eval_fixture_oracle(name, kind, T, V, classes, layout):
 @pytest.mark.parametrize('tag', ['gcn', 'gcn_res', 'tcn9', 'tcn1s2', 'ctrgcn', 'MSTCN', 'gcn_offset_post', 'gcn_importance',
                                  'gcn_fixed_post', 'ctrhgcn', 'ctrhgcn_same', 'msmlp', 'msmlp_s2', 'unitmlp9', 'unitmlp9_s2'])
 def test_oracle_units_vs_reference_live(tag):
-    """Build container only: every unit restated in the oracle against the IMPORTED reference module, fp64."""
+    """Every unit restated in the oracle against the reference module's fp64 output (weights and input rebuilt from the
+    shared seeded recipe; their digests are part of the fixture)."""
     import sys
     sys.path.insert(0, GOLD)
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip('reference tree not present (GPU box)')
-    from closed_form import make_unit
-    R = ref_shim.load()
-    Gs = R.graph.Graph(layout='nturgb+d', mode='spatial')
-    A = torch.tensor(Gs.A, dtype=torch.float32)
-    m, x, _ = make_unit(R.gutils, tag, A, Gs.edge_type, Gs.node_type)
-    m = m.double().train()
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    want = m(x.double())
-    got = _unit_oracle(tag, x.double(), sd)
-    assert (want - got).abs().max().item() < 1e-11
+    from closed_form import array_digest, make_unit, sd_digest
+    import dsgcn_amd as D
+    z = load('reference_fp64.npz')
+    A = torch.tensor(O.graph_A('nturgb+d', 'spatial'), dtype=torch.float32)
+    m, x, _ = make_unit(D, tag, A, *_graph_tables())
+    assert sd_digest(m) == str(z[f'unit_{tag}_sd_digest']), 'seeded unit weights differ from the reference build'
+    assert array_digest(x) == str(z[f'unit_{tag}_x_digest']), 'seeded unit input differs from the reference build'
+    sd = {k: (v.double() if v.dtype.is_floating_point else v) for k, v in m.state_dict().items()}
+    assert_ref64(z, f'unit_{tag}', _unit_oracle(tag, x.double(), sd), 1e-11)
 
 
 @pytest.mark.parametrize('cls,stride', [('dgmstcn', 1), ('dgmstcn', 2), ('mstcn', 1), ('mstcn', 2)])
 def test_oracle_temporal_units_vs_reference_live(cls, stride):
-    import sys
-    sys.path.insert(0, GOLD)
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip('reference tree not present (GPU box)')
-    R = ref_shim.load()
-    torch.manual_seed(5)
-    m = getattr(R.gutils, cls)(64, 64, stride=stride).double().train()
-    with torch.no_grad():
-        if hasattr(m, 'add_coeff'):
-            m.add_coeff.normal_(0, .5)
-    x = torch.randn(2, 64, 10, 25, dtype=torch.float64)
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    want = m(x)
+    """dgmstcn / mstcn 64 -> 64 against the reference module's fp64 output."""
+    z, cases = ref64_group('temporal')
+    name = f'temporal_{cls}_s{stride}'
+    sd, x = next((sd, x) for n, sd, x in cases if n == name)
     got = (O.dgmstcn_forward if cls == 'dgmstcn' else O.mstcn_forward)(x, sd, stride)
-    assert (want - got).abs().max().item() < 1e-11
+    assert_ref64(z, name, got, 1e-11)
 
 
 # ---- round-3 fixtures (tests/golden/gen_golden_r3.py) ------------------------------------------------------------
