@@ -63,6 +63,10 @@ def off_knife_edge(x1, a1, x2, a2, relu, tol=1e-4):
     (128, 24, 64, 25, True, True), (128, 48, 64, 25, True, True), (128, 48, 32, 25, True, True), (128, 96, 32, 25, True, True),
     (128, 96, 16, 25, True, True)])
 def test_aggregate(n, KC, T, V, relu, affine):
+    check_aggregate(n, KC, T, V, relu, affine)
+
+
+def check_aggregate(n, KC, T, V, relu, affine):
     g = torch.Generator().manual_seed(n * 1000 + KC + T)
     zp = torch.randn(n, KC, T, V, generator=g)
     ahat = torch.randn(n, KC, V, V, generator=g) * 0.3
@@ -110,6 +114,10 @@ def _dyn_inputs(n, Ci, mid, V, layout, seed=0):
     (128, 3, 8, 25, 'nturgb+d'), (128, 64, 8, 25, 'nturgb+d'), (128, 64, 16, 25, 'nturgb+d'), (128, 128, 16, 25, 'nturgb+d'),
     (128, 128, 32, 25, 'nturgb+d'), (128, 256, 32, 25, 'nturgb+d'), (64, 256, 32, 17, 'coco')])
 def test_dynadj(n, Ci, mid, V, layout):
+    check_dynadj(n, Ci, mid, V, layout)
+
+
+def check_dynadj(n, Ci, mid, V, layout):
     t, nt, et = _dyn_inputs(n, Ci, mid, V, layout, seed=Ci + mid)
     g = torch.Generator().manual_seed(7)
     dah = torch.randn(n, 3 * mid, V, V, generator=g)
@@ -325,6 +333,11 @@ def test_bn_batching_leaves_the_step_bit_identical(kind, monkeypatch):
     (128, 8, 64, 25, 25, 1, False, 'plain'),         # CTR-GCN conv4 (config 4)
 ])
 def test_pwconv(n, Ci, Co, T, V, stride, aug, mode):
+    check_pwconv(n, Ci, Co, T, V, stride, aug, mode)
+
+
+def check_pwconv(n, Ci, Co, T, V, stride, aug, mode, want_bn=True, bias=True):
+    """want_bn / bias False: the convs without a BatchNorm behind them (K-B's and the CTR-GCN refinement's projections)."""
     g = torch.Generator().manual_seed(Ci * 7 + Co + T)
     x1 = _rand(g, n, Ci, T, V)
     a1 = a2 = x2 = None
@@ -351,17 +364,24 @@ def test_pwconv(n, Ci, Co, T, V, stride, aug, mode):
     def run(mod, dt, dev):
         def mk(t):
             return None if t is None else t.to(dev, dt).requires_grad_()
-        tx1, tx2, tw, tb, tg, tbeta = mk(x1), mk(x2), mk(w), mk(b), mk(gamma), mk(beta)
+        tx1, tx2, tw, tb, tg, tbeta = mk(x1), mk(x2), mk(w), mk(b if bias else None), mk(gamma), mk(beta)
         ta1 = None if a1 is None else (mk(a1[0]), mk(a1[1]))
         ta2 = None if a2 is None else (mk(a2[0]), mk(a2[1]))
-        z, zaug, sc, sh, mean, var = mod.pwconv(tx1, ta1, tx2, ta2, relu, tw, tb, stride, aug, tg, tbeta, 1e-5, n_aff,
-                                                True)
-        loss = (z * gz.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()
+        if want_bn:
+            z, zaug, sc, sh, mean, var = mod.pwconv(tx1, ta1, tx2, ta2, relu, tw, tb, stride, aug, tg, tbeta, 1e-5, n_aff,
+                                                    True)
+            loss = (z * gz.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()
+        else:
+            z, zaug = mod.pwconv(tx1, ta1, tx2, ta2, relu, tw, tb, stride, aug)[:2]
+            loss = (z * gz.to(dev, dt)).sum()
         if aug:
             loss = loss + (zaug * gza.to(dev, dt)).sum()
         loss.backward()
-        outs = dict(z=z, sc=sc, sh=sh, mean=mean, var=var, dx1=tx1.grad, dw=tw.grad, db=tb.grad, dgamma=tg.grad,
-                    dbeta=tbeta.grad)
+        outs = dict(z=z, dx1=tx1.grad, dw=tw.grad)
+        if want_bn:
+            outs.update(sc=sc, sh=sh, mean=mean, var=var, dgamma=tg.grad, dbeta=tbeta.grad)
+        if bias:
+            outs['db'] = tb.grad
         if aug:
             outs['zaug'] = zaug
         if tx2 is not None:
@@ -385,6 +405,52 @@ def test_pwconv(n, Ci, Co, T, V, stride, aug, mode):
         assert err < tol, (k, err)
 
 
+def check_pwconv_group(Kk, n, Ci, Co, T, V, affine):
+    """pwconv_group (CTR-GCN's conv4 of the Kk subsets in one launch each way: csrc/pw4.hip grouped over blockIdx.y) against
+    Kk single pwconv calls of the same operands — the same kernel, so the outputs and the data gradients bit for bit; the
+    weight and input-scale gradients too where the single call's backward takes the same dgrad / wgrad kernels (the
+    one-pass backward of narrow convs, csrc/bwd64.hip, sums in another order: 2e-6 there) — and against fp64 with
+    test_pwconv's bars."""
+    lib = dsgcn_amd.native.lib()
+    assert lib.dsgcn_pwconv_group_ok(n, Ci, Co, T, V) == 1
+    g = torch.Generator().manual_seed(Kk * 100 + Ci + Co)
+    xs = [_rand(g, n, Ci, T, V) for _ in range(Kk)]
+    affs = [(torch.rand(Ci, generator=g) + 0.5, _rand(g, Ci, scale=0.3)) if affine else None for _ in range(Kk)]
+    ws = [_rand(g, Co, Ci, scale=Ci ** -0.5) for _ in range(Kk)]
+    gzs = [_rand(g, n, Co, T, V) for _ in range(Kk)]
+
+    def run(how, dt, dev):
+        tx = [x.to(dev, dt).requires_grad_() for x in xs]
+        ta = [None if a is None else (a[0].to(dev, dt).requires_grad_(), a[1].to(dev, dt).requires_grad_()) for a in affs]
+        tw = [w.to(dev, dt).requires_grad_() for w in ws]
+        if how == 'group':
+            buf = torch.empty((Kk, n, Co, T, V), device=dev, dtype=dt)
+            zs = K.pwconv_group(tx, ta, tw, [K.OutSlot(buf[k]) for k in range(Kk)])
+        else:
+            mod = K if how == 'single' else R
+            zs = [mod.pwconv(x, a, None, None, False, w, None, 1, False)[0] for x, a, w in zip(tx, ta, tw)]
+        sum((z * gz.to(dev, dt)).sum() for z, gz in zip(zs, gzs)).backward()
+        res = {}
+        for k in range(Kk):
+            res[f'z{k}'], res[f'dx{k}'], res[f'dw{k}'] = zs[k], tx[k].grad, tw[k].grad
+            if affine:
+                res[f'ds{k}'], res[f'dh{k}'] = ta[k][0].grad, ta[k][1].grad
+        return res
+
+    got = run('group', torch.float32, DEV)
+    single = run('single', torch.float32, DEV)
+    same_bwd = lib.dsgcn_pwconv_bwd_rows(n, Ci, Co, T, V, 1) <= 0
+    for k, v in single.items():
+        if k[0] == 'z' or k[:2] == 'dx' or same_bwd:
+            assert torch.equal(got[k], v), (k, rel(got[k], v))
+        else:
+            assert rel(got[k], v) < 2e-6, (k, rel(got[k], v))
+    ref = run('ref', torch.float64, ref_dev(n))
+    for k, v in ref.items():
+        tol = 5e-5 if (n >= 64 and k[:2] in ('dw', 'ds', 'dh')) else 2e-5
+        assert rel(got[k], v) < tol, (k, rel(got[k], v))
+
+
 @pytest.mark.parametrize('n,Ci,Co,T,V,KT,mode,stride', [(a_ + (1,)) for a_ in [
     (2, 64, 64, 16, 25, 9, 'res_affine'),     # ST-GCN unit_tcn after unit_gcn with a conv residual
     (3, 64, 64, 64, 25, 9, 'res_plain'),      # first stage: 13 tiles per sample, the last one partial
@@ -404,6 +470,10 @@ def test_pwconv(n, Ci, Co, T, V, stride, aug, mode):
     (128, 128, 256, 32, 25, 9, 'res_affine', 2), (128, 256, 256, 16, 25, 9, 'res_plain', 1),
 ])
 def test_tconv_gemm(n, Ci, Co, T, V, KT, mode, stride):
+    check_tconv_gemm(n, Ci, Co, T, V, KT, mode, stride)
+
+
+def check_tconv_gemm(n, Ci, Co, T, V, KT, mode, stride):
     """csrc/tcg.hip: the dense (KT,1) temporal conv as a GEMM on bf16 terms — forward with BatchNorm statistics, data
     gradient with the mask / affine epilogue, weight gradient — against the fp64 evaluation of the same op."""
     g = torch.Generator().manual_seed(Ci * 3 + Co + T + KT)
@@ -546,13 +616,19 @@ def test_pwconv_bf16_split_edge_cases(case):
     (2, 64, 32, 25, 'res_plain', True, 3), (2, 32, 16, 25, 'res_affine', False, 3), (2, 16, 8, 17, 'affine', False, 2),
     (2, 16, 8, 25, 'res_affine', False, 0)])
 def test_fuse_out(n, C, T, V, mode, tmean, flags):
+    check_fuse_out(n, C, T, V, mode, tmean, flags)
+
+
+def check_fuse_out(n, C, T, V, mode, tmean, flags, tee=False):
+    """tmean: False / True / an int ld > V (the time mean with its joint row zero-padded to ld, the layout dynadj reads);
+    tee: the output as three aliases (1), the third one the even frames as a tensor of their own (2)."""
     g = torch.Generator().manual_seed(C + T)
     x1 = _rand(g, n, C, T, V)
     a1 = None if mode == 'plain' else (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3))
     x2 = _rand(g, n, C, T, V) if mode.startswith('res') else None
     a2 = (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3)) if mode == 'res_affine' else None
     go = _rand(g, n, C, T, V)
-    gb = _rand(g, n, C, V)
+    gb = _rand(g, n, C, V if tmean is True or not tmean else int(tmean))
 
     def run(mod, dt, dev):
         def mk(t):
@@ -560,12 +636,20 @@ def test_fuse_out(n, C, T, V, mode, tmean, flags):
         tx1, tx2 = mk(x1), mk(x2)
         ta1 = None if a1 is None else (mk(a1[0]), mk(a1[1]))
         ta2 = None if a2 is None else (mk(a2[0]), mk(a2[1]))
-        out, xbar = mod.fuse_out(tx1, ta1, tx2, ta2, flags, tmean)
+        out, xbar = mod.fuse_out(tx1, ta1, tx2, ta2, flags, tmean, tee)
+        even = None
+        if tee:
+            out, _, third = out
+            even = third.x if tee == 2 and mod is K else (out[:, :, ::2] if tee == 2 else None)
         loss = (out * go.to(dev, dt)).sum()
+        if even is not None:
+            loss = loss + (even * go[:, :, ::2].to(dev, dt)).sum()
         if tmean:
             loss = loss + (xbar * gb.to(dev, dt)).sum()
         loss.backward()
         res = dict(out=out, dx1=tx1.grad)
+        if even is not None:
+            res['even'] = even
         if tmean:
             res['xbar'] = xbar
         if tx2 is not None:
@@ -577,7 +661,7 @@ def test_fuse_out(n, C, T, V, mode, tmean, flags):
         return res
 
     got = run(K, torch.float32, DEV)
-    ref = run(R, torch.float64, 'cpu')
+    ref = run(R, torch.float64, ref_dev(n))
     for k, v in ref.items():
         # elementwise fp32 + sums over <= n*T*V terms: 1e-5 relative L2
         assert rel(got[k].detach().cpu(), v.detach()) < 1e-5, (k, rel(got[k].detach().cpu(), v.detach()))
@@ -599,6 +683,10 @@ def _drop_record_of_last_call(p):
     (2, 16, 7, 18, 'res_plain', 3, 'pool')])
 @pytest.mark.parametrize('p', [0.5, 0.1])
 def test_fuse_out_dropout(n, C, T, V, mode, flags, form, p):
+    check_fuse_out_dropout(n, C, T, V, mode, flags, form, p)
+
+
+def check_fuse_out_dropout(n, C, T, V, mode, flags, form, p):
     """Dropout inside fuse_out (csrc/dropout.h; reference: nn.Dropout behind the temporal unit's BatchNorm, tcn.py:30,33):
     no mask tensor exists in the product — the test asks dsgcn_dropout_mask for the multipliers the call used and checks
     (i) the multipliers: {0, 1/(1-p)}, keep rate within 5 sigma; (ii) forward AND backward (regenerated masks) against fp64
@@ -641,10 +729,11 @@ def test_fuse_out_dropout(n, C, T, V, mode, flags, form, p):
     N = m.numel()
     assert abs(keep.float().mean().item() - (1 - p)) < 5 * (p * (1 - p) / N) ** 0.5
     # fp64 reference with the same multipliers
-    md = m.double().cpu()
-    rx1, rx2 = mk(x1, 'cpu', torch.float64), mk(x2, 'cpu', torch.float64)
-    ra1 = (mk(a1[0], 'cpu', torch.float64), mk(a1[1], 'cpu', torch.float64))
-    ra2 = None if a2 is None else (mk(a2[0], 'cpu', torch.float64), mk(a2[1], 'cpu', torch.float64))
+    rdev = ref_dev(n)
+    md = m.double().to(rdev)
+    rx1, rx2 = mk(x1, rdev, torch.float64), mk(x2, rdev, torch.float64)
+    ra1 = (mk(a1[0], rdev, torch.float64), mk(a1[1], rdev, torch.float64))
+    ra2 = None if a2 is None else (mk(a2[0], rdev, torch.float64), mk(a2[1], rdev, torch.float64))
     v = rx1 * ra1[0].view(1, -1, 1, 1) + ra1[1].view(1, -1, 1, 1)
     if flags & 2:
         v = v.relu()
@@ -653,16 +742,16 @@ def test_fuse_out_dropout(n, C, T, V, mode, flags, form, p):
         v = v + (rx2 * ra2[0].view(1, -1, 1, 1) + ra2[1].view(1, -1, 1, 1) if ra2 is not None else rx2)
     ro = v.relu() if flags & 1 else v
     if form == 'pool':
-        rloss = (ro.mean((2, 3)) * gp.double()).sum()
+        rloss = (ro.mean((2, 3)) * gp.double().to(rdev)).sum()
         refs = dict(pm=ro.mean((2, 3)))
     elif form == 'tee2':
-        rloss = (ro * go.double()).sum() + (ro[:, :, ::2] * ge.double()).sum()
+        rloss = (ro * go.double().to(rdev)).sum() + (ro[:, :, ::2] * ge.double().to(rdev)).sum()
         refs = dict(out=ro, even=ro[:, :, ::2])
     else:
-        rloss = (ro * go.double()).sum()
+        rloss = (ro * go.double().to(rdev)).sum()
         refs = dict(out=ro)
         if form == 'tmean':
-            rloss = rloss + (ro.mean(2) * gb.double()).sum()
+            rloss = rloss + (ro.mean(2) * gb.double().to(rdev)).sum()
             refs['xbar'] = ro.mean(2)
     rloss.backward()
     for k, want in refs.items():
@@ -748,6 +837,10 @@ def test_fuse_out_even_frame_output(n, C, T, V, streams):
                                             (1, 64, 4, 25, 1), (2, 36, 8, 5, 1), (2, 64, 100, 17, 1)])
 @pytest.mark.parametrize('fused', ['1', '0', 'split'])
 def test_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
+    check_temporal_ms(n, C, T, V, stride, fused, monkeypatch)
+
+
+def check_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
     """fused '1': the one-launch-per-direction stage (csrc/tms.hip) wherever the shape is eligible; '0': the staged chain
     (branch_act -> tapconv -> combine); 'split': the split layout (csrc/tmsplit.hip: no (V+1)-column tensors) wherever
     the shape is eligible (V odd, T % 4 == 0; stride 2: T % 8 == 0) — ineligible shapes are skipped, not silently run on
@@ -799,7 +892,7 @@ def test_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
         return res
 
     got = run(K, torch.float32, DEV)
-    ref = run(R, torch.float64, 'cpu')
+    ref = run(R, torch.float64, ref_dev(n))
     for k, v in ref.items():
         # three HIP stages (branch_act, the fp32-MFMA tap kernels, combine + statistics): 5e-5 relative L2 against fp64
         assert rel(got[k].detach().cpu(), v.detach()) < 5e-5, (k, rel(got[k].detach().cpu(), v.detach()))
@@ -850,6 +943,10 @@ def test_temporal_ms_split_at_full_size(C, T, stride, monkeypatch):
     (128, 3, 64, 64, 25, False, True), (128, 3, 128, 32, 25, False, True), (128, 3, 256, 16, 25, False, True),
     (128, 3, 64, 64, 25, True, True), (128, 3, 256, 16, 25, True, True)])
 def test_aggregate_sum(n, K, Co, T, V, shared, bn):
+    check_aggregate_sum(n, K, Co, T, V, shared, bn)
+
+
+def check_aggregate_sum(n, K, Co, T, V, shared, bn):
     g = torch.Generator().manual_seed(Co + T + V)
     p = _rand(g, n, K * Co, T, V)
     adj = _rand(g, K, V, V, scale=0.3) if shared else _rand(g, n, K * Co, V, V, scale=0.3)
@@ -881,6 +978,10 @@ def test_aggregate_sum(n, K, Co, T, V, shared, bn):
 @pytest.mark.parametrize('n,K,Co,T,V', [(2, 3, 16, 64, 25), (3, 3, 32, 32, 25), (2, 3, 8, 130, 17), (128, 3, 64, 64, 25),
                                         (128, 3, 256, 16, 25)])
 def test_aggregate_sum_subset_major_adjacency(n, K, Co, T, V):
+    check_aggregate_sum_subset_major_adjacency(n, K, Co, T, V)
+
+
+def check_aggregate_sum_subset_major_adjacency(n, K, Co, T, V):
     """The per-sample, per-channel adjacency handed over as (K, n, Co, V, V) (what ctr_topology's one-conv form writes): the
     same launches with other strides — bit-identical to the (n, K*Co, V, V) call on the permuted tensor, gradient included."""
     g = torch.Generator().manual_seed(Co + T)
@@ -907,6 +1008,10 @@ def test_aggregate_sum_subset_major_adjacency(n, K, Co, T, V):
                                        (128, 64, 64, 25), (128, 256, 256, 25)])
 @pytest.mark.parametrize('subset_major', [False, True])
 def test_ctr_topology(n, Ci, Co, V, subset_major):
+    check_ctr_topology(n, Ci, Co, V, subset_major)
+
+
+def check_ctr_topology(n, Ci, Co, V, subset_major):
     """subset_major: Ahat as (K, n, Co, V, V) through the one-conv form of the classic refinement (conv4 + alpha + A as one
     1x1 conv over [d | A[k] | 1]); the plain call keeps the (n, K*Co, V, V) contract and the separate affine pass."""
     g = torch.Generator().manual_seed(Ci + Co)
@@ -1088,6 +1193,10 @@ def test_ctr_operands_one_launch_per_step_is_bit_identical(monkeypatch):
                                                (2, 32, 21, 17, 2, 5), (1, 16, 9, 18, 1, 3)])
 @pytest.mark.parametrize('fused', ['1', '0'])
 def test_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
+    check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch)
+
+
+def check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
     """MSTCN's stage: BN+ReLU, two dilated (k,1) convs, max-pool, strided copy, closing BatchNorm statistics."""
     monkeypatch.setattr(K, 'FUSED_TEMPORAL', fused)
     g = torch.Generator().manual_seed(C + T + stride)
@@ -1120,7 +1229,7 @@ def test_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
         return res
 
     got = run(K_, torch.float32, DEV)
-    ref = run(R, torch.float64, 'cpu')
+    ref = run(R, torch.float64, ref_dev(n))
     for k, v in ref.items():
         # fp32 MFMA accumulation over <= 5*64 (fwd) / n*T*V (wgrad, statistics) terms: 2e-5 relative L2
         assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
@@ -1131,6 +1240,10 @@ def test_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
     (1, 256, 256, 8, 25, 1, 9, 1, True), (2, 40, 72, 21, 17, 2, 9, 1, False), (2, 16, 16, 12, 18, 1, 3, 2, True),
     (2, 70, 130, 10, 25, 1, 5, 2, True)])
 def test_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
+    check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn)
+
+
+def check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
     """unit_tcn's dense (k,1) temporal conv (ST-GCN: k=9) + the statistics of the BatchNorm that follows."""
     g = torch.Generator().manual_seed(Ci + Co + T)
     h = _rand(g, n, Ci, T, V)
@@ -1156,15 +1269,25 @@ def test_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
         return res
 
     got = run(K_, torch.float32, DEV)
-    ref = run(R, torch.float64, 'cpu')
+    ref = run(R, torch.float64, ref_dev(n))
     for k, v in ref.items():
         # fp32 MFMA accumulation over <= 9*256 (fwd) / n*T*V (wgrad) terms: 2e-5 relative L2
         assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
 
 
 def test_tmean():
-    x = torch.randn(4, 3, 20, 25)
-    assert rel(K_.tmean(x.cuda()).cpu(), x.mean(2)) < 1e-6
+    check_tmean(4, 3, 20, 25, True)
+
+
+def check_tmean(n, C, T, V, ld):
+    """ld: True (rows of V joints) or an int >= V (rows zero-padded to ld, the layout dynadj reads)."""
+    x = torch.randn(n, C, T, V, generator=torch.Generator().manual_seed(n + T))
+    got = K_.tmean(x.cuda(), ld)
+    want = x.to(ref_dev(n), torch.float64).mean(2)
+    if ld is not True:
+        assert got.shape == (n, C, ld) and not got[..., V:].any()
+        got = got[..., :V]
+    assert rel(got.cpu(), want) < 1e-6
 
 
 @pytest.mark.parametrize('R,C', [(32768, 25), (1664, 192), (128, 48), (7, 3), (4096, 70000 // 64)])
@@ -1534,6 +1657,10 @@ def test_wsplit_images_batched_per_step_and_never_stale():
                                              (32, 2, 256, 400, 0.5, True), (5, 1, 96, 3, 1.0, False),
                                              (7, 3, 70, 11, 2.0, True), (1, 2, 256, 60, 1.0, True)])
 def test_head_loss(N, M, C, K, lw, bias):
+    check_head_loss(N, M, C, K, lw, bias)
+
+
+def check_head_loss(N, M, C, K, lw, bias):
     """Person mean + Linear + cross entropy + accuracies (csrc/head.hip) against torch in fp64: loss and gradients to 2e-6
     of their norm, the accuracies EXACT (a rank is an integer; ties are planted to pin the stable-argsort rule)."""
     g = torch.Generator().manual_seed(N * 31 + K)
@@ -1607,6 +1734,10 @@ def test_bn_running_update_matches_batch_norm():
     (2, 16, 9, 17, 'res_affine', 3), (2, 16, 8, 25, 'res_affine', 0),
     (128, 256, 25, 25, 'res_plain', 1)])                     # the bench step's last block
 def test_fuse_out_pool(n, C, T, V, mode, flags):
+    check_fuse_out_pool(n, C, T, V, mode, flags)
+
+
+def check_fuse_out_pool(n, C, T, V, mode, flags):
     """The last block's output as plane means only (no activation written) against mean(fuse_out) in fp64, and — same
     launches, same order of operations — bit-identical to the mean the full kernel's output gives when summed the same way
     is NOT claimed: torch's mean runs in another order, so 2e-6 of the norm."""
@@ -1685,6 +1816,10 @@ def test_sgd_step_matches_torch(n, mom, wd, nesterov):
                                                (5, 1, 7, 18, 2, 'MVC'), (2, 3, 30, 25, 9, 'VC')])
 @pytest.mark.parametrize('affine', [True, False])
 def test_data_bn(N, M, T, V, C, bn_type, affine):
+    check_data_bn(N, M, T, V, C, bn_type, affine)
+
+
+def check_data_bn(N, M, T, V, C, bn_type, affine):
     """The backbones' input BatchNorm1d (dgstgcn.py:158-164) in two launches, no permute copies: output, parameter
     gradients and the buffer updates against nn.BatchNorm1d in fp64 on the permuted clip; then eval mode on the buffers."""
     import torch.nn as nn
