@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import kernels
 from .builder import BACKBONES
-from .gcn_units import dggcn, dgphgcn1, unit_aagcn, unit_ctrgcn, unit_ctrhgcn, unit_gcn, flush_running_stats
+from .gcn_units import dggcn, dghgcn, dgphgcn1, unit_aagcn, unit_ctrgcn, unit_ctrhgcn, unit_gcn, flush_running_stats
 from .graph import Graph
 from .tcn_units import MSTCN, dgmstcn, msmlp, mstcn, unit_tcn, unitmlp
 
@@ -128,6 +128,8 @@ class DGBlock(_FusedBlock):
             self.gcn = dggcn(in_channels, out_channels, A, **gcn_kwargs)
         elif gcn_type == 'dgphgcn1':
             self.gcn = dgphgcn1(in_channels, out_channels, A, edge_type, node_type, **gcn_kwargs)
+        elif gcn_type == 'dghgcn':                   # DGSTGCN's default unit (dgstgcn.py:40)
+            self.gcn = dghgcn(in_channels, out_channels, A, edge_type, node_type, **gcn_kwargs)
         else:
             raise NotImplementedError(f'gcn_type={gcn_type} is outside the DS-GCN hot path (SURVEY §8f)')
         self.relu = nn.ReLU()

@@ -347,6 +347,116 @@ class dggcn(nn.Module):
         return out
 
 
+class dghgcn(nn.Module):
+    """DS-GCN's "every subset is semantic" unit, ``DGSTGCN``'s default ``gcn_type`` (reference: pyskl/models/gcns/utils/
+    gcn.py:1586-1806; dgstgcn.py:40).  All K subsets get node-typed projections (``node_attention``: conv1 / conv2 have
+    K*mid*P rows, joint v keeps row (k*mid + c)*P + type(v)) and the edge-typed attention (``edge_attention``: one linear
+    over all K*mid channels, each joint pair keeps the variant of its edge class, ``add_type`` adds the plain difference):
+    ``Ahat_k = A_k + alpha_k tanh(D_k) + beta_k softmax_u(sum_c x1_k x2_k)`` with alpha_k = alpha[0] unless subset_wise.
+    Adjacency through ``kernels.dynadj_typed`` (K-C projections, typed K-B); the rest is ``dggcn``'s chain.  Implemented:
+    the four flags in every combination, ctr='T', ada='T', tanh / softmax, BN / ReLU, K = 3, V <= 32, mid <= 64."""
+
+    def __init__(self, in_channels, out_channels, A, edge_type, node_type, ratio=0.25, ctr='T', ada='T',
+                 node_attention=False, edge_attention=False, ada_attention=False, target_specific=False, add_type=False,
+                 num_types=5, edge_num=15, subset_wise=False, ada_act='softmax', ctr_act='tanh', norm='BN', act='ReLU'):
+        super().__init__()
+        assert ada_act in ['tanh', 'relu', 'sigmoid', 'softmax']
+        assert ctr_act in ['tanh', 'relu', 'sigmoid', 'softmax']
+        assert ctr in [None, 'NA', 'T']
+        assert ada in [None, 'NA', 'T']
+        for flag, bad in (('ada_attention', ada_attention), ('target_specific', target_specific),
+                          ("ctr (only 'T')", ctr != 'T'), ("ada (only 'T')", ada != 'T'),
+                          ("ctr_act (only 'tanh')", ctr_act != 'tanh'), ("ada_act (only 'softmax')", ada_act != 'softmax')):
+            if bad:
+                raise NotImplementedError(f'dghgcn: {flag} has no HIP path')
+        _check_act(act)
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_subsets = K = A.size(0)
+        if K != 3:
+            raise NotImplementedError(f'dghgcn: num_subsets (A.size(0)) = {K}: the typed K-B implements K = 3')
+        V = A.size(-1)
+        if V > 32:
+            raise NotImplementedError(f'dghgcn: {V} joints: the typed K-B implements V <= 32')
+        self.node_attention, self.edge_attention, self.add_type = node_attention, edge_attention, add_type
+        self.subset_wise = subset_wise
+        self.num_types, self.edge_num = num_types, edge_num
+        if ratio is None:
+            ratio = 1 / K
+        self.ratio = ratio
+        self.mid_channels = mid = int(ratio * out_channels)
+        if not 0 < mid <= 64:
+            raise NotImplementedError(f'dghgcn: ratio {ratio} gives mid = {mid}: the typed K-B implements 1 <= mid <= 64')
+        if edge_attention and edge_num > 16:
+            raise NotImplementedError(f'dghgcn: edge_num = {edge_num}: the typed K-B implements up to 16 edge classes')
+        nt = torch.as_tensor(node_type).to(torch.int32).reshape(-1).contiguous()
+        et = torch.as_tensor(edge_type).to(torch.int32).reshape(-1).contiguous()
+        if node_attention and not (nt.numel() == V and 0 <= int(nt.min()) and int(nt.max()) < num_types):
+            raise ValueError(f'dghgcn: node_type must hold {V} values in [0, {num_types})')
+        if edge_attention and not (et.numel() == V * V and 0 <= int(et.min()) and int(et.max()) < edge_num):
+            raise ValueError(f'dghgcn: edge_type must hold {V}x{V} values in [0, {edge_num})')
+        self.register_buffer('node_type_idx', nt, persistent=False)
+        self.register_buffer('edge_type_idx', et, persistent=False)
+        P = num_types if node_attention else 1
+        # parameter creation order follows the reference ctor (same RNG consumption, same key order)
+        self.A = nn.Parameter(A.clone())
+        self.pre = nn.Sequential(nn.Conv2d(in_channels, mid * K, 1), _norm_layer(norm, mid * K), nn.ReLU())
+        self.post = nn.Conv2d(mid * K, out_channels, 1)
+        self.alpha = nn.Parameter(torch.zeros(K))
+        self.beta = nn.Parameter(torch.zeros(K))
+        self.conv1 = nn.Conv2d(in_channels, K * mid * P, 1)
+        self.conv2 = nn.Conv2d(in_channels, K * mid * P, 1)
+        if edge_attention:
+            self.edge_linears = nn.Conv2d(K * mid, edge_num * K * mid, 1)
+        if in_channels != out_channels:
+            self.down = nn.Sequential(nn.Conv2d(in_channels, out_channels, 1), _norm_layer(norm, out_channels))
+        else:
+            self.down = None
+        self.bn = _norm_layer(norm, out_channels)
+
+    def flat_groups(self):
+        """(see dgmstcn.flat_groups) the two mean-pooled projections run as one conv over their stacked weights"""
+        return [[self.conv1.weight, self.conv2.weight], [self.conv1.bias, self.conv2.bias]]
+
+    def fusable_pairs(self):
+        return [(self.post, self.bn)]
+
+    def adjacency(self, xbar):
+        """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V or 32)."""
+        a = self.alpha if self.subset_wise else self.alpha[0].expand(3)
+        b = self.beta if self.subset_wise else self.beta[0].expand(3)
+        el = self.edge_linears if self.edge_attention else None
+        return kernels.ops().dynadj_typed(
+            xbar, self.A, a, b, self.conv1.weight.flatten(1), self.conv1.bias, self.conv2.weight.flatten(1),
+            self.conv2.bias, None if el is None else el.weight.flatten(1), None if el is None else el.bias,
+            self.node_type_idx, self.edge_type_idx, self.num_types if self.node_attention else 1, self.add_type)
+
+    def forward_deferred(self, x, xbar=None, x_res=None):
+        """xbar: the time mean of x, joint rows padded to 32 (the previous block's fuse_out); computed here otherwise."""
+        ops = kernels.ops()
+        x_res = x if x_res is None else x_res
+        if xbar is None:
+            xbar = ops.tmean(x, 32)
+        ahat = self.adjacency(xbar)
+        zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
+        y = ops.aggregate(zp, ap, True, ahat)
+        zo, _, ao = conv_bn(y, None, None, None, False, self.post, 1, False, self.bn)
+        if self.down is None:
+            return Deferred(zo, ao, x_res, None, True)
+        zd, _, ad = conv_bn(x_res, None, None, None, False, self.down[0], 1, False, self.down[1])
+        return Deferred(zo, ao, zd, ad, True)
+
+    def forward(self, x, A=None):
+        out = self.forward_deferred(x).materialize()
+        flush_running_stats()
+        return out
+
+    def init_weights(self):
+        _kaiming_conv_init(self)
+        nn.init.constant_(self.bn.weight, 1e-6)
+        nn.init.constant_(self.bn.bias, 0)
+
+
 class unit_aagcn(nn.Module):
     """2s-AGCN / AAGCN spatial unit (reference: pyskl/models/gcns/utils/gcn.py:349-460): per subset a data-dependent
     topology ``A_i + alpha * tanh(conv_a_i(x)^T conv_b_i(x) / (inter_c * T))`` per sample, ``y = sum_i conv_d_i(x A_i)``,

@@ -859,6 +859,95 @@ def dynadj(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, node_type, ed
                          bool(single_use), host)
 
 
+class _TypedSelect(torch.autograd.Function):
+    """proj (n, 2*KM*P, ld) [conv1 | conv2] -> x12 (n, KM, 2, 32): the node-typed row of each joint (P = 1: a re-layout)."""
+
+    @staticmethod
+    def forward(ctx, proj, node_type, KM, P, V):
+        _require_cuda(proj)
+        proj = _f32c(proj)
+        n, _, ld = proj.shape
+        x12 = torch.empty((n, KM, 2, 32), device=proj.device, dtype=torch.float32)
+        native.check(native.lib().dsgcn_dyntyped_select_fwd(_ptr(proj), _ptr(node_type), _ptr(x12), n, KM, P, V, ld,
+                                                            _stream()), 'dsgcn_dyntyped_select_fwd')
+        ctx.save_for_backward(node_type)
+        ctx.dims = (tuple(proj.shape), KM, P, V)
+        return x12
+
+    @staticmethod
+    def backward(ctx, dx12):
+        node_type, = ctx.saved_tensors
+        shape, KM, P, V = ctx.dims
+        dx12 = _f32c(dx12)
+        dproj = torch.empty(shape, device=dx12.device, dtype=torch.float32)
+        native.check(native.lib().dsgcn_dyntyped_select_bwd(_ptr(dx12), _ptr(node_type), _ptr(dproj), shape[0], KM, P, V,
+                                                            shape[2], _stream()), 'dsgcn_dyntyped_select_bwd')
+        return dproj, None, None, None, None
+
+
+class _TypedAdj(torch.autograd.Function):
+    """x12 (n, 3*mid, 2, 32), pq (n, E*3*mid, 2, 32) or None -> Ahat (n, 3*mid, V, V) (typed K-B, one launch each way)."""
+
+    @staticmethod
+    def forward(ctx, x12, pq, be, A, alpha, beta, edge_type, flags, defer_ok):
+        _require_cuda(x12, A)
+        x12, pq, be, A, alpha, beta = [_f32c(t) for t in (x12, pq, be, A, alpha, beta)]
+        n, KM = x12.shape[:2]
+        mid, V = KM // 3, A.shape[-1]
+        E = pq.shape[1] // KM if pq is not None else 0
+        ahat = torch.empty((n, KM, V, V), device=x12.device, dtype=torch.float32)
+        rc = native.lib().dsgcn_dyntyped_fwd(_ptr(x12), _ptr(pq), _ptr(be), _ptr(A), _ptr(alpha), _ptr(beta),
+                                             _ptr(edge_type), _ptr(ahat), n, mid, V, E, flags, _stream())
+        native.check(rc, 'dsgcn_dyntyped_fwd')
+        ctx.save_for_backward(x12, pq, be, alpha, beta, edge_type)
+        ctx.dims = (n, mid, V, E, flags)
+        ctx.defer_ok = defer_ok
+        return ahat
+
+    @staticmethod
+    def backward(ctx, dahat):
+        x12, pq, be, alpha, beta, edge_type = ctx.saved_tensors
+        n, mid, V, E, flags = ctx.dims
+        dahat = _f32c(dahat)
+        lib = native.lib()
+        dd = torch.empty_like(dahat)
+        dx12 = torch.empty_like(x12)
+        dpq = torch.empty_like(pq) if pq is not None else None
+        pstride = lib.dsgcn_dyntyped_partial_stride(mid, V, E, flags)
+        ppar = torch.empty((n, pstride), device=x12.device, dtype=torch.float32)
+        rc = lib.dsgcn_dyntyped_bwd(_ptr(x12), _ptr(pq), _ptr(be), _ptr(alpha), _ptr(beta), _ptr(edge_type), _ptr(dahat),
+                                    _ptr(dd), _ptr(dx12), _ptr(dpq), _ptr(ppar), pstride, n, mid, V, E, flags, _stream())
+        native.check(rc, 'dsgcn_dyntyped_bwd')
+        red = param_colsum(ppar, bool(ctx.defer_ok))                       # ordered sum over samples: deterministic
+        o = 3 * V * V
+        dA, dalpha, dbeta = red[:o].view(3, V, V), red[o:o + 3], red[o + 3:o + 6]
+        dbe = red[o + 6:o + 6 + E * 3 * mid] if pq is not None else None
+        return dx12, dpq, dbe, dA, dalpha, dbeta, None, None, None
+
+
+def dynadj_typed(xbar, A, alpha, beta, w1, b1, w2, b2, we, be, node_type, edge_type, P, add_type, single_use=True):
+    """Dynamic adjacency of ``dghgcn``: node-typed projections (P node types; P = 1: untyped) and edge-typed attention
+    (``we`` (E*3*mid, 3*mid), ``be``; None: no edge attention) on all three subsets.  conv1 / conv2 are one K-C launch on
+    xbar padded to 32 joints (as in ``dynadj``), the node-typed select one small launch, the edge linear one K-C launch over
+    [x1 | x2] viewed as a (n, 3*mid, 2, 32) clip, then the typed K-B.  The gradients of x12 from K-B and from the edge
+    linear's K-C backward meet in autograd; the parameter partials are ordered column sums."""
+    n = xbar.shape[0]
+    V = A.shape[-1]
+    R = w1.shape[0]
+    KM = R // P
+    w_all = cat_rows([w1, w2])
+    b_all = cat_rows([b1, b2])
+    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
+    proj = pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
+    x12 = _TypedSelect.apply(proj.view(n, 2 * R, xpad.shape[-1]), node_type, KM, P, V)
+    pq, flags = None, 0
+    if we is not None:
+        pq = pwconv(x12, None, None, None, False, we, None, 1, False)[0]
+        flags = 1 | (2 if add_type else 0)
+    defer_ok = bool(single_use) and _leafish(A, alpha, beta, be)
+    return _TypedAdj.apply(x12, pq, be if we is not None else None, A, alpha, beta, edge_type, flags, defer_ok)
+
+
 # ---------------------------------------------------------------------------------------------
 # K-C  1x1 channel mix + train-mode BN statistics / deferred affine
 # ---------------------------------------------------------------------------------------------

@@ -74,6 +74,29 @@ int dsgcn_dynadj_bwd_jobs(const float* proj, const float* alpha, const float* be
                           float* ppar, int pstride, int n, int mid, int V, int ld, int P, int E,
                           const dsgcn_bn_coef_job* jobs, int njobs, void* stream);
 
+/* K-B typed: the dynamic adjacency of dghgcn (gcn.py:1586-1806), node-typed projections and edge-typed attention on all
+ * K = 3 subsets.  Rows are padded to 32 joints.
+ *   select: proj (n, 2*KM*P, ld) [conv1 | conv2], row r*P + p (r = k*mid + c; P = 1: untyped) -> x12 (n, KM, 2, 32),
+ *           slot 0 = conv1 row r*P + node_type[v], slot 1 = conv2 (joints >= V zero); its backward writes every dproj
+ *           element (zero outside the selected rows).  KM = 3*mid.
+ *   fwd:    x12, pq (n, E*3*mid, 2, 32) = edge_linears . x12 without its bias (row (k*E + e)*mid + c), be (E*3*mid),
+ *           A (3,V,V), alpha, beta (3), edge_type (V*V) int32 in [0,E) -> ahat (n, 3*mid, V, V).  flags: 1 = edge
+ *           attention (pq, be, edge_type read), 2 = add_type.  V <= 32, mid <= 64, E <= 16.
+ *   bwd:    dd_ws workspace (n, 3*mid, V, V); outputs dx12 (softmax-Gram and direct terms; padding zero), dpq (edge only:
+ *           d of pq, every element written) and ppar (n, pstride >= dsgcn_dyntyped_partial_stride): per-sample partials
+ *           [sum_c dAhat (3*V*V) | dalpha (3) | dbeta (3) | dbe (E*3*mid, edge only)], summed by dsgcn_colsum. */
+int dsgcn_dyntyped_select_fwd(const float* proj, const int* node_type, float* x12, int n, int KM, int P, int V, int ld,
+                              void* stream);
+int dsgcn_dyntyped_select_bwd(const float* dx12, const int* node_type, float* dproj, int n, int KM, int P, int V, int ld,
+                              void* stream);
+int dsgcn_dyntyped_partial_stride(int mid, int V, int E, int flags);
+int dsgcn_dyntyped_fwd(const float* x12, const float* pq, const float* be, const float* A, const float* alpha,
+                       const float* beta, const int* edge_type, float* ahat, int n, int mid, int V, int E, int flags,
+                       void* stream);
+int dsgcn_dyntyped_bwd(const float* x12, const float* pq, const float* be, const float* alpha, const float* beta,
+                       const int* edge_type, const float* dahat, float* dd_ws, float* dx12, float* dpq, float* ppar,
+                       int pstride, int n, int mid, int V, int E, int flags, void* stream);
+
 /* Block output (materialise once): out = relu?(x1*s1+h1 (+ x2*s2+h2 | + x2)), xbar = mean_t out (optional).
  * Replaces BN + residual add + ReLU of dgstgcn.py:63-65 / tcn.py:427 and x.mean(-2) of gcn.py:2246.
  * relu: bit 0 = the outer ReLU, bit 1 = a ReLU on the first term before the add (CTR-GCN: msg3d_utils.py:139-141
