@@ -13,6 +13,7 @@ import dsgcn_amd as D
 import dghgcn_fp64 as F
 from test_dghgcn_host import CASES, Z, make_unit, unit_inputs
 from test_oracle_golden import GOLD, load, rel, sd_of
+import test_kernels_gpu as KG
 
 pytestmark = pytest.mark.gpu
 
@@ -114,40 +115,7 @@ FULL_CASES = ([(c, 'node_edge') for c in FULL] + [(c, f) for c in ((64, 64, 0.12
 def test_typed_kb_full_size_vs_fp64(case, flags):
     """n = 128, V = 25: Ahat, the input gradient (of the time mean) and every parameter gradient of the adjacency path
     (K-C projections + typed select + K-C edge linear + typed K-B) against the fp64 restatement."""
-    ci, co, ratio = case
-    na, ea, at = {'node_edge': (True, True, False), 'plain': (False, False, False), 'node': (True, False, False),
-                  'edge': (False, True, False), 'add_type': (True, True, True)}[flags]
-    g = D.Graph(layout='nturgb+d', mode='spatial')
-    torch.manual_seed(7)
-    np.random.seed(7)
-    A = torch.tensor(np.asarray(D.Graph(layout='nturgb+d', mode='random', num_filter=3, init_off=.04, init_std=.02).A),
-                     dtype=torch.float32)
-    m = D.dghgcn(ci, co, A, torch.tensor(g.edge_type), torch.tensor(g.node_type), ratio=ratio, node_attention=na,
-                 edge_attention=ea, add_type=at, subset_wise=True)
-    with torch.no_grad():
-        m.alpha.normal_(0, 0.5)
-        m.beta.normal_(0, 0.5)
-    m = m.cuda()
-    n, V = 128, 25
-    gen = torch.Generator().manual_seed(11)
-    xbar = torch.randn(n, ci, V, generator=gen).cuda().requires_grad_()
-    dah = torch.randn(n, 3 * m.mid_channels, V, V, generator=gen).cuda()
-    ahat = m.adjacency(xbar)
-    (ahat * dah).sum().backward()
-    names = ['A', 'alpha', 'beta', 'conv1.weight', 'conv1.bias', 'conv2.weight', 'conv2.bias'] + (
-        ['edge_linears.weight', 'edge_linears.bias'] if ea else [])
-    params = dict(m.named_parameters())
-    p64 = {k: params[k].detach().double().requires_grad_() for k in names}
-    x64 = xbar.detach().double().requires_grad_()
-    want = F.adjacency(x64, p64['A'], p64['alpha'], p64['beta'], p64['conv1.weight'], p64['conv1.bias'],
-                       p64['conv2.weight'], p64['conv2.bias'], p64.get('edge_linears.weight'), p64.get('edge_linears.bias'),
-                       m.node_type_idx, m.edge_type_idx, m.num_types if na else 1, at, True)
-    (want * dah.double()).sum().backward()
-    assert rel(ahat.detach().cpu(), want.detach().cpu()) < 1e-5, rel(ahat.detach().cpu(), want.detach().cpu())
-    assert rel(xbar.grad.cpu(), x64.grad.cpu()) < 1e-4, rel(xbar.grad.cpu(), x64.grad.cpu())
-    for k in names:
-        e = rel(params[k].grad.cpu(), p64[k].grad.cpu())
-        assert e < 1e-4, (k, e)
+    KG.check_typed_kb(case, flags)
 
 
 DGH_CFG = dict(

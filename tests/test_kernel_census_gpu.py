@@ -8,6 +8,7 @@ record is a key of the arguments that decide the kernel and its tiling, plus the
 more than one.  FULL_SIZE_CASES must hold exactly the recorded keys: a shape or path the steps start to run and no test
 covers fails the census, and so does a table entry no step runs any more.  The fp64 comparisons below are parametrized
 from the same table (the per-op helpers of tests/test_kernels_gpu.py, with the bars of the tests they came from)."""
+import copy
 import gc
 import inspect
 
@@ -58,7 +59,18 @@ def _k_dynadj(a):
     n, Ci, ld = _shape(a['xbar'])
     V = int(a['A'].shape[-1])
     mid = int(a['we'].shape[1])
-    return (n, Ci, mid, V, ld, a['host'] is not None)
+    key = (n, Ci, mid, V, ld, a['host'] is not None)
+    # single_use=False (dggcn: A feeds two calls, the parameter sums are never deferred) extends the key; the default keeps
+    # the key the BASELINE steps have always recorded
+    return key if a['single_use'] else key + (False,)
+
+
+def _k_dynadj_typed(a):
+    n, Ci, ld = _shape(a['xbar'])
+    V = int(a['A'].shape[-1])
+    KM = int(a['w1'].shape[0]) // int(a['P'])
+    E = int(a['we'].shape[0]) // KM if a['we'] is not None else 0
+    return (n, Ci, KM, V, ld, int(a['P']), E, bool(a['add_type']) and E > 0, bool(a['single_use']))
 
 
 def _pw_paths(n, Ci, Co, T, V, stride, aug):
@@ -89,8 +101,15 @@ def _k_ctr_topology(a):
     Kk = int(a['A'].shape[0])
     one_conv = (bool(a['subset_major']) and K.CTR_ONE_CONV and a['beta'] is None and not a['edge'] and
                 a['alpha'].numel() == 1 and Kk <= 4)
-    return (n, Ci, int(a['w4'][0].shape[0]), V, Kk, int(a['w1'].shape[0]) // Kk, bool(a['subset_major']),
-            'one_conv' if one_conv else 'per_subset')
+    Rr = int(a['w1'].shape[0]) // Kk
+    key = (n, Ci, int(a['w4'][0].shape[0]), V, Kk, Rr, bool(a['subset_major']), 'one_conv' if one_conv else 'per_subset')
+    edge = a['edge'] or {}
+    if a['alpha'].numel() == 1 and a['beta'] is None and not edge:
+        return key                                  # the classic unit (unit_ctrgcn)
+    # unit_ctrhgcn: + (alpha elements, Gram term, edge subsets, edge classes E)
+    E = {int(we.shape[0]) // Rr for we, _, _ in edge.values()}
+    assert len(E) <= 1, E
+    return key + ((int(a['alpha'].numel()), a['beta'] is not None, tuple(sorted(edge)), E.pop() if E else 0),)
 
 
 def _k_tconv_bn(a):
@@ -115,6 +134,28 @@ def _k_temporal(a, path):
     n, C, T, V = _shape(a['z'])
     return (n, C, T, V, int(a['stride']), _cfg(a['branch_cfg']), tuple(int(w) for w in a['widths']), int(a['n_act']),
             bool(a['want_bn']), path)
+
+
+def _k_temporal_mlp(a):
+    n, C, T, V = _shape(a['z'])
+    return (n, C, T, V, int(a['stride']), _cfg(a['branch_cfg']), tuple(int(w) for w in a['widths']), int(a['n_act']),
+            int(a['dw_w'].shape[1]), bool(a['merge_after']), bool(a['want_bn']))
+
+
+def _k_temporal_unitmlp(a):
+    n, C, T, V = _shape(a['h'])
+    tw = a['tw']
+    return (n, C, T, V, int(a['stride']), int(a['dw_w'].shape[1]), tuple(sorted({int(d) for d in a['dw_dil'].tolist()})),
+            int(tw.shape[2]) if tw is not None else 0, int(a['tdil']) if tw is not None else 0, bool(a['merge_after']),
+            bool(a['want_bn']))
+
+
+def _k_gram(a):
+    return _shape(a['a'])
+
+
+def _k_gate(a):
+    return _shape(a['y']) + (int(a['mode']), int(a['rmode']))
 
 
 def _k_fuse_out(a):
@@ -164,10 +205,28 @@ KEYS = dict(aggregate=_k_aggregate, aggregate_sum=_k_aggregate_sum, dynadj=_k_dy
             pwconv_group=_k_pwconv_group, ctr_topology=_k_ctr_topology, tconv_bn=_k_tconv_bn, tconv=_k_tconv,
             temporal_ms=None, temporal_branches_bn=None, fuse_out=_k_fuse_out, fuse_out_pool=_k_fuse_out_pool,
             head_loss=_k_head_loss, data_bn=_k_data_bn, tmean=_k_tmean, tee3=_k_tee3,
-            bn_running_update=_k_bn_running_update, strided_frames=_k_strided_frames)
-# public ops that the BASELINE steps do not reach (AAGCN's gates, the MLP temporal units of the shipped configs): a call
-# of one of them fails the census until it has a key
-UNKEYED = ('gram', 'gate', 'temporal_mlp_bn', 'temporal_unitmlp_bn')
+            bn_running_update=_k_bn_running_update, strided_frames=_k_strided_frames, dynadj_typed=_k_dynadj_typed,
+            gram=_k_gram, gate=_k_gate, temporal_mlp_bn=_k_temporal_mlp, temporal_unitmlp_bn=_k_temporal_unitmlp)
+# The public functions of dsgcn_amd.kernels that the census does not wrap, and why.  KEYS and this table partition the
+# module's public functions exactly (test_model_census_gpu.py::test_every_public_op_is_keyed_or_listed, no GPU needed):
+# a new op fails that test until it is keyed here or listed with a reason.
+UNWRAPPED = {
+    'ops': 'returns the dispatch namespace; launches nothing',
+    'use_ops': 'installs a dispatch namespace; launches nothing',
+    'tconv_gemm_ok': 'host predicate; its answer is part of the tconv_bn key',
+    'prestrided_fits': 'host predicate; its answer is part of the fuse_out key',
+    'data_bn_eligible': 'host predicate deciding whether data_bn runs; launches nothing',
+    'dropout_step_advance': 'host counter of the fused dropout streams; launches nothing',
+    'dropout_mask': 'materialises a fused dropout mask for tests; the models never call it',
+    'reset_leaf_uses': 'step bookkeeping (TrainEngine); launches nothing',
+    'end_step': 'step bookkeeping (TrainEngine); launches nothing',
+    'flush_param_sums': 'deferred column sums of TrainEngine; test_colsum / the bit-identical step tests check them',
+    'param_colsum': 'ordered column sum inside the keyed ops; test_colsum checks its reduction at the census heights',
+    'colsum': 'ordered column sum inside the keyed ops; test_colsum checks the one- and two-stage forms',
+    'colsum_pair': 'two column sums sharing launches; test_colsum_pair checks every fold combination',
+    'cat_rows': 'parameter concatenation, a view under FlatParams; its backward hands back row slices (no kernel)',
+    'bn_finalize': 'BatchNorm finalize inside the keyed convs; their checks compare the statistics and affine it makes',
+}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -196,8 +255,44 @@ def _model_cfg(model, keep_drop):
     return other_cfg(model, tcn_dropout=0.5) if keep_drop else other_cfg(model)
 
 
-def _record_step(mp, model, clips, T, V, classes, keep_drop):
-    """One eager train_step + backward of a BASELINE config (bench.py's model and inputs) -> {op: set of keys}."""
+def public_functions(module=K):
+    """The public functions defined in dsgcn_amd.kernels (no leading underscore)."""
+    return {name for name, fn in inspect.getmembers(module, inspect.isfunction)
+            if not name.startswith('_') and fn.__module__ == module.__name__}
+
+
+BN_PAIRS = '_bn_feed_multi'        # the log entry of BatchNorm coefficient launches that name one BNCtx twice
+
+
+def _watch_bn_feeds(mp, log):
+    """Log every launch of BatchNorm coefficient jobs in which two jobs write one BNCtx's coef buffer — the second one
+    accumulating into what the first one writes, in the same launch — as (the jobs' channel counts, jobs).  Covers the
+    launches of kernels._bn_feed_multi and of the waiting jobs, and the jobs _bn_feed_multi hands to the caller's next
+    (hosting) launch."""
+    def same_ctx(jobs):
+        coefs = [j.coef for j in jobs]
+        if len(set(coefs)) < len(coefs):
+            log.setdefault(BN_PAIRS, set()).add((tuple(int(j.C) for j in jobs), len(jobs)))
+
+    def launch_coef(fn):
+        def wrapped(jobs):
+            same_ctx(jobs)
+            return fn(jobs)
+        return wrapped
+
+    def feed_multi(fn):
+        def wrapped(feeds, launch=True):
+            out = fn(feeds, launch)
+            same_ctx(out)
+            return out
+        return wrapped
+    mp.setattr(K, '_launch_coef', launch_coef(K._launch_coef))
+    mp.setattr(K, '_bn_feed_multi', feed_multi(K._bn_feed_multi))
+
+
+def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
+    """One eager train_step + backward of a BASELINE config (bench.py's model and inputs; or of the model dict ``cfg``)
+    -> {op: set of keys}."""
     log = {}
     path = {}
 
@@ -227,14 +322,13 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop):
 
     for name, keyfn in KEYS.items():
         mp.setattr(K, name, recorder(name, getattr(K, name), keyfn))
-    for name in UNKEYED:
-        mp.setattr(K, name, recorder(name, getattr(K, name), lambda a: ('unkeyed',)))
     mp.setattr(K, '_fused_temporal', dispatcher('fused', K._fused_temporal))
     mp.setattr(K, '_split_temporal', dispatcher('split', K._split_temporal))
+    _watch_bn_feeds(mp, log)
 
     np.random.seed(0)
     torch.manual_seed(0)
-    m = dsgcn_amd.build_model(_model_cfg(model, keep_drop))
+    m = dsgcn_amd.build_model(copy.deepcopy(cfg) if cfg is not None else _model_cfg(model, keep_drop))
     gen = torch.Generator().manual_seed(1)
     with torch.no_grad():
         for k, p in m.named_parameters():
@@ -256,15 +350,16 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop):
     return log
 
 
-def census():
-    """{op: {key: [the runs that recorded it]}} over the BASELINE steps, default knobs."""
+def census(runs=BASELINE_RUNS, cfg_of=lambda model: None):
+    """{op: {key: [the runs that recorded it]}} over the BASELINE steps (or ``runs``), default knobs.  The entry BN_PAIRS
+    holds the coefficient launches that named one BatchNorm twice, if any."""
     import os
     knobs = sorted(k for k in os.environ if k.startswith('DSGCN_'))
     assert not knobs, f'the census runs the default dispatch: unset {knobs}'
     seen = {}
-    for name, model, clips, T, V, classes, keep_drop in BASELINE_RUNS:
+    for name, model, clips, T, V, classes, keep_drop in runs:
         with pytest.MonkeyPatch.context() as mp:
-            log = _record_step(mp, model, clips, T, V, classes, keep_drop)
+            log = _record_step(mp, model, clips, T, V, classes, keep_drop, cfg_of(model))
         for op, keys in log.items():
             for key in keys:
                 seen.setdefault(op, {}).setdefault(key, []).append(name)
@@ -312,7 +407,7 @@ FULL_SIZE_CASES = {
         (85,),   # ctrgcn
         (95,),   # ds, ds120, ds_k400
     ],
-    # (n, Ci, Co, V, subsets, R, subset_major, path)
+    # (n, Ci, Co, V, subsets, R, subset_major, path[, (alpha elements, beta, edge subsets, edge classes E)])
     'ctr_topology': [
         (128, 128, 128, 25, 3, 16, True, 'one_conv'),   # ctrgcn
         (128, 128, 256, 25, 3, 16, True, 'one_conv'),   # ctrgcn
@@ -327,7 +422,7 @@ FULL_SIZE_CASES = {
         (64, 2, 64, 25, 3, 'MVC', True),   # ctrgcn
         (64, 2, 64, 25, 3, 'VC', True),   # stgcn, stgcn_dropout, ds, ds120
     ],
-    # (n, Ci, mid, V, xbar row length, BatchNorm jobs hosted)
+    # (n, Ci, mid, V, xbar row length, BatchNorm jobs hosted[, False: single_use=False])
     'dynadj': [
         (128, 128, 16, 25, 32, True),   # ds, ds120
         (128, 128, 32, 25, 32, True),   # ds, ds120
@@ -548,7 +643,7 @@ def _listing(keys):
 
 def test_census_every_kernel_call_is_in_the_table(recorded):
     missing = {op: {k: runs for k, runs in keys.items() if k not in FULL_SIZE_CASES.get(op, ())}
-               for op, keys in recorded.items()}
+               for op, keys in recorded.items() if op != BN_PAIRS}
     missing = {op: keys for op, keys in missing.items() if keys}
     assert not missing, 'kernel calls of the BASELINE steps that FULL_SIZE_CASES lacks:\n' + _listing(missing)
 
@@ -558,6 +653,12 @@ def test_census_table_has_no_stale_entries(recorded):
     stale = {op: keys for op, keys in stale.items() if keys}
     assert not stale, f'FULL_SIZE_CASES entries no BASELINE step records: {stale!r}'
     assert all(len(set(keys)) == len(keys) for keys in FULL_SIZE_CASES.values())
+
+
+def test_census_no_bn_coef_launch_writes_one_batchnorm_twice(recorded):
+    """two jobs of one coefficient launch that name the same BNCtx race (the second accumulates into the coef
+    buffer the first one writes)."""
+    assert BN_PAIRS not in recorded, _listing({BN_PAIRS: recorded.get(BN_PAIRS, {})})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -580,10 +681,10 @@ def _existing(test):
     return [dict(kv for d in combo for kv in d.items()) for combo in itertools.product(*lists)]
 
 
-def _cases(op, to_args, test=None, keep=lambda key: True):
+def _cases(op, to_args, test=None, keep=lambda key: True, table=None):
     have = _existing(test) if test is not None else []
     out = []
-    for key in FULL_SIZE_CASES[op]:
+    for key in (FULL_SIZE_CASES if table is None else table)[op]:
         if not keep(key):
             continue
         args = to_args(key)
@@ -640,11 +741,18 @@ def test_aggregate_sum_subset_major_census(key, args):
 
 
 def _ctr_args(k):
-    n, Ci, Co, V, Kk, Rr, subset_major, path = k
+    n, Ci, Co, V, Kk, Rr, subset_major, path = k[:8]
+    n_alpha, beta, edge, E = k[8] if len(k) > 8 else (1, False, (), 0)
     # check_ctr_topology builds three subsets of R = 8 (Ci <= 16) / Ci // 8 channels, as unit_ctrgcn does; with
-    # subset_major it asserts the (K, n, Co, V, V) result of the one-conv form
-    assert Kk == 3 and Rr == (8 if Ci <= 16 else Ci // 8) and path == ('one_conv' if subset_major else 'per_subset'), k
-    return dict(n=n, Ci=Ci, Co=Co, V=V, subset_major=subset_major)
+    # subset_major it asserts the (K, n, Co, V, V) result of the one-conv form, which the library takes exactly for the
+    # classic unit (one alpha, no Gram term, no edge subsets)
+    classic = n_alpha == 1 and not beta and not edge
+    assert Kk == 3 and Rr == (8 if Ci <= 16 else Ci // 8) and n_alpha in (1, Kk), k
+    assert path == ('one_conv' if subset_major and classic else 'per_subset'), k
+    args = dict(n=n, Ci=Ci, Co=Co, V=V, subset_major=subset_major)
+    if not classic:
+        args.update(alpha_per_subset=n_alpha == Kk, beta=beta, edge=edge, E=E)
+    return args
 
 
 @pytest.mark.parametrize('key,args', _cases('ctr_topology', _ctr_args, KG.test_ctr_topology))
@@ -659,12 +767,17 @@ def test_data_bn_census(key, args):
 
 
 def _dyn_args(k):
-    n, Ci, mid, V, ld, hosted = k
+    n, Ci, mid, V, ld, hosted = k[:6]
+    single_use = len(k) == 6
     # ld = 32: the step hands xbar over zero-padded to 32 joints (fuse_out's time mean); dynadj pads an unpadded xbar to
-    # the same tensor before its first launch, so the helper's unpadded input runs the same launches.  hosted: BatchNorm
-    # finalize jobs ride in K-B's launches, bit-identical to the plain call (test_bn_jobs_batched_and_hosted_are_bit_identical)
-    assert ld == 32 and V < 32
-    return dict(n=n, Ci=Ci, mid=mid, V=V, layout={25: 'nturgb+d', 17: 'coco'}[V])
+    # the same tensor before its first launch, so the helper's unpadded input (ld = V) runs the same launches.  hosted:
+    # BatchNorm finalize jobs ride in K-B's launches, bit-identical to the plain call
+    # (test_bn_jobs_batched_and_hosted_are_bit_identical)
+    assert ld in (32, V) and V < 32
+    args = dict(n=n, Ci=Ci, mid=mid, V=V, layout={25: 'nturgb+d', 17: 'coco'}[V])
+    if not single_use:
+        args['single_use'] = False
+    return args
 
 
 @pytest.mark.parametrize('key,args', _cases('dynadj', _dyn_args, KG.test_dynadj))
@@ -771,9 +884,16 @@ def test_temporal_ms_census(key, args, monkeypatch):
 def _tb_args(k):
     n, C, T, V, stride, cfg, widths, n_act, want_bn, path = k
     ks = cfg[0][0]
+    args = dict(n=n, C=C, T=T, V=V, stride=stride, ks=ks, fused={'fused': 'auto', 'staged': '0'}[path])
+    assert want_bn, k
+    if cfg == DGMSTCN:
+        # ST-GCN++'s mstcn: dgmstcn's six branches, C // 6 channels each, the remainder on the first
+        mid = C // 6
+        assert widths == (C - 5 * mid,) + (mid,) * 5 and n_act == C - mid, k
+        return dict(args, cfg=cfg)
     bc = C // 4
-    assert cfg == ((ks, 1), (ks, 2), ('max', 3), '1x1') and widths == (bc, bc, bc, C - 3 * bc) and n_act == 3 * bc and want_bn
-    return dict(n=n, C=C, T=T, V=V, stride=stride, ks=ks, fused={'fused': 'auto', 'staged': '0'}[path])
+    assert cfg == ((ks, 1), (ks, 2), ('max', 3), '1x1') and widths == (bc, bc, bc, C - 3 * bc) and n_act == 3 * bc, k
+    return args
 
 
 @pytest.mark.parametrize('key,args', _cases('temporal_branches_bn', _tb_args))

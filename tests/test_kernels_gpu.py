@@ -117,7 +117,8 @@ def test_dynadj(n, Ci, mid, V, layout):
     check_dynadj(n, Ci, mid, V, layout)
 
 
-def check_dynadj(n, Ci, mid, V, layout):
+def check_dynadj(n, Ci, mid, V, layout, single_use=True):
+    """single_use=False: what dggcn passes (its A feeds two calls; the parameter sums are never deferred)."""
     t, nt, et = _dyn_inputs(n, Ci, mid, V, layout, seed=Ci + mid)
     g = torch.Generator().manual_seed(7)
     dah = torch.randn(n, 3 * mid, V, V, generator=g)
@@ -125,7 +126,7 @@ def check_dynadj(n, Ci, mid, V, layout):
 
     def run(mod, dt, dev):
         tt = {k: v.to(dev, dt).requires_grad_() for k, v in t.items()}
-        out = mod.dynadj(*[tt[k] for k in order], nt.to(dev), et.to(dev))
+        out = mod.dynadj(*[tt[k] for k in order], nt.to(dev), et.to(dev), single_use=single_use)
         out.backward(dah.to(dev, dt))
         return out, {k: v.grad for k, v in tt.items()}
 
@@ -624,9 +625,14 @@ def check_fuse_out(n, C, T, V, mode, tmean, flags, tee=False):
     tee: the output as three aliases (1), the third one the even frames as a tensor of their own (2)."""
     g = torch.Generator().manual_seed(C + T)
     x1 = _rand(g, n, C, T, V)
-    a1 = None if mode == 'plain' else (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3))
+    a1 = None if mode in ('plain', 'res_x1') else (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3))
     x2 = _rand(g, n, C, T, V) if mode.startswith('res') else None
     a2 = (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3)) if mode == 'res_affine' else None
+    # the ReLU's input off the knife edge (off_knife_edge): the inner one on the first term (flags bit 1), else the outer
+    if int(flags) & 2:
+        off_knife_edge(x1, a1, None, None, True)
+    elif int(flags) & 1:
+        off_knife_edge(x1, a1, x2, a2, True)
     go = _rand(g, n, C, T, V)
     gb = _rand(g, n, C, V if tmean is True or not tmean else int(tmean))
 
@@ -1011,9 +1017,12 @@ def test_ctr_topology(n, Ci, Co, V, subset_major):
     check_ctr_topology(n, Ci, Co, V, subset_major)
 
 
-def check_ctr_topology(n, Ci, Co, V, subset_major):
+def check_ctr_topology(n, Ci, Co, V, subset_major, alpha_per_subset=False, beta=False, edge=(), E=15):
     """subset_major: Ahat as (K, n, Co, V, V) through the one-conv form of the classic refinement (conv4 + alpha + A as one
-    1x1 conv over [d | A[k] | 1]); the plain call keeps the (n, K*Co, V, V) contract and the separate affine pass."""
+    1x1 conv over [d | A[k] | 1]); the plain call keeps the (n, K*Co, V, V) contract and the separate affine pass.
+    alpha_per_subset / beta / edge: unit_ctrhgcn's form on the per-subset path — one alpha per subset (_CtrAffine), the
+    Gram term beta_k x1_k^T x2_k (kernels.gram on one-frame planes), and on the subsets in ``edge`` the edge-typed attention
+    conv over E classes + select (_EdgeSelect) before conv4."""
     g = torch.Generator().manual_seed(Ci + Co)
     K = 3
     Rr = 8 if Ci <= 16 else Ci // 8
@@ -1023,23 +1032,38 @@ def check_ctr_topology(n, Ci, Co, V, subset_major):
     w4 = [_rand(g, Co, Rr, scale=Rr ** -0.5) for _ in range(K)]
     b4 = [_rand(g, Co, scale=0.1) for _ in range(K)]
     gah = _rand(g, n, K * Co, V, V)
+    classic = not (alpha_per_subset or beta or edge)
+    if alpha_per_subset:
+        t['alpha'] = _rand(g, K, scale=0.7)
+    if beta:
+        t['beta'] = _rand(g, K, scale=0.5)
+    et = torch.tensor(dsgcn_amd.Graph(layout={25: 'nturgb+d', 17: 'coco'}[V], mode='spatial').edge_type,
+                      dtype=torch.int32).reshape(-1) if edge else None
+    assert et is None or int(et.max()) < E
+    we = {k: _rand(g, E * Rr, Rr, scale=Rr ** -0.5) for k in edge}
+    be = {k: _rand(g, E * Rr, scale=0.1) for k in edge}
 
     def run(mod, dt, dev):
         tt = {k: v.to(dev, dt).requires_grad_() for k, v in t.items()}
         tw4 = [w.to(dev, dt).requires_grad_() for w in w4]
         tb4 = [b.to(dev, dt).requires_grad_() for b in b4]
+        twe = {k: w.to(dev, dt).requires_grad_() for k, w in we.items()}
+        tbe = {k: b.to(dev, dt).requires_grad_() for k, b in be.items()}
+        ted = {k: (twe[k], tbe[k], et.to(dev)) for k in edge}
         ah = mod.ctr_topology(tt['xbar'], tt['w1'], tt['b1'], tt['w2'], tt['b2'], tw4, tb4, tt['alpha'], tt['A'],
-                              subset_major=subset_major)
+                              tt.get('beta'), ted, subset_major=subset_major)
         if ah.dim() == 5:
             assert mod is K_ and ah.shape == (K, n, Co, V, V)
             ah = ah.permute(1, 0, 2, 3, 4).reshape(n, K * Co, V, V)
         else:
-            assert not (mod is K_ and subset_major)
+            assert not (mod is K_ and subset_major and classic)
         ah.backward(gah.to(dev, dt))
         res = {'ahat': ah}
         res.update({'d' + k: v.grad for k, v in tt.items()})
         for k in range(K):
             res[f'dw4_{k}'], res[f'db4_{k}'] = tw4[k].grad, tb4[k].grad
+        for k in edge:
+            res[f'dwe_{k}'], res[f'dbe_{k}'] = twe[k].grad, tbe[k].grad
         return res
 
     got = run(K_, torch.float32, DEV)
@@ -1196,19 +1220,31 @@ def test_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
     check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch)
 
 
-def check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
-    """MSTCN's stage: BN+ReLU, two dilated (k,1) convs, max-pool, strided copy, closing BatchNorm statistics."""
+def _ms_widths(C, cfg):
+    """dgmstcn / mstcn / msmlp's branch widths: C // branches each, the remainder on the first branch"""
+    mid = C // len(cfg)
+    return [C - mid * (len(cfg) - 1)] + [mid] * (len(cfg) - 1)
+
+
+def check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch, cfg=None):
+    """MSTCN's stage: BN+ReLU, two dilated (k,1) convs, max-pool, strided copy, closing BatchNorm statistics.
+    cfg: another branch table (mstcn's six branches, widths as the unit makes them) instead of MSTCN's four of kernel ks."""
     monkeypatch.setattr(K, 'FUSED_TEMPORAL', fused)
     g = torch.Generator().manual_seed(C + T + stride)
-    cfg = [(ks, 1), (ks, 2), ('max', 3), '1x1']
-    bc = C // 4
-    widths = [bc, bc, bc, C - 3 * bc]
-    n_act = 3 * bc
+    if cfg is None:
+        cfg = [(ks, 1), (ks, 2), ('max', 3), '1x1']
+        bc = C // 4
+        widths = [bc, bc, bc, C - 3 * bc]
+    else:
+        cfg = [tuple(c) if isinstance(c, (tuple, list)) else c for c in cfg]
+        widths = _ms_widths(C, cfg)
+    n_act = sum(w for w, c in zip(widths, cfg) if c != '1x1')
+    convs = [(w, c[0]) for w, c in zip(widths, cfg) if c != '1x1' and c[0] != 'max']
     z = _rand(g, n, C, T, V)
     scale = torch.cat([torch.rand(n_act, generator=g) + 0.5, torch.ones(C - n_act)])
     shift = torch.cat([_rand(g, n_act, scale=0.3), torch.zeros(C - n_act)])
-    cw = [_rand(g, bc, bc, ks, 1, scale=(ks * bc) ** -0.5) for _ in range(2)]
-    cb = [_rand(g, bc, scale=0.1) for _ in range(2)]
+    cw = [_rand(g, w, w, k, 1, scale=(k * w) ** -0.5) for w, k in convs]
+    cb = [_rand(g, w, scale=0.1) for w, _ in convs]
     gamma = torch.rand(C, generator=g) + 0.5
     beta = _rand(g, C, scale=0.2)
     Tout = (T + stride - 1) // stride
@@ -1224,7 +1260,7 @@ def check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
         ((o * go.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
         res = dict(o=o, sc=sc, sh=sh, mean=mean, var=var, dz=tz.grad, dscale=tsc.grad, dshift=tsh.grad,
                    dgamma=tga.grad, dbeta=tbe.grad)
-        for i in range(2):
+        for i in range(len(convs)):
             res[f'dw{i}'], res[f'db{i}'] = tw[i].grad, tb[i].grad
         return res
 
@@ -1233,6 +1269,160 @@ def check_temporal_branches_bn(n, C, T, V, stride, ks, fused, monkeypatch):
     for k, v in ref.items():
         # fp32 MFMA accumulation over <= 5*64 (fwd) / n*T*V (wgrad, statistics) terms: 2e-5 relative L2
         assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+
+
+CFG6 = ((3, 1), (3, 2), (3, 3), (3, 4), ('max', 3), '1x1')       # msmlp / mstcn / dgmstcn's default branches
+
+
+# the edges of k_dwcausal_*: T odd with stride 2, (KM-1)*dil >= T (every tap but the last reads the zero padding), channels
+# with dil = 0 (msmlp's max-pool / pass-through windows; set by zero_dil for unitmlp) next to active ones, V = 17 / 18, n = 1
+@pytest.mark.parametrize('n,C,T,V,stride,cfg,merge_after', [
+    (2, 24, 9, 25, 2, CFG6, True), (2, 24, 9, 25, 2, CFG6, False), (1, 12, 4, 17, 1, CFG6, True),
+    (2, 18, 7, 18, 2, CFG6, False), (2, 16, 12, 25, 1, ((5, 1), (5, 2), ('max', 3), '1x1'), True)])
+def test_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after):
+    check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after)
+
+
+def check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after):
+    """msmlp's stage (kernels.temporal_mlp_bn) as the unit builds its operands: BN+ReLU, the alpha-scaled dilated convs /
+    max-pool / strided copy, the depthwise causal taps (zero outside the mlp windows), the windows' 1x1 convs as one
+    block-diagonal mix (zero blocks for the other windows with merge_after, identity blocks without), the closing
+    BatchNorm statistics — outputs, statistics and every input / parameter gradient."""
+    cfg = [tuple(c) if isinstance(c, (tuple, list)) else c for c in cfg]
+    g = torch.Generator().manual_seed(C * 5 + T + stride)
+    widths = _ms_widths(C, cfg)
+    n_act = sum(w for w, c in zip(widths, cfg) if c != '1x1')
+    mlp = [(w, c) for w, c in zip(widths, cfg) if c != '1x1' and c[0] != 'max']
+    assert [c for _, c in mlp] == cfg[:len(mlp)]                  # the mlp windows come first (block-diagonal mix)
+    kms = {(c[0] + 1) // 2 for _, c in mlp}
+    assert len(kms) == 1
+    KM = kms.pop()
+    nm = sum(w for w, _ in mlp)
+    dil = torch.tensor(sum(([c[1]] * w for w, c in mlp), []) + [0] * (C - nm), dtype=torch.int32)
+    z = _rand(g, n, C, T, V)
+    scale = torch.cat([torch.rand(n_act, generator=g) + 0.5, torch.ones(C - n_act)])
+    shift = torch.cat([_rand(g, n_act, scale=0.3), torch.zeros(C - n_act)])
+    cw = [_rand(g, w, w, c[0], 1, scale=(c[0] * w) ** -0.5) for w, c in mlp]
+    cb = [_rand(g, w, scale=0.1) for w, _ in mlp]
+    dw_w = torch.cat([_rand(g, nm, KM, scale=0.5), torch.zeros(C - nm, KM)])
+    dw_b = torch.cat([_rand(g, nm, scale=0.1), torch.zeros(C - nm)])
+    rest = torch.zeros(C - nm, C - nm) if merge_after else torch.eye(C - nm)
+    pw_w = torch.block_diag(*[_rand(g, w, w, scale=w ** -0.5) for w, _ in mlp], rest)
+    pw_b = torch.cat([_rand(g, nm, scale=0.1), torch.zeros(C - nm)])
+    gamma = torch.rand(C, generator=g) + 0.5
+    beta = _rand(g, C, scale=0.2)
+    Tout = (T + stride - 1) // stride
+    go, gsc, gsh = _rand(g, n, C, Tout, V), _rand(g, C), _rand(g, C)
+
+    def run(mod, dt, dev):
+        def mk(t):
+            return t.to(dev, dt).requires_grad_()
+        tz, tsc, tsh, tga, tbe = mk(z), mk(scale), mk(shift), mk(gamma), mk(beta)
+        tw, tb = [mk(w) for w in cw], [mk(b) for b in cb]
+        tdw, tdb, tpw, tpb = mk(dw_w), mk(dw_b), mk(pw_w), mk(pw_b)
+        o, sc, sh, mean, var = mod.temporal_mlp_bn(tz, tsc, tsh, n_act, cfg, widths, tw, tb, tdw, tdb, dil.to(dev), tpw,
+                                                   tpb, merge_after, stride, tga, tbe, 1e-5, True)
+        ((o * go.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
+        res = dict(o=o, sc=sc, sh=sh, mean=mean, var=var, dz=tz.grad, dscale=tsc.grad, dshift=tsh.grad,
+                   ddw_w=tdw.grad, ddw_b=tdb.grad, dpw_w=tpw.grad, dpw_b=tpb.grad, dgamma=tga.grad, dbeta=tbe.grad)
+        for i in range(len(mlp)):
+            res[f'dw{i}'], res[f'db{i}'] = tw[i].grad, tb[i].grad
+        return res
+
+    got = run(K_, torch.float32, DEV)
+    ref = run(R, torch.float64, ref_dev(n))
+    for k, v in ref.items():
+        # fp32 accumulation over <= 3*C (fwd) / n*T*V (weight gradients, statistics) terms: 2e-5 relative L2
+        assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+
+
+@pytest.mark.parametrize('n,C,T,V,stride,ks,dil,add_tcn,merge_after,zero_dil', [
+    (2, 16, 9, 25, 2, 9, 1, True, True, False), (2, 16, 9, 25, 2, 9, 1, True, False, True),
+    (1, 8, 6, 17, 1, 9, 2, False, False, False), (2, 12, 7, 18, 2, 5, 4, False, True, True),
+    (1, 24, 13, 18, 1, 5, 2, True, True, True), (2, 20, 11, 17, 1, 3, 2, True, False, False)])
+def test_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil):
+    check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil)
+
+
+def check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil=False):
+    """unitmlp as a whole temporal unit (kernels.temporal_unitmlp_bn): the (ks+1)/2 depthwise causal taps at dilation dil,
+    the alpha-scaled dense (ks,1) conv (add_tcn), the 1x1 conv after (merge_after) or before the add, the BatchNorm
+    statistics.  zero_dil: every third channel gets dil = 0 (no taps: zero output, zero gradients)."""
+    g = torch.Generator().manual_seed(C * 3 + T + ks + stride)
+    KM = (ks + 1) // 2
+    h = _rand(g, n, C, T, V)
+    dw_w, dw_b = _rand(g, C, KM, scale=0.5), _rand(g, C, scale=0.1)
+    dils = torch.tensor([0 if zero_dil and c % 3 == 1 else dil for c in range(C)], dtype=torch.int32)
+    tw = _rand(g, C, C, ks, 1, scale=(ks * C) ** -0.5) if add_tcn else None
+    tb = _rand(g, C, scale=0.1) if add_tcn else None
+    pw_w, pw_b = _rand(g, C, C, scale=C ** -0.5), _rand(g, C, scale=0.1)
+    gamma = torch.rand(C, generator=g) + 0.5
+    beta = _rand(g, C, scale=0.2)
+    Tout = (T + stride - 1) // stride
+    go, gsc, gsh = _rand(g, n, C, Tout, V), _rand(g, C), _rand(g, C)
+
+    def run(mod, dt, dev):
+        def mk(t):
+            return None if t is None else t.to(dev, dt).requires_grad_()
+        th, tdw, tdb, ttw, ttb, tpw, tpb, tga, tbe = [mk(t) for t in (h, dw_w, dw_b, tw, tb, pw_w, pw_b, gamma, beta)]
+        o, sc, sh, mean, var = mod.temporal_unitmlp_bn(th, tdw, tdb, dils.to(dev), ttw, ttb, dil, tpw, tpb, merge_after,
+                                                       stride, tga, tbe, 1e-5, True)
+        ((o * go.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
+        res = dict(o=o, sc=sc, sh=sh, mean=mean, var=var, dh=th.grad, ddw_w=tdw.grad, ddw_b=tdb.grad, dpw_w=tpw.grad,
+                   dpw_b=tpb.grad, dgamma=tga.grad, dbeta=tbe.grad)
+        if add_tcn:
+            res.update(dtw=ttw.grad, dtb=ttb.grad)
+        return res
+
+    got = run(K_, torch.float32, DEV)
+    ref = run(R, torch.float64, ref_dev(n))
+    for k, v in ref.items():
+        # fp32 accumulation over <= ks*C (fwd) / n*T*V (weight gradients, statistics) terms: 2e-5 relative L2
+        assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+    if zero_dil:
+        off = (dils == 0).nonzero().view(-1)
+        assert not got['ddw_w'][off].any() and not got['ddw_b'][off].any()
+
+
+def check_typed_kb(case, flags):
+    """n = 128, V = 25: Ahat, the input gradient (of the time mean) and every parameter gradient of dghgcn's adjacency path
+    (K-C projections + typed select + K-C edge linear + typed K-B, kernels.dynadj_typed) against the fp64 restatement
+    (tests/dghgcn_fp64.py).  case = (Ci, Co, ratio): mid = ratio * Co channels per subset."""
+    import dghgcn_fp64 as F64
+    ci, co, ratio = case
+    na, ea, at = {'node_edge': (True, True, False), 'plain': (False, False, False), 'node': (True, False, False),
+                  'edge': (False, True, False), 'add_type': (True, True, True)}[flags]
+    g = dsgcn_amd.Graph(layout='nturgb+d', mode='spatial')
+    torch.manual_seed(7)
+    np.random.seed(7)
+    A = torch.tensor(np.asarray(dsgcn_amd.Graph(layout='nturgb+d', mode='random', num_filter=3, init_off=.04,
+                                                init_std=.02).A), dtype=torch.float32)
+    m = dsgcn_amd.dghgcn(ci, co, A, torch.tensor(g.edge_type), torch.tensor(g.node_type), ratio=ratio, node_attention=na,
+                         edge_attention=ea, add_type=at, subset_wise=True)
+    with torch.no_grad():
+        m.alpha.normal_(0, 0.5)
+        m.beta.normal_(0, 0.5)
+    m = m.cuda()
+    n, V = 128, 25
+    gen = torch.Generator().manual_seed(11)
+    xbar = torch.randn(n, ci, V, generator=gen).cuda().requires_grad_()
+    dah = torch.randn(n, 3 * m.mid_channels, V, V, generator=gen).cuda()
+    ahat = m.adjacency(xbar)
+    (ahat * dah).sum().backward()
+    names = ['A', 'alpha', 'beta', 'conv1.weight', 'conv1.bias', 'conv2.weight', 'conv2.bias'] + (
+        ['edge_linears.weight', 'edge_linears.bias'] if ea else [])
+    params = dict(m.named_parameters())
+    p64 = {k: params[k].detach().double().requires_grad_() for k in names}
+    x64 = xbar.detach().double().requires_grad_()
+    want = F64.adjacency(x64, p64['A'], p64['alpha'], p64['beta'], p64['conv1.weight'], p64['conv1.bias'],
+                         p64['conv2.weight'], p64['conv2.bias'], p64.get('edge_linears.weight'),
+                         p64.get('edge_linears.bias'), m.node_type_idx, m.edge_type_idx, m.num_types if na else 1, at, True)
+    (want * dah.double()).sum().backward()
+    assert rel(ahat.detach().cpu(), want.detach().cpu()) < 1e-5, rel(ahat.detach().cpu(), want.detach().cpu())
+    assert rel(xbar.grad.cpu(), x64.grad.cpu()) < 1e-4, rel(xbar.grad.cpu(), x64.grad.cpu())
+    for k in names:
+        e = rel(params[k].grad.cpu(), p64[k].grad.cpu())
+        assert e < 1e-4, (k, e)
 
 
 @pytest.mark.parametrize('n,Ci,Co,T,V,stride,ks,dil,bn', [
@@ -1560,47 +1750,82 @@ def test_aagcn_gram_gates_and_per_sample_aggregate(n, C, T, V):
     """The AAGCN pieces on the HIP path (gcn.py:431-437, 447-459): the embedding Gram (K-A''s backward product + ordered
     channel sum), K-A' with one topology per sample shared by the channels, and the three gate passes with the next gate's
     mean in the same launch — values and gradients against the fp64 statement of each op."""
+    check_gram(n, C, T, V)
+    check_aggregate_sum_per_sample(n, 3, max(C // 2, 1), T, V)
+    for mode in range(3):
+        for rmode in ((1, 2, 0)[mode], 0):
+            check_gate(n, C, T, V, mode, rmode)
+
+
+def check_gram(n, C, T, V):
+    """G = sum_{c,t} a[., c, t, u] b[., c, t, w] and its two gradients (AAGCN's embeddings; CTRHGC's one-frame planes)."""
     g = torch.Generator().manual_seed(n + C + T)
     a, b = _rand(g, n, C, T, V), _rand(g, n, C, T, V)
     dG = _rand(g, n, V, V)
-    S, Co = 3, max(C // 2, 1)
+
+    def run(mod, dt, dev):
+        ta, tb = a.to(dev, dt).requires_grad_(), b.to(dev, dt).requires_grad_()
+        G = mod.gram(ta, tb)
+        (G * dG.to(dev, dt)).sum().backward()
+        return dict(G=G, da=ta.grad, db=tb.grad)
+
+    got = run(K, torch.float32, DEV)
+    ref = run(R, torch.float64, ref_dev(n))
+    for k, v in ref.items():
+        # fp32 sums over <= C*T (Gram) / V (its gradients) terms: 2e-5 relative L2
+        assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+
+
+def check_aggregate_sum_per_sample(n, S, Co, T, V):
+    """K-A' with one (S, V, V) topology per sample shared by the channels (AAGCN), with the BatchNorm statistics."""
+    g = torch.Generator().manual_seed(n + S * Co + T)
     p = _rand(g, n, S * Co, T, V)
     adj = _rand(g, n, S, V, V, scale=0.3)
     gam, bet = torch.rand(Co, generator=g) + 0.5, _rand(g, Co, scale=0.2)
     gy, gsc, gsh = _rand(g, n, Co, T, V), _rand(g, Co), _rand(g, Co)
-    y = _rand(g, n, C, T, V)
-    gates = [torch.rand(n, V, generator=g), torch.rand(n, T, generator=g), torch.rand(n, C, generator=g)]
-    gout = _rand(g, n, C, T, V)
-    dr = [None, _rand(g, n, C, T), _rand(g, n, C)]
 
     def run(mod, dt, dev):
         mk = lambda t: t.to(dev, dt).requires_grad_()            # noqa: E731
-        res = {}
-        ta, tb = mk(a), mk(b)
-        G = mod.gram(ta, tb)
-        (G * dG.to(dev, dt)).sum().backward()
-        res.update(G=G, da=ta.grad, db=tb.grad)
         tp, tadj, tg, tbt = mk(p), mk(adj), mk(gam), mk(bet)
         yy, sc, sh, mean, var = mod.aggregate_sum(tp, tadj, S, tg, tbt, 1e-5, True, per_sample=True)
         ((yy * gy.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
-        res.update(y=yy, sc=sc, sh=sh, dp=tp.grad, dadj=tadj.grad, dgamma=tg.grad)
-        for mode in range(3):
-            for rmode in ((1, 2, 0)[mode], 0):
-                ty, tgt = mk(y), mk(gates[mode])
-                out, r = mod.gate(ty, tgt, mode, rmode)
-                loss = (out * gout.to(dev, dt)).sum()
-                if rmode:
-                    loss = loss + (r * dr[rmode].to(dev, dt)).sum()
-                    res[f'r{mode}{rmode}'] = r
-                loss.backward()
-                res.update({f'out{mode}{rmode}': out, f'dy{mode}{rmode}': ty.grad, f'dg{mode}{rmode}': tgt.grad})
+        return dict(y=yy, sc=sc, sh=sh, mean=mean, var=var, dp=tp.grad, dadj=tadj.grad, dgamma=tg.grad, dbeta=tbt.grad)
+
+    got = run(K, torch.float32, DEV)
+    ref = run(R, torch.float64, ref_dev(n))
+    for k, v in ref.items():
+        # fp32 sums over S*V (fwd) / Co*T (dadj) / n*T*V (statistics) terms: 2e-5 relative L2
+        assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+
+
+def check_gate(n, C, T, V, mode, rmode):
+    """out = y * (1 + g) with g per joint / frame / channel (mode 0 / 1 / 2) and the next gate's mean (rmode 1: over
+    joints, 2: over the plane) from the same pass, with both gradients."""
+    g = torch.Generator().manual_seed(n + C + T + 10 * mode + rmode)
+    y = _rand(g, n, C, T, V)
+    gt = torch.rand(n, (V, T, C)[mode], generator=g)
+    gout = _rand(g, n, C, T, V)
+    dr = _rand(g, *((n, C, T) if rmode == 1 else (n, C))) if rmode else None
+
+    def run(mod, dt, dev):
+        ty, tg = y.to(dev, dt).requires_grad_(), gt.to(dev, dt).requires_grad_()
+        out, r = mod.gate(ty, tg, mode, rmode)
+        loss = (out * gout.to(dev, dt)).sum()
+        if rmode:
+            loss = loss + (r * dr.to(dev, dt)).sum()
+        loss.backward()
+        res = dict(out=out, dy=ty.grad, dg=tg.grad)
+        if rmode:
+            res['r'] = r
         return res
 
     got = run(K, torch.float32, DEV)
-    ref = run(R, torch.float64, 'cpu')
+    ref = run(R, torch.float64, ref_dev(n))
     for k, v in ref.items():
-        # fp32 sums over <= C*T (Gram) / n*T*V (statistics) terms: 2e-5 relative L2
-        assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
+        e = rel(got[k].detach().cpu(), v.detach())
+        # out, dy: a product per element (plus, for dy, the mean's gradient spread over its terms): a few fp32 roundings.
+        # r, dg: fp32 sums over <= T*V / C*T*V terms: 2e-5 relative L2
+        assert e < (1e-6 if k in ('out', 'dy') else 2e-5), (k, e)
 
 
 def test_wsplit_images_batched_per_step_and_never_stale():
@@ -1743,7 +1968,7 @@ def check_fuse_out_pool(n, C, T, V, mode, flags):
     is NOT claimed: torch's mean runs in another order, so 2e-6 of the norm."""
     g = torch.Generator().manual_seed(C + T + flags)
     x1 = _rand(g, n, C, T, V)
-    a1 = None if mode == 'plain' else (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3))
+    a1 = None if mode in ('plain', 'res_x1') else (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3))
     x2 = _rand(g, n, C, T, V) if mode.startswith('res') else None
     a2 = (torch.rand(C, generator=g) + 0.5, _rand(g, C, scale=0.3)) if mode == 'res_affine' else None
     gp = _rand(g, n, C)
