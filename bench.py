@@ -7,7 +7,12 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 it
 
 A "step" = one pass of the hot path over one batch of synthetic clips resident in HBM: forward (train-mode
 BatchNorm, CE loss) + backward + gradient all-reduce (N>1) + the SGD-nesterov update.  Weak scaling: 64
-clips per GPU.  The line also carries
+clips per GPU.
+
+A plain run does only what the headline figure needs: set-up, the warm-up, the timed steps, ``--dump-outputs`` and
+the line (value, ms_per_step, final_loss, hip_graph; per-rank step times at N>1).  ``--full`` runs everything else
+after the timed steps: host_enqueue_ms, optimizer_ms / fwd_bwd_ms, dist.allreduce_ms and param_sha256 (each after
+steps or replays of its own), and the figures below; the --no-* switches leave single parts of it out.
   roofline     — the gather-aggregate kernel (K-A) timed live with HIP events on the launch stream over the
                  model's own 10-layer shape mix, against the 8 TB/s HBM peak (algorithmic bytes only);
   cpu_baseline — the CPU oracle (op-for-op PyTorch restatement of the reference path) timed on this box's
@@ -684,6 +689,8 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--clips-per-gpu', type=int, default=CLIPS_PER_GPU)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline figure does not need (see the docstring)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the BASELINE configs 1 / 3 / 4 / 5 step times')
@@ -813,6 +820,17 @@ def main(argv=None):
                               'rccl_version': '.'.join(str(v) for v in torch.cuda.nccl.version()),
                               'rank_ms_per_step': per, 'rank_ms_min': min(per), 'rank_ms_max': max(per),
                               'grad_bytes': int(flat.flat_g.numel() * flat.flat_g.element_size())}
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1 or force_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+    if not args.full:
+        finish()
+        return
+    # --full from here on: nothing below feeds the headline figure
     # host time per step: how long the Python thread takes to ENQUEUE a step (batch copies, two graph
     # replays, the collective) against the GPU time of the step — the margin the host has before jitter reaches the GPU;
     # at N > 1 this is what decides weak-scaling efficiency, and it is measurable at N = 1
@@ -879,11 +897,7 @@ def main(argv=None):
         cb = cpu_baseline(args.cpu_budget)
         result['cpu_baseline'] = cb
         result['gpu_over_cpu'] = round(result['value'] / cb['value'], 1)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1 or force_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == '__main__':

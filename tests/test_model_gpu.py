@@ -425,7 +425,7 @@ def _run_bench_child(extra_env, *args):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **extra_env)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--no-cpu-baseline', '--no-roofline',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--no-cpu-baseline', '--no-roofline',
                           '--no-other-configs', *args],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -466,7 +466,7 @@ def test_bench_through_torch_distributed_run():
         env.pop(k, None)
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
                           '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(root, 'bench.py'),
-                          '--gpus', '1', '--steps', '2', '--warmup', '4', '--clips-per-gpu', '8', '--no-cpu-baseline',
+                          '--gpus', '1', '--steps', '2', '--warmup', '4', '--clips-per-gpu', '8', '--full', '--no-cpu-baseline',
                           '--no-roofline', '--no-other-configs'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     b = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
@@ -570,7 +570,7 @@ def test_bench_self_launch_path():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'DSGCN_BENCH_FORCE_DIST'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '4',
-                          '--clips-per-gpu', '8', '--no-cpu-baseline', '--no-roofline', '--no-other-configs'],
+                          '--clips-per-gpu', '8', '--full', '--no-cpu-baseline', '--no-roofline', '--no-other-configs'],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert 'self-launch' in out.stderr
@@ -580,6 +580,32 @@ def test_bench_self_launch_path():
     assert b['hip_graph'] and b['n_gpus'] == 1
     assert b['dist']['world_size'] == 1 and b['dist']['self_launched'] and b['dist']['backend'] == 'nccl'
     assert a['param_sha256'] == b['param_sha256'] and a['final_loss'] == b['final_loss']
+
+
+def test_plain_bench_is_the_headline_alone():
+    """``python bench.py`` without ``--full``: the same timed steps as the ``--full`` run (same final loss), and a line that
+    carries the headline figure and nothing measured after the timed region."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'DSGCN_BENCH_FORCE_DIST',
+              'DSGCN_BENCH_SELF_LAUNCH'):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '4',
+                          '--clips-per-gpu', '8'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    a = json.loads(lines[0])
+    assert a['hip_graph'] and a['n_gpus'] == 1 and a['steps'] == 2 and a['warmup'] == 4
+    assert a['unit'] == 'clips/s' and a['higher_is_better'] is True and a['dtype'] == 'f32'
+    assert a['value'] > 0 and a['ms_per_step'] > 0
+    extras = ('host_enqueue_ms', 'optimizer_ms', 'fwd_bwd_ms', 'param_sha256', 'roofline', 'roofline_other',
+              'roofline_step', 'other_configs', 'cpu_baseline', 'gpu_over_cpu', 'dist')
+    assert not [k for k in extras if k in a]
+    b = _run_bench_child({}, '--steps', '2', '--warmup', '4', '--clips-per-gpu', '8')
+    assert a['final_loss'] == b['final_loss'] and 'param_sha256' in b and 'host_enqueue_ms' in b
 
 
 @pytest.mark.parametrize('graph', [False, True])
