@@ -290,10 +290,16 @@ def _watch_bn_feeds(mp, log):
     mp.setattr(K, '_bn_feed_multi', feed_multi(K._bn_feed_multi))
 
 
-def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
-    """One eager train_step + backward of a BASELINE config (bench.py's model and inputs; or of the model dict ``cfg``)
-    -> {op: set of keys}."""
-    log = {}
+# The ops whose dispatch reads grad mode or requires_grad: an eval record (_record_eval) extends their keys with EVAL, so
+# a no-grad launch is never mistaken for the training launch of the same shape.  tee3 launches nothing for an input
+# without history; data_bn normalises with the running statistics of an eval-mode BatchNorm (data_bn_eligible also
+# reads requires_grad).
+EVAL = 'eval'
+GRAD_READING = ('tee3', 'data_bn')
+
+
+def _install_recorders(mp, log, eval_keys=False):
+    """Wrap every op of KEYS, the temporal dispatchers and the BatchNorm feeds: each call adds its key to ``log``."""
     path = {}
 
     def dispatcher(name, fn):
@@ -306,6 +312,7 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
 
     def recorder(name, fn, keyfn):
         sig = inspect.signature(fn)
+        extend = (EVAL,) if eval_keys and name in GRAD_READING else ()
 
         def wrapped(*args, **kw):
             b = sig.bind(*args, **kw)
@@ -314,9 +321,9 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
                 path.clear()
                 out = fn(*args, **kw)
                 taken = {'fused': 'fused', 'split': 'split'}.get(path.get('taken'), 'staged')
-                log.setdefault(name, set()).add(_k_temporal(b.arguments, taken))
+                log.setdefault(name, set()).add(_k_temporal(b.arguments, taken) + extend)
                 return out
-            log.setdefault(name, set()).add(keyfn(b.arguments))
+            log.setdefault(name, set()).add(keyfn(b.arguments) + extend)
             return fn(*args, **kw)
         return wrapped
 
@@ -326,10 +333,11 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
     mp.setattr(K, '_split_temporal', dispatcher('split', K._split_temporal))
     _watch_bn_feeds(mp, log)
 
+
+def _build(model, keep_drop, cfg, gen):
     np.random.seed(0)
     torch.manual_seed(0)
     m = dsgcn_amd.build_model(copy.deepcopy(cfg) if cfg is not None else _model_cfg(model, keep_drop))
-    gen = torch.Generator().manual_seed(1)
     with torch.no_grad():
         for k, p in m.named_parameters():
             if k.endswith(('alpha', 'beta', 'add_coeff')):
@@ -337,6 +345,25 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
     for mod in m.modules():
         if isinstance(mod, torch.nn.Dropout) and not keep_drop:
             mod.p = 0.0
+    return m
+
+
+def fill_running_stats(m, gen):
+    """Running statistics of every BatchNorm drawn from ``gen``, so that eval-mode affines are not the identity."""
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm) and mod.running_mean is not None:
+                mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=gen) * 0.3)
+                mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=gen) + 0.5)
+
+
+def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
+    """One eager train_step + backward of a BASELINE config (bench.py's model and inputs; or of the model dict ``cfg``)
+    -> {op: set of keys}."""
+    log = {}
+    _install_recorders(mp, log)
+    gen = torch.Generator().manual_seed(1)
+    m = _build(model, keep_drop, cfg, gen)
     m = m.to(DEV).train()
     x = torch.randn(clips, 1, 2, T, V, 3, generator=gen).to(DEV)
     y = torch.randint(0, classes, (clips, 1), generator=gen).to(DEV)
@@ -350,20 +377,48 @@ def _record_step(mp, model, clips, T, V, classes, keep_drop, cfg=None):
     return log
 
 
-def census(runs=BASELINE_RUNS, cfg_of=lambda model: None):
-    """{op: {key: [the runs that recorded it]}} over the BASELINE steps (or ``runs``), default knobs.  The entry BN_PAIRS
-    holds the coefficient launches that named one BatchNorm twice, if any."""
+def _record_eval(mp, model, videos, clips, T, V, cfg=None):
+    """One eval-mode forward_test (``model(keypoint=x, return_loss=False)``) of ``videos`` x ``clips`` clips of 2 persons,
+    running statistics drawn from a seeded generator -> {op: set of keys}; the ops of GRAD_READING record EVAL keys."""
+    log = {}
+    _install_recorders(mp, log, eval_keys=True)
+    gen = torch.Generator().manual_seed(1)
+    m = _build(model, False, cfg, gen)
+    fill_running_stats(m, gen)
+    m = m.to(DEV).eval()
+    x = torch.randn(videos, clips, 2, T, V, 3, generator=gen).to(DEV)
+    probs = m(keypoint=x, return_loss=False)
+    torch.cuda.synchronize()
+    assert probs.shape[0] == videos and np.isfinite(probs).all()
+    del m, x
+    gc.collect()
+    torch.cuda.empty_cache()
+    return log
+
+
+def _collect(runs, record):
     import os
     knobs = sorted(k for k in os.environ if k.startswith('DSGCN_'))
     assert not knobs, f'the census runs the default dispatch: unset {knobs}'
     seen = {}
-    for name, model, clips, T, V, classes, keep_drop in runs:
+    for run in runs:
         with pytest.MonkeyPatch.context() as mp:
-            log = _record_step(mp, model, clips, T, V, classes, keep_drop, cfg_of(model))
+            log = record(mp, *run[1:])
         for op, keys in log.items():
             for key in keys:
-                seen.setdefault(op, {}).setdefault(key, []).append(name)
+                seen.setdefault(op, {}).setdefault(key, []).append(run[0])
     return seen
+
+
+def census(runs=BASELINE_RUNS, cfg_of=lambda model: None):
+    """{op: {key: [the runs that recorded it]}} over the BASELINE steps (or ``runs``), default knobs.  The entry BN_PAIRS
+    holds the coefficient launches that named one BatchNorm twice, if any."""
+    return _collect(runs, lambda mp, model, *rest: _record_step(mp, model, *rest, cfg=cfg_of(model)))
+
+
+def census_eval(runs, cfg_of=lambda model: None):
+    """census() of eval-mode forward_test runs: ``runs`` holds (name, model, videos, clips per video, T, V)."""
+    return _collect(runs, lambda mp, model, *rest: _record_eval(mp, model, *rest, cfg=cfg_of(model)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

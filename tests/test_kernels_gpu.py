@@ -337,8 +337,10 @@ def test_pwconv(n, Ci, Co, T, V, stride, aug, mode):
     check_pwconv(n, Ci, Co, T, V, stride, aug, mode)
 
 
-def check_pwconv(n, Ci, Co, T, V, stride, aug, mode, want_bn=True, bias=True):
-    """want_bn / bias False: the convs without a BatchNorm behind them (K-B's and the CTR-GCN refinement's projections)."""
+def check_pwconv(n, Ci, Co, T, V, stride, aug, mode, want_bn=True, bias=True, grad=True):
+    """want_bn / bias False: the convs without a BatchNorm behind them (K-B's and the CTR-GCN refinement's projections).
+    grad False: the eval-mode call (torch.no_grad(), inputs without history, want_bn False) and its outputs alone."""
+    assert grad or not want_bn
     g = torch.Generator().manual_seed(Ci * 7 + Co + T)
     x1 = _rand(g, n, Ci, T, V)
     a1 = a2 = x2 = None
@@ -364,10 +366,14 @@ def check_pwconv(n, Ci, Co, T, V, stride, aug, mode, want_bn=True, bias=True):
 
     def run(mod, dt, dev):
         def mk(t):
-            return None if t is None else t.to(dev, dt).requires_grad_()
+            return None if t is None else t.to(dev, dt).requires_grad_(grad)
         tx1, tx2, tw, tb, tg, tbeta = mk(x1), mk(x2), mk(w), mk(b if bias else None), mk(gamma), mk(beta)
         ta1 = None if a1 is None else (mk(a1[0]), mk(a1[1]))
         ta2 = None if a2 is None else (mk(a2[0]), mk(a2[1]))
+        if not grad:
+            with torch.no_grad():
+                z, zaug = mod.pwconv(tx1, ta1, tx2, ta2, relu, tw, tb, stride, aug)[:2]
+            return dict(z=z, zaug=zaug) if aug else dict(z=z)
         if want_bn:
             z, zaug, sc, sh, mean, var = mod.pwconv(tx1, ta1, tx2, ta2, relu, tw, tb, stride, aug, tg, tbeta, 1e-5, n_aff,
                                                     True)
@@ -846,11 +852,12 @@ def test_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
     check_temporal_ms(n, C, T, V, stride, fused, monkeypatch)
 
 
-def check_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
+def check_temporal_ms(n, C, T, V, stride, fused, monkeypatch, want_bn=True):
     """fused '1': the one-launch-per-direction stage (csrc/tms.hip) wherever the shape is eligible; '0': the staged chain
     (branch_act -> tapconv -> combine); 'split': the split layout (csrc/tmsplit.hip: no (V+1)-column tensors) wherever
     the shape is eligible (V odd, T % 4 == 0; stride 2: T % 8 == 0) — ineligible shapes are skipped, not silently run on
-    the staged chain.  All against the fp64 statement of the op."""
+    the staged chain.  All against the fp64 statement of the op.  want_bn False: the eval-mode call — no statistics,
+    under torch.no_grad() on inputs without history — and its output alone."""
     monkeypatch.setattr(K, 'FUSED_TEMPORAL', '0' if fused == 'split' else fused)
     monkeypatch.setattr(K, 'SPLIT_TEMPORAL', '2' if fused == 'split' else '0')
     g = torch.Generator().manual_seed(C + T + stride)
@@ -884,9 +891,12 @@ def check_temporal_ms(n, C, T, V, stride, fused, monkeypatch):
 
     def run(mod, dt, dev):
         def mk(t):
-            return t.to(dev, dt).requires_grad_()
+            return t.to(dev, dt).requires_grad_(want_bn)
         tz, tza, tsc, tsh, tco, tga, tbe = mk(z), mk(zaug), mk(scale), mk(shift), mk(coeff), mk(gamma), mk(beta)
         tw, tb = [mk(w) for w in cw], [mk(b) for b in cb]
+        if not want_bn:
+            with torch.no_grad():
+                return dict(f=mod.temporal_ms(tz, tza, tsc, tsh, n_act, cfg, widths, tw, tb, tco, stride)[0])
         f, sc, sh, mean, var = mod.temporal_ms(tz, tza, tsc, tsh, n_act, cfg, widths, tw, tb, tco, stride, tga, tbe,
                                                1e-5, True)
         ((f * gf.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
@@ -952,7 +962,9 @@ def test_aggregate_sum(n, K, Co, T, V, shared, bn):
     check_aggregate_sum(n, K, Co, T, V, shared, bn)
 
 
-def check_aggregate_sum(n, K, Co, T, V, shared, bn):
+def check_aggregate_sum(n, K, Co, T, V, shared, bn, grad=True):
+    """grad False: the eval-mode call (torch.no_grad(), inputs without history, bn False) and its output alone."""
+    assert grad or not bn
     g = torch.Generator().manual_seed(Co + T + V)
     p = _rand(g, n, K * Co, T, V)
     adj = _rand(g, K, V, V, scale=0.3) if shared else _rand(g, n, K * Co, V, V, scale=0.3)
@@ -962,8 +974,11 @@ def check_aggregate_sum(n, K, Co, T, V, shared, bn):
 
     def run(mod, dt, dev):
         def mk(t):
-            return t.to(dev, dt).requires_grad_()
+            return t.to(dev, dt).requires_grad_(grad)
         tp, ta, tg, tb = mk(p), mk(adj), mk(gamma), mk(beta)
+        if not grad:
+            with torch.no_grad():
+                return dict(y=mod.aggregate_sum(tp, ta, K)[0])
         y, sc, sh, mean, var = mod.aggregate_sum(tp, ta, K, tg if bn else None, tb if bn else None, 1e-5, bn)
         loss = (y * gy.to(dev, dt)).sum()
         if bn:
@@ -1283,11 +1298,12 @@ def test_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after):
     check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after)
 
 
-def check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after):
+def check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after, want_bn=True):
     """msmlp's stage (kernels.temporal_mlp_bn) as the unit builds its operands: BN+ReLU, the alpha-scaled dilated convs /
     max-pool / strided copy, the depthwise causal taps (zero outside the mlp windows), the windows' 1x1 convs as one
     block-diagonal mix (zero blocks for the other windows with merge_after, identity blocks without), the closing
-    BatchNorm statistics — outputs, statistics and every input / parameter gradient."""
+    BatchNorm statistics — outputs, statistics and every input / parameter gradient.  want_bn False: the eval-mode call
+    (no statistics, torch.no_grad(), inputs without history) and its output alone."""
     cfg = [tuple(c) if isinstance(c, (tuple, list)) else c for c in cfg]
     g = torch.Generator().manual_seed(C * 5 + T + stride)
     widths = _ms_widths(C, cfg)
@@ -1316,10 +1332,14 @@ def check_temporal_mlp_bn(n, C, T, V, stride, cfg, merge_after):
 
     def run(mod, dt, dev):
         def mk(t):
-            return t.to(dev, dt).requires_grad_()
+            return t.to(dev, dt).requires_grad_(want_bn)
         tz, tsc, tsh, tga, tbe = mk(z), mk(scale), mk(shift), mk(gamma), mk(beta)
         tw, tb = [mk(w) for w in cw], [mk(b) for b in cb]
         tdw, tdb, tpw, tpb = mk(dw_w), mk(dw_b), mk(pw_w), mk(pw_b)
+        if not want_bn:
+            with torch.no_grad():
+                return dict(o=mod.temporal_mlp_bn(tz, tsc, tsh, n_act, cfg, widths, tw, tb, tdw, tdb, dil.to(dev), tpw,
+                                                  tpb, merge_after, stride)[0])
         o, sc, sh, mean, var = mod.temporal_mlp_bn(tz, tsc, tsh, n_act, cfg, widths, tw, tb, tdw, tdb, dil.to(dev), tpw,
                                                    tpb, merge_after, stride, tga, tbe, 1e-5, True)
         ((o * go.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
@@ -1344,10 +1364,11 @@ def test_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, 
     check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil)
 
 
-def check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil=False):
+def check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after, zero_dil=False, want_bn=True):
     """unitmlp as a whole temporal unit (kernels.temporal_unitmlp_bn): the (ks+1)/2 depthwise causal taps at dilation dil,
     the alpha-scaled dense (ks,1) conv (add_tcn), the 1x1 conv after (merge_after) or before the add, the BatchNorm
-    statistics.  zero_dil: every third channel gets dil = 0 (no taps: zero output, zero gradients)."""
+    statistics.  zero_dil: every third channel gets dil = 0 (no taps: zero output, zero gradients).  want_bn False: the
+    eval-mode call (no statistics, torch.no_grad(), inputs without history) and its output alone."""
     g = torch.Generator().manual_seed(C * 3 + T + ks + stride)
     KM = (ks + 1) // 2
     h = _rand(g, n, C, T, V)
@@ -1363,8 +1384,12 @@ def check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after,
 
     def run(mod, dt, dev):
         def mk(t):
-            return None if t is None else t.to(dev, dt).requires_grad_()
+            return None if t is None else t.to(dev, dt).requires_grad_(want_bn)
         th, tdw, tdb, ttw, ttb, tpw, tpb, tga, tbe = [mk(t) for t in (h, dw_w, dw_b, tw, tb, pw_w, pw_b, gamma, beta)]
+        if not want_bn:
+            with torch.no_grad():
+                return dict(o=mod.temporal_unitmlp_bn(th, tdw, tdb, dils.to(dev), ttw, ttb, dil, tpw, tpb, merge_after,
+                                                      stride)[0])
         o, sc, sh, mean, var = mod.temporal_unitmlp_bn(th, tdw, tdb, dils.to(dev), ttw, ttb, dil, tpw, tpb, merge_after,
                                                        stride, tga, tbe, 1e-5, True)
         ((o * go.to(dev, dt)).sum() + (sc * gsc.to(dev, dt)).sum() + (sh * gsh.to(dev, dt)).sum()).backward()
@@ -1379,7 +1404,7 @@ def check_temporal_unitmlp_bn(n, C, T, V, stride, ks, dil, add_tcn, merge_after,
     for k, v in ref.items():
         # fp32 accumulation over <= ks*C (fwd) / n*T*V (weight gradients, statistics) terms: 2e-5 relative L2
         assert rel(got[k].detach().cpu(), v.detach()) < 2e-5, (k, rel(got[k].detach().cpu(), v.detach()))
-    if zero_dil:
+    if zero_dil and want_bn:
         off = (dils == 0).nonzero().view(-1)
         assert not got['ddw_w'][off].any() and not got['ddw_b'][off].any()
 
@@ -1433,8 +1458,10 @@ def test_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
     check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn)
 
 
-def check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
-    """unit_tcn's dense (k,1) temporal conv (ST-GCN: k=9) + the statistics of the BatchNorm that follows."""
+def check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn, grad=True):
+    """unit_tcn's dense (k,1) temporal conv (ST-GCN: k=9) + the statistics of the BatchNorm that follows.  grad False:
+    the eval-mode call (torch.no_grad(), inputs without history, bn False) and its output alone."""
+    assert grad or not bn
     g = torch.Generator().manual_seed(Ci + Co + T)
     h = _rand(g, n, Ci, T, V)
     w = _rand(g, Co, Ci, ks, 1, scale=(ks * Ci) ** -0.5)
@@ -1446,8 +1473,11 @@ def check_tconv_dense(n, Ci, Co, T, V, stride, ks, dil, bn):
 
     def run(mod, dt, dev):
         def mk(t):
-            return t.to(dev, dt).requires_grad_()
+            return t.to(dev, dt).requires_grad_(grad)
         th, tw, tb, tga, tbe = mk(h), mk(w), mk(b), mk(gamma), mk(beta)
+        if not grad:
+            with torch.no_grad():
+                return dict(z=mod.tconv(th, tw, tb, stride, dil)[0])
         zz, sc, sh, mean, var = mod.tconv(th, tw, tb, stride, dil, tga if bn else None, tbe if bn else None, 1e-5, bn)
         loss = (zz * gz.to(dev, dt)).sum()
         if bn:
