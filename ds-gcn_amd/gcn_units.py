@@ -124,56 +124,96 @@ def _check_act(act):
 
 
 class dgphgcn1(nn.Module):
-    """Dynamic-semantic graph conv.  Implemented configuration = the one every shipped DS-STGCN
-    config selects (configs/dsstgcn/DSSTGCN_model.py:10-27): decompose + node/edge attention +
-    subset-wise alpha/beta, ctr='T', ada='T', tanh / softmax.  Other flag combinations of the
-    reference class are research variants outside BASELINE's configs and raise."""
+    """Dynamic-semantic graph conv (reference: pyskl/models/gcns/utils/gcn.py:2074-2370).  The flag set every shipped
+    DS-STGCN config selects (configs/dsstgcn/DSSTGCN_model.py:10-27: decompose + node/edge attention + subset-wise
+    alpha/beta) runs on K-B (``kernels.dynadj``); the other combinations of the reference's switches — the paper's ablation
+    arms — run on the flag-specialised K-B (``kernels.dynadj_flags``, csrc/dynadj_flags.hip):
+
+      decompose        off: three plain subsets (conv1 / conv2 have K*mid rows; no conv1_se / conv2_se / edge_linears, and
+                       node_attention / edge_attention are ignored, as the reference ignores them)
+      node_attention   off: conv1_se / conv2_se have S*mid rows, no node-typed select
+      edge_attention   off: subset 1 takes plain differences like the other two
+      subset_wise      off: alpha[0] / beta[0] scale every subset (alpha[1:] / beta[1:] get an exact zero gradient)
+      ada_attention    ada_linears = Conv2d(K, edge_num*K, 1) mixes the three Grams per edge class before the softmax
+      stage            False switches node/edge attention, target_specific, decompose and subset_wise off (gcn.py:2123-2128)
+      sub_att, add_type   accepted: at K = 3 they change neither a shape nor the arithmetic of this class
+
+    Rejected (NotImplementedError naming the flag): target_specific with decompose (a node-typed `pre` conv), ctr / ada
+    other than 'T', activations other than tanh / softmax / ReLU, K != 3, and on the flag path V > 32, mid > 64,
+    edge_num > 16, num_types > 16.  Under decompose subset 2 pairs conv1_se with itself: conv2_se is created and never
+    used (quirk Q1)."""
 
     def __init__(self, in_channels, out_channels, A, edge_type, node_type, ratio=0.25, decompose=False, ctr='T',
                  ada='T', node_attention=False, edge_attention=False, ada_attention=False, target_specific=False,
                  add_type=False, sub_att=True, stage=True, num_types=5, edge_num=15, subset_wise=True,
                  ada_act='softmax', ctr_act='tanh', norm='BN', act='ReLU'):
         super().__init__()
+        if stage is False:                                    # gcn.py:2123-2128: before any parameter is created
+            node_attention = edge_attention = target_specific = decompose = subset_wise = False
         assert ada_act in ['tanh', 'relu', 'sigmoid', 'softmax']
         assert ctr_act in ['tanh', 'relu', 'sigmoid', 'softmax']
         assert ctr in [None, 'NA', 'T']
         assert ada in [None, 'NA', 'T']
-        supported = (decompose and node_attention and edge_attention and subset_wise and sub_att and stage
-                     and not ada_attention and not target_specific and not add_type and ctr == 'T' and ada == 'T'
-                     and ada_act == 'softmax' and ctr_act == 'tanh')
-        if not supported:
-            raise NotImplementedError(
-                'dgphgcn1: only the shipped DS-STGCN configuration (decompose, node_attention, edge_attention, '
-                "subset_wise, sub_att, ctr='T', ada='T', tanh/softmax) has a HIP path")
+        for flag, bad in (('target_specific', bool(target_specific and decompose)),
+                          ("ctr (only 'T')", ctr != 'T'), ("ada (only 'T')", ada != 'T'),
+                          ("ctr_act (only 'tanh')", ctr_act != 'tanh'), ("ada_act (only 'softmax')", ada_act != 'softmax')):
+            if bad:
+                raise NotImplementedError(f'dgphgcn1: {flag} has no HIP path')
         _check_act(act)
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.num_subsets = K = A.size(0)
         self.num_types = num_types
         self.edge_num = edge_num
+        self.decompose, self.node_attention = bool(decompose), bool(node_attention)
+        self.edge_attention, self.ada_attention = bool(edge_attention), bool(ada_attention)
+        self.subset_wise, self.sub_att, self.add_type = bool(subset_wise), bool(sub_att), add_type
+        self.target_specific = bool(target_specific)
         if ratio is None:
             ratio = 1 / K
         self.ratio = ratio
         self.mid_channels = mid = int(ratio * out_channels)
-        self.semantic_num = S = ceil(K / 3)
-        self.norm_num = K - S
         if K != 3:
-            raise NotImplementedError('the HIP dynadj kernel implements K=3 subsets (2 plain + 1 semantic)')
-        self.register_buffer('node_type_idx', torch.as_tensor(node_type).to(torch.int32).contiguous(),
-                             persistent=False)
-        self.register_buffer('edge_type_idx', torch.as_tensor(edge_type).to(torch.int32).contiguous(),
-                             persistent=False)
+            raise NotImplementedError(f'dgphgcn1: num_subsets (A.size(0)) = {K}: the HIP dynadj kernels implement K = 3 '
+                                      'subsets (2 plain + 1 semantic)')
+        self.semantic_num = S = ceil(K / 3) if decompose else 0
+        self.norm_num = K - S
+        # the shipped arithmetic (sub_att / add_type do not enter it at K = 3) stays on today's K-B
+        self._shipped = bool(decompose and node_attention and edge_attention and subset_wise and not ada_attention)
+        V = A.size(-1)
+        nt = torch.as_tensor(node_type).to(torch.int32).contiguous()
+        et = torch.as_tensor(edge_type).to(torch.int32).contiguous()
+        if not self._shipped:
+            typed = decompose and node_attention
+            classed = (decompose and edge_attention) or ada_attention
+            for flag, bad in ((f'{V} joints (V <= 32)', V > 32),
+                              (f'ratio {ratio} gives mid = {mid} (1 <= mid <= 64)', not 0 < mid <= 64),
+                              (f'edge_num = {edge_num} (up to 16 edge classes)', classed and not 0 < edge_num <= 16),
+                              (f'num_types = {num_types} (up to 16 node types)', typed and not 0 < num_types <= 16)):
+                if bad:
+                    raise NotImplementedError(f'dgphgcn1: {flag}: outside the flag-specialised K-B')
+            if typed and not (nt.numel() == V and 0 <= int(nt.min()) and int(nt.max()) < num_types):
+                raise ValueError(f'dgphgcn1: node_type must hold {V} values in [0, {num_types})')
+            if classed and not (et.numel() == V * V and 0 <= int(et.min()) and int(et.max()) < edge_num):
+                raise ValueError(f'dgphgcn1: edge_type must hold {V}x{V} values in [0, {edge_num})')
+        self.register_buffer('node_type_idx', nt, persistent=False)
+        self.register_buffer('edge_type_idx', et, persistent=False)
+        P = num_types if node_attention else 1
         # parameter creation order follows the reference ctor (same RNG consumption, same key order)
         self.A = nn.Parameter(A.clone())
         self.pre = nn.Sequential(nn.Conv2d(in_channels, mid * K, 1), _norm_layer(norm, mid * K), nn.ReLU())
         self.post = nn.Conv2d(mid * K, out_channels, 1)
-        self.alpha = nn.Parameter(torch.zeros(K))
-        self.beta = nn.Parameter(torch.zeros(K))
-        self.conv1_se = nn.Conv2d(in_channels, S * mid * num_types, kernel_size=1)
-        self.conv2_se = nn.Conv2d(in_channels, S * mid * num_types, kernel_size=1)   # never used (quirk Q1)
+        self.alpha = nn.Parameter(torch.zeros(K if sub_att else 3))
+        self.beta = nn.Parameter(torch.zeros(K if sub_att else 3))
+        if decompose:
+            self.conv1_se = nn.Conv2d(in_channels, S * mid * P, kernel_size=1)
+            self.conv2_se = nn.Conv2d(in_channels, S * mid * P, kernel_size=1)   # never used (quirk Q1)
         self.conv1 = nn.Conv2d(in_channels, self.norm_num * mid, 1)
         self.conv2 = nn.Conv2d(in_channels, self.norm_num * mid, 1)
-        self.edge_linears = nn.Conv2d(S * mid, edge_num * S * mid, 1)
+        if edge_attention and decompose:
+            self.edge_linears = nn.Conv2d(S * mid, edge_num * S * mid, 1)
+        if ada_attention:
+            self.ada_linears = nn.Conv2d(K, edge_num * K, 1)
         if in_channels != out_channels:
             self.down = nn.Sequential(nn.Conv2d(in_channels, out_channels, 1), _norm_layer(norm, out_channels))
         else:
@@ -181,9 +221,9 @@ class dgphgcn1(nn.Module):
         self.bn = _norm_layer(norm, out_channels)
 
     def flat_groups(self):
-        """(see dgmstcn.flat_groups) the three mean-pooled projections run as one conv over their stacked weights"""
-        return [[self.conv1.weight, self.conv2.weight, self.conv1_se.weight],
-                [self.conv1.bias, self.conv2.bias, self.conv1_se.bias]]
+        """(see dgmstcn.flat_groups) the mean-pooled projections run as one conv over their stacked weights"""
+        se = [self.conv1_se] if self.decompose else []
+        return [[c.weight for c in [self.conv1, self.conv2] + se], [c.bias for c in [self.conv1, self.conv2] + se]]
 
     def fusable_pairs(self):
         """(conv, bn) pairs whose BatchNorm consumes the conv's output directly (checkpoint.fuse_conv_bn); `pre` and
@@ -192,8 +232,20 @@ class dgphgcn1(nn.Module):
 
     def adjacency(self, xbar, host=None):
         """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V).  host: a kernels.bn_batch whose waiting
-        finalize jobs K-B's launch carries."""
-        c1, c2, cs, el = self.conv1, self.conv2, self.conv1_se, self.edge_linears
+        finalize jobs K-B's launch carries (shipped flag set only)."""
+        c1, c2 = self.conv1, self.conv2
+        if not self._shipped:
+            cs = self.conv1_se if self.decompose else None
+            el = self.edge_linears if self.decompose and self.edge_attention else None
+            al = self.ada_linears if self.ada_attention else None
+            return kernels.ops().dynadj_flags(
+                xbar, self.A, self.alpha, self.beta, c1.weight.flatten(1), c1.bias, c2.weight.flatten(1), c2.bias,
+                None if cs is None else cs.weight.flatten(1), None if cs is None else cs.bias,
+                None if el is None else el.weight.flatten(1), None if el is None else el.bias,
+                None if al is None else al.weight.flatten(1), None if al is None else al.bias,
+                self.node_type_idx.reshape(-1), self.edge_type_idx.reshape(-1),
+                self.num_types if self.node_attention else 1, self.edge_num, self.subset_wise)
+        cs, el = self.conv1_se, self.edge_linears
         kw = {} if host is None else dict(host=host)
         return kernels.ops().dynadj(
             xbar, self.A, self.alpha, self.beta,
@@ -209,7 +261,10 @@ class dgphgcn1(nn.Module):
             xbar = ops.tmean(x, 32) if x.shape[-1] <= 32 else ops.tmean(x)
         fork = getattr(ops, 'side_branch', None)
         batch = getattr(ops, 'bn_batch', None)
-        if batch is not None and not getattr(ops, 'OVERLAP', False):
+        if not self._shipped:                     # the ablation arms: K-B, then the `pre` conv (dghgcn's chain)
+            ahat = self.adjacency(xbar)
+            zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
+        elif batch is not None and not getattr(ops, 'OVERLAP', False):
             # `pre` conv first, K-B behind it: K-B (and its projection conv) read nothing of the `pre` BatchNorm, so its
             # finalize rides in K-B's launch as extra workgroups (kernels.bn_batch) instead of a launch of its own between
             # the conv and K-A; the backward mirrors it (K-A's rows -> the coefficient job hosted by K-B's backward)

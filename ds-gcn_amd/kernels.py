@@ -2942,3 +2942,8 @@ def data_bn(x, bn, bn_type):
     """x (N, M, T, V, C) -> (N*M, C, T, V): the backbones' input BatchNorm1d ('VC' | 'MVC') without the permute copies."""
     training = bn.training or not bn.track_running_stats or bn.running_mean is None
     return _DataBN.apply(x, bn.weight, bn.bias, bn, bn_type == 'MVC', training)
+
+
+# the flag-specialised K-B of dgphgcn1's ablation arms lives in a module of its own (csrc/dynadj_flags.hip's front);
+# re-exported here so that it is reached like every other op, through ops()
+from .kernels_flags import dynadj_flags  # noqa: E402,F401

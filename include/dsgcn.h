@@ -97,6 +97,28 @@ int dsgcn_dyntyped_bwd(const float* x12, const float* pq, const float* be, const
                        const int* edge_type, const float* dahat, float* dd_ws, float* dx12, float* dpq, float* ppar,
                        int pstride, int n, int mid, int V, int E, int flags, void* stream);
 
+/* K-B flags: the dynamic adjacency of dgphgcn1 (gcn.py:2074-2370) for its non-shipped flag sets (the ablation arms; the
+ * shipped set stays on dsgcn_dynadj_*).  flags selects a compile-time instantiation:
+ *   flags & 3   0 = decompose off: proj (n, 6*mid, ld) rows [conv1 (3*mid) | conv2 (3*mid)];
+ *               1 / 2 = decompose: proj (n, 4*mid + mid*P, ld) rows [conv1 (2*mid) | conv2 (2*mid) | conv1_se (mid*P)],
+ *               subset 2 pairs the conv1_se rows with themselves; 2 = node-typed rows c*P + node_type[v] (1: P = 1)
+ *   flags & 4   edge linear on subset 1: pq (n, E*mid, 2, 32) = edge_linears . [x1_1 | x2_1] without its bias, be (E*mid)
+ *   flags & 8   class-mixed Gram: wa (3E, 3), ba (3E) = ada_linears, applied per edge class before the softmax
+ *   flags & 16  per-subset alpha / beta (else alpha[0] / beta[0] for all three subsets)
+ * V <= 32, mid <= 64, E <= 16, P <= 16, ld >= V; node_type (V) in [0,P), edge_type (V*V) in [0,E) (clamped on load).
+ *   bwd: dd_ws workspace (n, 3*mid, V, V); outputs dproj (every element written), dpq (edge only, every element
+ *        written) and ppar (n, pstride >= dsgcn_dynflag_partial_stride): per-sample partials [sum_c dAhat (3*V*V) |
+ *        dalpha_k (3) | dbeta_k (3) | dbe (E*mid, edge only) | dwa (9E) | dba (3E) (mixed Gram only)], summed by
+ *        dsgcn_colsum; without flag 16 the caller adds the three dalpha_k / dbeta_k. */
+int dsgcn_dynflag_partial_stride(int mid, int V, int E, int flags);
+int dsgcn_dynflag_fwd(const float* proj, const float* pq, const float* be, const float* wa, const float* ba,
+                      const float* A, const float* alpha, const float* beta, const int* node_type, const int* edge_type,
+                      float* ahat, int n, int mid, int V, int ld, int P, int E, int flags, void* stream);
+int dsgcn_dynflag_bwd(const float* proj, const float* pq, const float* be, const float* wa, const float* ba,
+                      const float* alpha, const float* beta, const int* node_type, const int* edge_type,
+                      const float* dahat, float* dd_ws, float* dproj, float* dpq, float* ppar, int pstride, int n,
+                      int mid, int V, int ld, int P, int E, int flags, void* stream);
+
 /* Block output (materialise once): out = relu?(x1*s1+h1 (+ x2*s2+h2 | + x2)), xbar = mean_t out (optional).
  * Replaces BN + residual add + ReLU of dgstgcn.py:63-65 / tcn.py:427 and x.mean(-2) of gcn.py:2246.
  * relu: bit 0 = the outer ReLU, bit 1 = a ReLU on the first term before the add (CTR-GCN: msg3d_utils.py:139-141
