@@ -23,6 +23,8 @@ from .data_parallel import FlatParams, FlatDataParallel, shard_batch
 from .train import FlatSGD, cosine_lr
 from .checkpoint import load_checkpoint, save_checkpoint, resume, find_resume, fuse_conv_bn
 from .engine import TrainEngine
-from .apis import train_model, EpochRunner, epoch_indices
+from .apis import train_model, EpochRunner, EvalLoop, epoch_indices, evaluate_scores
+from .infer import InferEngine
+from .testing import test_model, dump_results, load_results, ensemble_results
 
 __version__ = '0.1.0'

@@ -222,6 +222,26 @@ class EpochRunner:
         return self
 
 
+def evaluate_scores(scores, labels, metrics=('top_k_accuracy', 'mean_class_accuracy'), metric_options=None):
+    """``BaseDataset.evaluate`` (datasets/base.py:111-199) on (n, classes) scores: ``top_k_accuracy`` -> ``top{k}_acc``,
+    ``mean_class_accuracy``, ``confusion_matrix``."""
+    metric_options = metric_options or dict(top_k_accuracy=dict(topk=(1, 5)))
+    out = OrderedDict()
+    for metric in metrics:
+        if metric == 'top_k_accuracy':
+            topk = metric_options.get('top_k_accuracy', {}).get('topk', (1, 5))
+            topk = (topk,) if isinstance(topk, int) else tuple(topk)
+            for k, acc in zip(topk, top_k_accuracy(scores, labels, topk)):
+                out[f'top{k}_acc'] = float(acc)
+        elif metric == 'mean_class_accuracy':
+            out['mean_class_accuracy'] = float(mean_class_accuracy(scores, labels)[0])
+        elif metric == 'confusion_matrix':
+            out['confusion_matrix'] = mean_class_accuracy(scores, labels)[1]
+        else:
+            raise KeyError(f'metric {metric} is not supported')
+    return out
+
+
 class EvalLoop:
     """The reference's ``DistEvalHook`` (pyskl/core/evaluation.py:11-19 over mmcv ``EvalHook`` / ``DistEvalHook``) for the
     epoch-based runner: after every ``interval``-th epoch (from ``start`` on) the val split is scored with ``forward_test``
@@ -236,7 +256,9 @@ class EvalLoop:
 
     def __init__(self, dataset, batch_size=1, interval=1, start=None, metrics='top_k_accuracy',
                  metric_options=None, save_best='auto', rule=None, by_epoch=True, device='cuda',
-                 broadcast_bn_buffer=True, **unsupported):
+                 broadcast_bn_buffer=True, engine=None, **unsupported):
+        """engine: an ``infer.InferEngine`` over the model that ``predict`` is given — the scores then come from its
+        hipGraph replay and stay on the device until the end of the pass (one read-back); ``None``: ``forward_test``."""
         if not by_epoch:
             raise NotImplementedError('evaluation by iteration is not used by the skeleton configs')
         unsupported.pop('key_indicator', None)
@@ -255,6 +277,7 @@ class EvalLoop:
         self.key_indicator = None if save_best in ('auto', None, True) else save_best
         self.best_score = self.best_ckpt = None
         self.broadcast_bn_buffer = bool(broadcast_bn_buffer)
+        self.engine = engine
         self.results = []
 
     def restore(self, meta):
@@ -297,36 +320,32 @@ class EvalLoop:
     @torch.no_grad()
     def predict(self, model, rank, world):
         """This rank's share of the val scores, in its sampler order."""
+        if self.engine is not None and self.engine.model is not model:
+            raise ValueError('EvalLoop(engine=...): the engine was built over another model')
         n = len(self.source)
         order = epoch_indices(n, 0, 0, rank, world, shuffle=False)
         was_training = model.training
         model.eval()
-        part = []
+        part, on_device = [], []
         # the reference samples val clips in loader worker processes: the test-mode sampler's np.random.seed(255) never
         # touches the TRAINING process's stream.  Here both run in one process, so the stream is put back afterwards.
         rng = np.random.get_state()
         try:
             for b in range(0, len(order), self.batch_size):
                 kp, _ = self.source.batch(order[b:b + self.batch_size])
-                part.extend(model(keypoint=kp, return_loss=False))
+                if self.engine is not None:
+                    on_device.append(self.engine(kp))
+                else:
+                    part.extend(model(keypoint=kp, return_loss=False))
         finally:
             np.random.set_state(rng)
+        if on_device:
+            part.extend(torch.cat(on_device).cpu().numpy())       # the pass's one device->host copy
         model.train(was_training)
         return part
 
     def evaluate(self, scores, labels):
-        out = OrderedDict()
-        for metric in self.metrics:
-            if metric == 'top_k_accuracy':
-                topk = self.metric_options.get('top_k_accuracy', {}).get('topk', (1, 5))
-                topk = (topk,) if isinstance(topk, int) else tuple(topk)
-                for k, acc in zip(topk, top_k_accuracy(scores, labels, topk)):
-                    out[f'top{k}_acc'] = float(acc)
-            elif metric == 'mean_class_accuracy':
-                out['mean_class_accuracy'] = float(mean_class_accuracy(scores, labels)[0])
-            elif metric == 'confusion_matrix':
-                out['confusion_matrix'] = mean_class_accuracy(scores, labels)[1]
-        return out
+        return evaluate_scores(scores, labels, self.metrics, self.metric_options)
 
     def _better(self, key, value):
         if self.best_score is None:

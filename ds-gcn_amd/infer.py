@@ -1,0 +1,132 @@
+"""Multi-clip inference of a recognizer on one GPU, the MI355X way: the counterpart of ``engine.TrainEngine`` for the test
+pass (reference: ``RecognizerGCN.forward_test``, pyskl/models/recognizers/recognizergcn.py:53-107, driven by mmcv's
+``multi_gpu_test`` from tools/test.py:101-105).
+
+``RecognizerGCN.forward_test`` here runs eagerly, asks the backbone for the whole last-block activation although a
+``GCNHead`` only reads its plane means, does the head as ~8 framework launches and ends every batch with a blocking
+``.cpu().numpy()``.  ``InferEngine`` is the same arithmetic as
+
+    one hipGraph replay per batch shape:  weight images of the wide convs  ->  backbone(x, pool=True)  ->  head_test
+
+and hands back DEVICE tensors: nothing in a call waits for the GPU, the caller reads back when it wants to (``test_model``:
+once per pass)."""
+import torch
+
+from . import kernels
+from .heads import SimpleHead
+
+
+class InferEngine:
+
+    def __init__(self, model, use_graph=True, warmup_eager=1, strict_graph=False, max_views=None):
+        """use_graph: capture one hipGraph per input shape after ``warmup_eager`` eager calls of that shape and replay it
+        from then on.  strict_graph: a failed capture raises instead of falling back to eager launches (``capture_error``
+        keeps the reason either way; multi-GPU runs: ranks must not silently differ).  max_views: the largest number of
+        clips (videos x clips) one forward may hold; a larger batch is cut into chunks of whole videos (a single video is
+        never split), at most two chunk shapes, results concatenated.
+
+        The captured graph contains the launches that build the bf16 weight images of the wide convs, so a replay after the
+        parameters were changed IN PLACE (an optimizer step, ``load_state_dict``) computes with the new values.  Anything
+        that changes tensor addresses or the module tree (``.to()``, ``fuse_conv_bn`` creating a bias, swapping a layer)
+        needs ``reset()`` — or build the engine afterwards, as ``test_model`` does."""
+        self.model = model
+        self._want_graph = bool(use_graph)
+        self.warmup_eager = int(warmup_eager)
+        self.strict_graph = strict_graph
+        self.max_views = None if not max_views else int(max_views)
+        # the engine's OWN table of weight images (kernels.private_weight_images): entries pinned by a capture live and die
+        # with this object, and a TrainEngine beside it never rebuilds them (nor this engine the TrainEngine's)
+        self._images = {}
+        self.reset()
+
+    def reset(self):
+        """Forget every captured graph, static buffer and weight image (after a structural change of the model)."""
+        self._graphs = {}          # (shape, dtype, average_clips) -> (graph, static input, static output)
+        self._seen = {}            # same key -> eager calls taken
+        self._images.clear()
+        self.use_graph = self._want_graph
+        self.capture_error = None
+        self.replays = self.eager_calls = 0
+        head, backbone = self.model.cls_head, self.model.backbone
+        # the pooled last block + the one-launch head apply when the head is the plain 'GCN' pooling head; anything else
+        # takes the module calls of forward_test (still on the device)
+        self.fused_head = bool(getattr(backbone, 'supports_pool', False) and isinstance(head, SimpleHead)
+                               and type(head).forward is SimpleHead.forward and head.mode == 'GCN' and head.dropout is None)
+
+    # ---- pieces --------------------------------------------------------------------------------------------
+    def _forward(self, x):
+        model = self.model
+        N, clips, M = x.shape[:3]
+        mode = model.test_cfg['average_clips']
+        head = model.cls_head
+        if self.fused_head and kernels.head_test_fits(clips, head.in_c, head.num_classes):
+            feat = model.backbone(x.float().flatten(0, 1), pool=True)                 # (N*clips, M, C) plane means
+            return kernels.head_test(feat.reshape(N * clips * M, -1), head.fc_cls.weight, head.fc_cls.bias, N, clips, M, mode)
+        scores = head(model.extract_feat(x.float().flatten(0, 1))).view(N, clips, -1)
+        if mode == 'prob':
+            scores = torch.softmax(scores, dim=2).mean(1)
+        elif mode == 'score':
+            scores = scores.mean(1)
+        return scores
+
+    def _capture(self, x):
+        sx = x.clone()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        # one chain on the capturing stream: no side streams, no parallel branches
+        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+            out = self._forward(sx)
+        torch.cuda.synchronize()
+        return g, sx, out
+
+    def _run(self, x):
+        key = (tuple(x.shape), x.dtype, self.model.test_cfg['average_clips'])
+        if self.use_graph and key not in self._graphs and self._seen.get(key, 0) >= self.warmup_eager:
+            try:
+                self._graphs[key] = self._capture(x)
+            except Exception as exc:       # noqa: BLE001 — report and fall back (or raise) below
+                self.capture_error = f'{type(exc).__name__}: {exc}'
+                if self.strict_graph:
+                    raise
+                self.use_graph = False
+        if self.use_graph and key in self._graphs:
+            g, sx, out = self._graphs[key]
+            sx.copy_(x)
+            g.replay()
+            self.replays += 1
+            return out.clone()             # the static buffer is rewritten by the next replay
+        out = self._forward(x)
+        self._seen[key] = self._seen.get(key, 0) + 1
+        self.eager_calls += 1
+        return out
+
+    def _chunks(self, N, clips):
+        if self.max_views is None or N * clips <= self.max_views:
+            return [(0, N)]
+        per = max(1, self.max_views // clips)
+        return [(a, min(a + per, N)) for a in range(0, N, per)]
+
+    # ---- the call ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def __call__(self, keypoint):
+        """keypoint (N, clips, M, T, V, C) on the device -> DEVICE tensor (N, classes) — (N, clips, classes) when the
+        model's ``test_cfg['average_clips']`` is None.  No host synchronisation."""
+        if keypoint.dim() != 6:
+            raise ValueError(f'InferEngine expects (N, clips, M, T, V, C), got {tuple(keypoint.shape)}')
+        if not keypoint.is_cuda:
+            raise RuntimeError('InferEngine runs on the GPU only (there is no CPU path): move the batch to the device')
+        model = self.model
+        was_training = model.training
+        if was_training:
+            model.eval()
+        try:
+            with kernels.private_weight_images(self._images):
+                parts = [self._run(keypoint[a:b]) for a, b in self._chunks(keypoint.shape[0], keypoint.shape[1])]
+        finally:
+            if was_training:
+                model.train()
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def graphed(self, keypoint):
+        key = (tuple(keypoint.shape), keypoint.dtype, self.model.test_cfg['average_clips'])
+        return key in self._graphs

@@ -139,6 +139,12 @@ def gather_results(part, size):
         return list(part)[:size]
     parts = [None] * world
     dist.all_gather_object(parts, list(part))
+    return interleave_parts(parts, size)
+
+
+def interleave_parts(parts, size):
+    """parts[r] = the results of samples r, r + world, ... -> one list in dataset order, cut to ``size`` (the wrapped
+    padding of the sampler falls off the end)."""
     hole = object()
     out = []
     for group in zip_longest(*parts, fillvalue=hole):

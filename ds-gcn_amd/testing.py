@@ -1,0 +1,144 @@
+"""``test_model`` — the testing half of the reference's command line (tools/test.py:71-176 over mmcv's ``multi_gpu_test``)
+with the call shape of ``apis.train_model``:
+
+    load the checkpoint [-> fuse_conv_bn] -> InferEngine over the model
+    every rank: samples rank, rank + world, ... in dataset order through the engine (one hipGraph replay per batch; the
+                scores stay on the device; ONE read-back at the end of the pass)
+    gather_results -> rank 0 writes ``out`` and evaluates the metrics
+
+``dump_results`` / ``ensemble_results`` end the j / b / jm / bm workflow inside the package: the paper's headline rows are
+sums of four such result files."""
+import json
+import os
+import pickle
+
+import numpy as np
+
+from .apis import EvalLoop, _get, _rank_world, evaluate_scores
+from .checkpoint import fuse_conv_bn, load_checkpoint
+from .infer import InferEngine
+from .recognizers import gather_results
+
+
+def test_batch_size(cfg):
+    """``data.test_dataloader.videos_per_gpu``, else ``data.videos_per_gpu``, else 1 (tools/test.py:143-147)."""
+    data = _get(cfg, 'data', None) or {}
+    loader = data.get('test_dataloader', None) or {}
+    return int(loader.get('videos_per_gpu', data.get('videos_per_gpu', 1)))
+
+
+test_batch_size.__test__ = False          # (a library function, not a pytest case)
+
+
+def dump_results(results, out):
+    """What ``dataset.dump_results`` writes (datasets/base.py:240-242): the list of per-video score arrays as ``.pkl``
+    (float32 arrays) or ``.json`` (nested lists), in dataset order."""
+    results = [np.asarray(r, dtype=np.float32) for r in results]
+    folder = os.path.dirname(os.path.abspath(out))
+    os.makedirs(folder, exist_ok=True)
+    suffix = os.path.splitext(out)[1].lower()
+    if suffix in ('.pkl', '.pickle'):
+        with open(out, 'wb') as f:
+            pickle.dump(results, f)
+    elif suffix == '.json':
+        with open(out, 'w') as f:
+            json.dump([r.tolist() for r in results], f)
+    else:
+        raise ValueError(f'dump_results: {out!r}: the output file is .pkl or .json')
+    return out
+
+
+def load_results(path):
+    suffix = os.path.splitext(path)[1].lower()
+    if suffix in ('.pkl', '.pickle'):
+        with open(path, 'rb') as f:
+            data = pickle.load(f)
+    elif suffix == '.json':
+        with open(path) as f:
+            data = json.load(f)
+    else:
+        raise ValueError(f'load_results: {path!r}: a result file is .pkl or .json')
+    return [np.asarray(r, dtype=np.float32) for r in data]
+
+
+def ensemble_results(files_or_lists, weights=None, labels=None, metrics=('top_k_accuracy', 'mean_class_accuracy')):
+    """Weighted sum of several result sets (file names or lists of per-video score arrays; the j + b + jm + bm rows of the
+    paper's tables, weights 1 by default) -> ``dict(results=[(classes,) float32 ...], metrics=OrderedDict | None)``;
+    the metrics are those of the summed scores and need ``labels``."""
+    sets = [load_results(s) if isinstance(s, (str, os.PathLike)) else [np.asarray(r, dtype=np.float32) for r in s]
+            for s in files_or_lists]
+    if not sets:
+        raise ValueError('ensemble_results: nothing to sum')
+    weights = [1.0] * len(sets) if weights is None else [float(w) for w in weights]
+    if len(weights) != len(sets):
+        raise ValueError(f'ensemble_results: {len(sets)} result sets, {len(weights)} weights')
+    if any(len(s) != len(sets[0]) for s in sets):
+        raise ValueError(f'ensemble_results: the result sets differ in length: {[len(s) for s in sets]}')
+    total = sum(np.stack(s).astype(np.float32) * np.float32(w) for s, w in zip(sets, weights))
+    vals = evaluate_scores(total, labels, metrics) if labels is not None else None
+    return dict(results=list(total), metrics=vals)
+
+
+def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
+               metrics=('top_k_accuracy', 'mean_class_accuracy'), average_clips=None, device='cuda', use_graph=True):
+    """Score ``dataset`` with ``model`` the way the reference's tools/test.py does for the skeleton configs.
+
+    dataset: a map-style dataset of ``dict(keypoint=(clips, M, T, V, C), label)`` items, or a (``SkeletonStore``,
+    ``SkeletonBatcher``) pair built from the test pipeline; ``None``: built from ``cfg.data.test`` with ``test_mode=True``.
+    checkpoint: loaded with ``load_checkpoint``; ``None``: ``<cfg.work_dir>/latest.pth`` when it exists, else the model as
+    it is.  fuse: ``fuse_conv_bn`` before the engine is built.  average_clips: 'prob' / 'score' override the model's
+    ``test_cfg`` for this pass (``--average-clips``; ``None`` = keep it).  out: rank 0 writes the results there (.pkl / .json).
+
+    -> ``dict(results=[...], metrics=OrderedDict | None)``: the scores of every video in dataset order on every rank
+    (``(classes,)`` float32 arrays; ``(clips, classes)`` when the model's ``average_clips`` is None, which has no metrics);
+    ``metrics`` on rank 0 only.  ``cfg.evaluation.metric_options`` is honoured.  The numpy RNG state is left as found."""
+    rank, world = _rank_world()
+    data = _get(cfg, 'data', None) or {}
+    if dataset is None:
+        from .pipeline import build_dataset
+        test_cfg = dict(data['test'])
+        test_cfg['test_mode'] = True
+        dataset = build_dataset(test_cfg)
+    if isinstance(dataset, list) and len(dataset) == 1:
+        dataset = dataset[0]
+    if average_clips not in (None, 'prob', 'score'):
+        raise ValueError(f'average_clips={average_clips!r}: "prob", "score" or None (keep the model\'s test_cfg)')
+    work_dir = _get(cfg, 'work_dir', None)
+    if checkpoint is None and work_dir and os.path.exists(os.path.join(work_dir, 'latest.pth')):
+        checkpoint = os.path.join(work_dir, 'latest.pth')
+    if checkpoint is not None:
+        load_checkpoint(model, checkpoint, map_location='cpu')
+    model = model.to(device)
+    was_training = model.training
+    model.eval()
+    if fuse:
+        fuse_conv_bn(model)
+    mode_before = model.test_cfg['average_clips']
+    if average_clips is not None:
+        model.test_cfg['average_clips'] = average_clips
+    try:
+        # built AFTER the structural steps above (device move, conv + BatchNorm folding): its graphs hold addresses
+        engine = InferEngine(model, use_graph=use_graph, strict_graph=world > 1)
+        eval_cfg = _get(cfg, 'evaluation', None) or {}
+        loop = EvalLoop(dataset, batch_size=test_batch_size(cfg), metrics=list(metrics),
+                        metric_options=eval_cfg.get('metric_options'), save_best=None,
+                        device=next(model.parameters()).device, engine=engine)
+        part = loop.predict(model, rank, world)
+        results = gather_results(part, len(loop.source))
+        per_clip = model.test_cfg['average_clips'] is None
+    finally:
+        model.test_cfg['average_clips'] = mode_before
+        model.train(was_training)
+    vals = None
+    if rank == 0:
+        if out is not None:
+            dump_results(results, out)
+        if not per_clip:
+            vals = loop.evaluate(np.stack(results), loop.labels())
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    return dict(results=results, metrics=vals)
+
+
+test_model.__test__ = False

@@ -572,6 +572,22 @@ int dsgcn_head_loss_fwd(const float* feat, const float* w, const float* b, const
 int dsgcn_head_loss_bwd(const float* prob, const float* pooled, const float* w, const long long* label, const float* gloss,
                         int N, int M, int C, int K, float loss_weight, float* dfeat, float* dw, float* db, void* stream);
 
+/* The test-time head: simple_head.py:88-98 (person mean + fc_cls) followed by recognizergcn.py's average_clips step —
+ * about eight framework launches and an (N*clips, K) round trip.  ONE launch, one workgroup per video.
+ *   feat (N*clips*M, C): per-person plane means, clip-major within a video (what dsgcn_fuse_out_fwd_drop writes for a
+ *   backbone input of (N*clips, M, ...));  w (K, C), b (K) or NULL.
+ *   score[n, q, k] = <(1/M) sum_m feat[(n*clips + q)*M + m], w[k]> + b[k]
+ *   clip_score (N, clips, K) or NULL: the scores;
+ *   out (N, K): mode 0 ('prob') = mean_q softmax_k(score[n, q]), max-subtracted; mode 1 ('score') = mean_q score[n, q];
+ *   mode 2 (None): unused, may be NULL (clip_score is the result).  out NULL with clip_score given: only the scores.
+ *   A NaN among a clip's scores makes that video's softmax row NaN, no other video's.  All sums in a fixed order:
+ *   repeated launches are bit-identical.
+ * DSGCN_EINVAL: NULL feat / w, a non-positive size, mode outside 0..2, nothing to write (both outputs NULL, or mode 2
+ * without clip_score).  DSGCN_EUNSUPPORTED: clips * (C + K) floats above 60 KB of LDS (C = 256 with K = 400 takes up to
+ * 23 clips; every N and M are taken).  C % 4 == 0 with a 16-byte aligned w reads the weights 16 bytes at a time. */
+int dsgcn_head_test_fwd(const float* feat, const float* w, const float* b, int N, int clips, int M, int C, int K, int mode,
+                        float* clip_score, float* out, void* stream);
+
 /* Training-mode buffer update of njobs BatchNorm layers in one launch (what F.batch_norm(training=True) does to its
  * buffers, momentum form): running_mean = (1 - m) running_mean + m mean; running_var = (1 - m) running_var + m var *
  * unbias (unbias = count / (count - 1)); num_batches_tracked += 1 (entries may be NULL).  The arrays are HOST arrays of
