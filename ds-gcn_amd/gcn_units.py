@@ -20,6 +20,7 @@ import torch.nn as nn
 import contextlib
 
 from . import kernels
+from . import kernels_plain
 
 
 class Deferred(NamedTuple):
@@ -312,11 +313,14 @@ class dggcn(nn.Module):
     ``DGSTGCN(gcn_type='dggcn')``, dgstgcn.py:42-43): K subsets, each with its own mean-pooled projections x1_k = conv1_k
     (xbar), x2_k = conv2_k(xbar), ``Ahat_k = A_k + alpha * tanh(x1_k[u] - x2_k[w]) + beta * softmax_u(sum_c x1_k x2_k)`` — the
     ``dgphgcn1`` arithmetic without the node-typed select and the edge-typed linear.  Implemented configuration: the
-    class defaults (ctr='T', ada='T', tanh / softmax), subset_wise on or off.
+    class defaults (ctr='T', ada='T', tanh / softmax), subset_wise on or off, 1 <= K <= 16 (graph_cfg num_filter),
+    mid <= 64, V <= 32.
 
-    K-B (dsgcn_dynadj_*) evaluates one plain subset pair (a0-b0, a1-b1) exactly when its edge-typed linear is the
-    identity (one edge class, We = I, be = 0); the third subset goes through a second call whose first slot carries
-    (a2, b2).  Two launches instead of one and a concatenation of the result: this unit is an f-4 row, not a bench path."""
+    K != 3: the adjacency is one ``kernels.dynadj_plain`` call (K-C projections + the plain K-B, csrc/dynadj_plain.hip).
+    K == 3 keeps its earlier form (the kernel census and the frozen fixtures of that model pin it): K-B (dsgcn_dynadj_*)
+    evaluates one plain subset pair (a0-b0, a1-b1) exactly when its edge-typed linear is the identity (one edge class,
+    We = I, be = 0); the third subset goes through a second call whose first slot carries (a2, b2).  Two launches instead
+    of one and a concatenation of the result.  The choice is made from A.size(0) alone."""
 
     def __init__(self, in_channels, out_channels, A, ratio=0.25, ctr='T', ada='T', subset_wise=False, ada_act='softmax',
                  ctr_act='tanh', norm='BN', act='ReLU'):
@@ -331,13 +335,13 @@ class dggcn(nn.Module):
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.num_subsets = K = A.size(0)
-        if K != 3:
-            raise NotImplementedError('the HIP dynadj kernel implements K=3 subsets')
         self.subset_wise = subset_wise
         if ratio is None:
             ratio = 1 / K
         self.ratio = ratio
         self.mid_channels = mid = int(ratio * out_channels)
+        if K != 3:
+            kernels_plain.check_range('dggcn', K, mid, A.size(-1))
         # parameter creation order follows the reference ctor (same RNG consumption, same key order)
         self.A = nn.Parameter(A.clone())
         self.pre = nn.Sequential(nn.Conv2d(in_channels, mid * K, 1), _norm_layer(norm, mid * K), nn.ReLU())
@@ -351,11 +355,12 @@ class dggcn(nn.Module):
         else:
             self.down = None
         self.bn = _norm_layer(norm, out_channels)
-        V = A.size(-1)
-        # constants that turn K-B's typed slots into plain ones: one node type, one edge class, identity edge linear
-        self.register_buffer('_nt0', torch.zeros(V, dtype=torch.int32), persistent=False)
-        self.register_buffer('_et0', torch.zeros(V, V, dtype=torch.int32), persistent=False)
-        self.register_buffer('_we_eye', torch.eye(mid), persistent=False)
+        if K == 3:
+            V = A.size(-1)
+            # constants that turn K-B's typed slots into plain ones: one node type, one edge class, identity edge linear
+            self.register_buffer('_nt0', torch.zeros(V, dtype=torch.int32), persistent=False)
+            self.register_buffer('_et0', torch.zeros(V, V, dtype=torch.int32), persistent=False)
+            self.register_buffer('_we_eye', torch.eye(mid), persistent=False)
 
     def fusable_pairs(self):
         return [(self.post, self.bn)]
@@ -365,6 +370,11 @@ class dggcn(nn.Module):
         m, Ci = self.mid_channels, self.in_channels
         w1, b1 = self.conv1.weight.flatten(1), self.conv1.bias
         w2, b2 = self.conv2.weight.flatten(1), self.conv2.bias
+        K = self.num_subsets
+        if K != 3:
+            a = self.alpha if self.subset_wise else self.alpha[0].expand(K)
+            b = self.beta if self.subset_wise else self.beta[0].expand(K)
+            return kernels.ops().dynadj_plain(xbar, self.A, a, b, w1, b1, w2, b2)
         zw, zb = w1.new_zeros(m, Ci), b1.new_zeros(m)
         we, be = self._we_eye, zb
         a = self.alpha if self.subset_wise else self.alpha[0].expand(3)

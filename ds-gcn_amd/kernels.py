@@ -2947,6 +2947,8 @@ def data_bn(x, bn, bn_type):
 # the flag-specialised K-B of dgphgcn1's ablation arms lives in a module of its own (csrc/dynadj_flags.hip's front);
 # re-exported here so that it is reached like every other op, through ops()
 from .kernels_flags import dynadj_flags  # noqa: E402,F401
+# ... and so does the plain K-B of dggcn at any number of subsets (csrc/dynadj_plain.hip's front)
+from .kernels_plain import dynadj_plain  # noqa: E402,F401
 
 # the ops of the test pass (csrc/head_test.hip's front, the engine-owned weight-image table) live in a module of their own
 from .kernels_infer import head_test, head_test_fits, private_weight_images  # noqa: E402,F401

@@ -137,6 +137,9 @@ SIGNATURES = {
     'dsgcn_dynflag_partial_stride': [c_int] * 4,
     'dsgcn_dynflag_fwd': [c_f] * 8 + [c_i, c_i, c_f] + [c_int] * 7 + [c_st],
     'dsgcn_dynflag_bwd': [c_f] * 7 + [c_i, c_i] + [c_f] * 5 + [c_int] * 8 + [c_st],
+    'dsgcn_dynplain_partial_stride': [c_int] * 2,
+    'dsgcn_dynplain_fwd': [c_f] * 5 + [c_int] * 5 + [c_st],
+    'dsgcn_dynplain_bwd': [c_f] * 6 + [c_int] * 6 + [c_st],
     'dsgcn_dynadj_fwd_jobs': [c_f] * 6 + [c_i, c_i, c_f] + [c_int] * 6 + [ctypes.c_void_p, c_int, c_st],
     'dsgcn_dynadj_bwd_jobs': [c_f] * 5 + [c_i, c_i] + [c_f] * 4 + [c_int] * 7 + [ctypes.c_void_p, c_int, c_st],
     'dsgcn_head_loss_fwd': [c_f, c_f, c_f, c_i] + [c_int] * 4 + [ctypes.c_float] + [c_f] * 6 + [c_st],

@@ -119,6 +119,19 @@ int dsgcn_dynflag_bwd(const float* proj, const float* pq, const float* be, const
                       const float* dahat, float* dd_ws, float* dproj, float* dpq, float* ppar, int pstride, int n,
                       int mid, int V, int ld, int P, int E, int flags, void* stream);
 
+/* K-B plain: the dynamic adjacency of dggcn (gcn.py:1445-1584) for any number of subsets K — no node types, no edge
+ * classes.  proj (n, 2*K*mid, ld) rows [conv1 (K*mid) | conv2 (K*mid)], row k*mid + c, joint stride ld >= V; A (K,V,V),
+ * alpha, beta (K) -> ahat (n, K*mid, V, V) = A_k + alpha_k tanh(x1[c,u] - x2[c,w]) + beta_k softmax_u(sum_c x1[c,u] x2[c,w]).
+ * 1 <= K <= 16, 1 <= mid <= 64, V <= 32; anything else (and a null pointer) is DSGCN_EINVAL before any launch.
+ *   bwd: no workspace; outputs dproj (every element written, padding columns zero) and ppar (n, pstride >=
+ *        dsgcn_dynplain_partial_stride): per-sample partials [sum_c dAhat (K*V*V) | dalpha (K) | dbeta (K)], summed by
+ *        dsgcn_colsum.  One launch each way, workgroup = (sample, subset); no float atomics. */
+int dsgcn_dynplain_partial_stride(int K, int V);
+int dsgcn_dynplain_fwd(const float* proj, const float* A, const float* alpha, const float* beta, float* ahat, int n, int K,
+                       int mid, int V, int ld, void* stream);
+int dsgcn_dynplain_bwd(const float* proj, const float* alpha, const float* beta, const float* dahat, float* dproj,
+                       float* ppar, int pstride, int n, int K, int mid, int V, int ld, void* stream);
+
 /* Block output (materialise once): out = relu?(x1*s1+h1 (+ x2*s2+h2 | + x2)), xbar = mean_t out (optional).
  * Replaces BN + residual add + ReLU of dgstgcn.py:63-65 / tcn.py:427 and x.mean(-2) of gcn.py:2246.
  * relu: bit 0 = the outer ReLU, bit 1 = a ReLU on the first term before the add (CTR-GCN: msg3d_utils.py:139-141
