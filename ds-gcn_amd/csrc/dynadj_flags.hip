@@ -13,16 +13,16 @@
 //   F & 16 (SW)    per-subset alpha / beta (alpha[k]); absent: alpha[0] / beta[0] scale every subset.
 //   Ahat[k,c,u,w] = A[k,u,w] + alpha tanh(D[k,c,u,w]) + beta softmax_u(G'[k])[u,w]
 //
-// Forward: workgroup = (sample, subset, channel window); it recomputes the Gram(s) + softmax and writes the window's rows.
-// Backward: workgroup = (sample, subset), or (sample) over the three subsets in order under ADA (the mix couples them).
-// Parameter partials per sample [sum_c dAhat (3*V*V) | dalpha_k (3) | dbeta_k (3) | dbe (E*mid, EDGE) | dWa (9E) | dba (3E)
-// (ADA)], summed over samples by dsgcn_colsum: no float atomics, one writer per output element, every sum in a fixed order.
-#include "common.h"
+// Forward: workgroup = (sample, subset, channel window).  Backward: workgroup = (sample, subset), or (sample) over the three
+// subsets in order under ADA (the mix couples them).  Partials per sample [sum_c dAhat (3*V*V) | dalpha_k (3) | dbeta_k (3) |
+// dbe (E*mid, EDGE) | dWa (9E) | dba (3E) (ADA)], summed by dsgcn_colsum.  The Gram, the softmax and the backward passes are
+// dynadj_common.h's; this file has the row layouts, the class mix, the fp64 row / column sums of dD and CH = 8 / 4.
+#include "dynadj_common.h"
 
 namespace {
 
 constexpr int KSUB = 3;
-constexpr int LDT = 32;          // joint stride of the pq rows
+constexpr int LDT = KB_LDT;
 constexpr int NTF = 256;         // forward workgroup
 constexpr int NTB = 1024;        // backward workgroup
 constexpr int NWB = NTB / DSGCN_WAVE;
@@ -56,36 +56,6 @@ __device__ __forceinline__ void flag_load(const FlagDims& d, int k, int nt, cons
     X1[o] = pn[(size_t)r1 * d.ld + v];
     X2[o] = pn[(size_t)r2 * d.ld + v];
   }
-}
-
-// G[u,w] = sum_c X1[c,u] X2[c,w] (fixed c order)
-__device__ __forceinline__ void flag_gram(int m, int V, int nt, const float* X1, const float* X2, float* G) {
-  for (int i = threadIdx.x; i < V * V; i += nt) {
-    const int u = i / V, w = i - u * V;
-    float g = 0.f;
-    for (int c = 0; c < m; ++c) g = fmaf(X1[c * V + u], X2[c * V + w], g);
-    G[i] = g;
-  }
-}
-
-// S <- softmax over u of each column w, in place
-__device__ __forceinline__ void flag_softmax(int V, int nt, float* S, float* cmx, float* cinv) {
-  const int tid = threadIdx.x;
-  if (tid < V) {
-    const int w = tid;
-    float mx = -INFINITY;
-    for (int u = 0; u < V; ++u) mx = fmaxf(mx, S[u * V + w]);
-    float ssum = 0.f;
-    for (int u = 0; u < V; ++u) ssum += expf(S[u * V + w] - mx);
-    cmx[w] = mx;
-    cinv[w] = 1.f / ssum;
-  }
-  __syncthreads();
-  for (int i = tid; i < V * V; i += nt) {
-    const int w = i % V;
-    S[i] = expf(S[i] - cmx[w]) * cinv[w];
-  }
-  __syncthreads();
 }
 
 __device__ __forceinline__ void flag_types(const FlagDims& d, bool want_et, bool want_nt, int nt,
@@ -124,8 +94,8 @@ __global__ __launch_bounds__(NTF) void k_dynflag_fwd(FlagDims d, const float* __
   if (VT) d.V = VT;
   const int m = d.mid, V = d.V, VV = V * V;
   const int n = blockIdx.x, k = blockIdx.y;
-  const int pc0 = (m * (int)blockIdx.z) / (int)gridDim.z;
-  const int pm = (m * ((int)blockIdx.z + 1)) / (int)gridDim.z - pc0;
+  int pc0, pm;
+  kb_window(m, (int)blockIdx.z, (int)gridDim.z, pc0, pm);
   const int R = SEM == 0 ? 2 * KSUB * m : 4 * m + m * d.P;
   const float* pn = proj + (size_t)n * R * d.ld;
   flag_types(d, EDGE || ADA, SEM == 2, NTF, edge_type, node_type, ET, NT);
@@ -134,7 +104,7 @@ __global__ __launch_bounds__(NTF) void k_dynflag_fwd(FlagDims d, const float* __
     for (int kk = 0; kk < KSUB; ++kk) {
       flag_load<SEM>(d, kk, NTF, pn, NT, X1, X2);
       __syncthreads();
-      flag_gram(m, V, NTF, X1, X2, GR + kk * VV);
+      kb_gram(m, V, NTF, X1, X2, GR + kk * VV);
       __syncthreads();
     }
     flag_load<SEM>(d, k, NTF, pn, NT, X1, X2);
@@ -147,20 +117,14 @@ __global__ __launch_bounds__(NTF) void k_dynflag_fwd(FlagDims d, const float* __
   } else {
     flag_load<SEM>(d, k, NTF, pn, NT, X1, X2);
     __syncthreads();
-    flag_gram(m, V, NTF, X1, X2, S);
+    kb_gram(m, V, NTF, X1, X2, S);
   }
   __syncthreads();
-  flag_softmax(V, NTF, S, cmx, cinv);
+  kb_col_softmax(V, NTF, S, cmx, cinv, 1);
   const float* pq_n = EDGE ? pq + (size_t)n * d.E * m * 2 * LDT : nullptr;
-  float* out = ahat + ((size_t)n * KSUB + k) * m * VV;
-  const float al = alpha[SW ? k : 0], bt = beta[SW ? k : 0];
-  const float* Ak = A + k * VV;
-  for (int i = threadIdx.x; i < pm * VV; i += NTF) {
-    const int cl = i / VV, r = i - cl * VV;
-    const int u = r / V, w = r - u * V, c = pc0 + cl;
-    const float dk = flag_D<EDGE>(m, V, k, c, u, w, EDGE ? (int)ET[r] : 0, X1, X2, pq_n, be);
-    out[(size_t)c * VV + r] = Ak[r] + al * tanhf(dk) + bt * S[r];
-  }
+  kb_ahat_window(V, NTF, pc0, pm, EDGE, ET, A + k * VV, alpha[SW ? k : 0], beta[SW ? k : 0], S,
+                 ahat + ((size_t)n * KSUB + k) * m * VV,
+                 [&](int c, int u, int w, int e) { return flag_D<EDGE>(m, V, k, c, u, w, e, X1, X2, pq_n, be); });
 }
 
 // grid (n, 3), or (n, 1) under ADA
@@ -183,7 +147,7 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
   __shared__ float bins[EDGE ? MAXE * CH * MAXV : 1];
   __shared__ float red[2][NWB];
   if (VT) d.V = VT;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int m = d.mid, V = d.V, VV = V * V, E = d.E, P = d.P, ld = d.ld;
   const int n = blockIdx.x;
   const int R = SEM == 0 ? 2 * KSUB * m : 4 * m + m * P;
@@ -200,7 +164,7 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
     for (int kk = 0; kk < KSUB; ++kk) {
       flag_load<SEM>(d, kk, NTB, pn, NT, X1, X2);
       __syncthreads();
-      flag_gram(m, V, NTB, X1, X2, GR + kk * PL);
+      kb_gram(m, V, NTB, X1, X2, GR + kk * PL);
       __syncthreads();
     }
 #pragma unroll 1
@@ -212,7 +176,7 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
         S[kq * PL + i] = g;
       }
       __syncthreads();
-      flag_softmax(V, NTB, S + kq * PL, cmx, cinv);
+      kb_col_softmax(V, NTB, S + kq * PL, cmx, cinv, 1);
     }
   }
 
@@ -225,45 +189,20 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
     flag_load<SEM>(d, k, NTB, pn, NT, X1, X2);
     __syncthreads();
     if (!ADA) {
-      flag_gram(m, V, NTB, X1, X2, Sk);
+      kb_gram(m, V, NTB, X1, X2, Sk);
       __syncthreads();
-      flag_softmax(V, NTB, Sk, cmx, cinv);
+      kb_col_softmax(V, NTB, Sk, cmx, cinv, 1);
     }
     const float* g_k = dahat + ((size_t)n * KSUB + k) * m * VV;
     float* dd_k = dd + ((size_t)n * KSUB + k) * m * VV;
     const float al = alpha[SW ? k : 0], bk = beta[SW ? k : 0];
     float pal = 0.f, pbe = 0.f;
-    for (int r = tid; r < VV; r += NTB) {
-      const int u = r / V, w = r - u * V, e = EDGE ? (int)ET[r] : 0;
-      float sc = 0.f, pa = 0.f;
-      for (int c = 0; c < m; ++c) {
-        const float gv = g_k[(size_t)c * VV + r];
-        const float th = tanhf(flag_D<EDGE>(m, V, k, c, u, w, e, X1, X2, pq_n, be));
-        sc += gv;
-        pa = fmaf(th, gv, pa);
-        dd_k[(size_t)c * VV + r] = al * (1.f - th * th) * gv;
-      }
-      SCk[r] = sc;
-      par[k * VV + r] = sc;
-      pbe = fmaf(Sk[r], sc, pbe);
-      pal += pa;
-    }
-    {
-      const float ra = wave_sum(pal), rb = wave_sum(pbe);
-      if (lane == 0) { red[0][wave] = ra; red[1][wave] = rb; }
-    }
+    kb_pass1(m, V, NTB, EDGE, ET, g_k, dd_k, al, Sk, SCk, par, k * VV,
+             [&](int c, int u, int w, int e) { return flag_D<EDGE>(m, V, k, c, u, w, e, X1, X2, pq_n, be); }, pal, pbe);
+    kb_reduce2_put(pal, pbe, red);
     __syncthreads();                 // (also: the dd_k writes of this workgroup are visible to it below)
-    if (tid < 2) {
-      float r = 0.f;
-      for (int i = 0; i < NWB; ++i) r += red[tid][i];
-      par[KSUB * VV + tid * KSUB + k] = r;
-    }
-    if (tid >= 64 && tid < 64 + V) {
-      const int w = tid - 64;
-      float dot = 0.f;
-      for (int u = 0; u < V; ++u) dot = fmaf(Sk[u * V + w], bk * SCk[u * V + w], dot);
-      for (int u = 0; u < V; ++u) SCk[u * V + w] = Sk[u * V + w] * (bk * SCk[u * V + w] - dot);
-    }
+    kb_reduce2_get(red, par, KSUB * VV + k, KSUB);
+    if (tid >= 64 && tid < 64 + V) kb_softmax_bwd(V, tid - 64, Sk, SCk, bk);
     __syncthreads();
   }
 
@@ -316,15 +255,9 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
         // row / column sums of dD in fp64: on the semantic subset both land on the same conv1_se row, where their sums
         // over the joints cancel exactly in exact arithmetic (a shift of xs leaves xs[u] - xs[w] alone) — the bias
         // gradient is what is left of the Gram term, so the difference is formed before it is rounded to fp32
-        double rs = 0., cs = 0.;
-        if (direct) {
-          const float* dk = dd_k + (size_t)c * VV;
-          for (int w = 0; w < V; ++w) rs += (double)dk[j * V + w];
-          for (int u = 0; u < V; ++u) cs += (double)dk[u * V + j];
-        }
-        float g1 = 0.f, g2 = 0.f;
-        for (int w = 0; w < V; ++w) g1 = fmaf(dG[j * V + w], X2[c * V + w], g1);
-        for (int u = 0; u < V; ++u) g2 = fmaf(dG[u * V + j], X1[c * V + u], g2);
+        double rs, cs;
+        float g1, g2;
+        kb_gram_bwd(V, c, j, direct, dd_k, dG, X1, X2, rs, cs, g1, g2);
         v1 = (float)rs + g1;
         v2 = g2 - (float)cs;
         v12 = (float)(rs - cs) + (g1 + g2);
@@ -356,43 +289,9 @@ __global__ __launch_bounds__(NTB) void k_dynflag_bwd(FlagDims d, const float* __
         for (int p = 0; p < PP; ++p) dpn[(size_t)(4 * m + c * PP + p) * ld + j] = 0.f;
       }
     }
-    if (EDGE && k == 1) {
-      // class-masked row (slot 0) / column (slot 1) sums of dD, CH channels per round; thread (cl, x) owns bins[*][cl][x]
-      float* dpq_n = dpq + (size_t)n * E * m * 2 * LDT;
-      float* pbe_ = par + KSUB * VV + 2 * KSUB;
-      for (int c0 = 0; c0 < m; c0 += CH) {
-        for (int slot = 0; slot < 2; ++slot) {
-          if (tid < CH * V) {
-            const int cl = tid / V, x = tid - cl * V, c = c0 + cl;
-            for (int e = 0; e < E; ++e) bins[(e * CH + cl) * V + x] = 0.f;
-            if (c < m) {
-              const float* dk = dd_k + (size_t)c * VV;
-              if (slot == 0) {
-                for (int y = 0; y < V; ++y) bins[(ET[x * V + y] * CH + cl) * V + x] += dk[x * V + y];
-              } else {
-                for (int y = 0; y < V; ++y) bins[(ET[y * V + x] * CH + cl) * V + x] -= dk[y * V + x];
-              }
-            }
-          }
-          __syncthreads();
-          for (int o = tid; o < E * CH * LDT; o += NTB) {
-            const int x = o & (LDT - 1), q = o >> 5, e = q / CH, cl = q - e * CH, c = c0 + cl;
-            if (c < m) dpq_n[((size_t)e * m + c) * 2 * LDT + slot * LDT + x] = x < V ? bins[(e * CH + cl) * V + x] : 0.f;
-          }
-          if (slot == 0) {           // dbe[e,c] = sum_u dP_e[c,u]
-            for (int o = tid; o < E * CH; o += NTB) {
-              const int e = o / CH, cl = o - e * CH, c = c0 + cl;
-              if (c < m) {
-                float acc = 0.f;
-                for (int x = 0; x < V; ++x) acc += bins[(e * CH + cl) * V + x];
-                pbe_[e * m + c] = acc;
-              }
-            }
-          }
-          __syncthreads();
-        }
-      }
-    }
+    if (EDGE && k == 1)
+      kb_edge_bins<CH>(m, V, E, NTB, ET, dd_k, bins, dpq + (size_t)n * E * m * 2 * LDT, par + KSUB * VV + 2 * KSUB,
+                       0);
   }
 }
 

@@ -16,10 +16,9 @@
 // floats; it is walked in 16-byte slots laid on the 16-byte grid of the address space, so the slots that lie wholly inside
 // the run are one 16-byte store / load each whatever the run's own alignment (mid * V * V % 4 != 0 only makes the first
 // and last slot partial: those go element by element).
-// Parameter partials per sample [sum_c dAhat (K*V*V) | dalpha (K) | dbeta (K)], summed over samples by dsgcn_colsum: no
-// float atomics, every output element has one writer, every sum runs in a fixed order.
-// Bound: tanh per element (VALU) and the HBM write of Ahat forward / read of dAhat backward.
-#include "common.h"
+// Partials per sample [sum_c dAhat (K*V*V) | dalpha (K) | dbeta (K)], summed by dsgcn_colsum.  The Gram, the softmax, its
+// backward and the scalar reduce are dynadj_common.h's; the 16-byte-slot walk is this file's.
+#include "dynadj_common.h"
 
 namespace {
 
@@ -35,7 +34,7 @@ __host__ __device__ constexpr int up4(int x) { return (x + 3) & ~3; }
 // X1 / X2 of subset k (mid x V, X2 right behind X1) from proj, then S = softmax_u(sum_c X1[c,u] X2[c,w])
 __device__ __forceinline__ void plain_prepare(const PlainDims& d, int k, const float* __restrict__ proj_n, float* X1,
                                               float* S, float* cst) {
-  const int tid = threadIdx.x, m = d.mid, V = d.V, VV = V * V;
+  const int tid = threadIdx.x, m = d.mid, V = d.V;
   const float* X2 = X1 + m * V;
   for (int o = tid; o < 2 * m * V; o += NT) {
     const int second = o >= m * V, r = o - second * m * V;
@@ -43,28 +42,9 @@ __device__ __forceinline__ void plain_prepare(const PlainDims& d, int k, const f
     X1[o] = proj_n[((size_t)(second * d.K + k) * m + c) * d.ld + v];
   }
   __syncthreads();
-  for (int i = tid; i < VV; i += NT) {
-    const int u = i / V, w = i - u * V;
-    float g = 0.f;
-    for (int c = 0; c < m; ++c) g = fmaf(X1[c * V + u], X2[c * V + w], g);
-    S[i] = g;
-  }
+  kb_gram(m, V, NT, X1, X2, S);
   __syncthreads();
-  if (tid < V) {
-    const int w = tid;
-    float mx = -INFINITY;
-    for (int u = 0; u < V; ++u) mx = fmaxf(mx, S[u * V + w]);
-    float ssum = 0.f;
-    for (int u = 0; u < V; ++u) ssum += expf(S[u * V + w] - mx);
-    cst[w * 2 + 0] = mx;
-    cst[w * 2 + 1] = 1.f / ssum;
-  }
-  __syncthreads();
-  for (int i = tid; i < VV; i += NT) {
-    const int w = i % V;
-    S[i] = expf(S[i] - cst[w * 2]) * cst[w * 2 + 1];
-  }
-  __syncthreads();
+  kb_col_softmax(V, NT, S, cst, cst + 1, 2);      // column w: max in cst[2w], 1 / sum in cst[2w + 1]
 }
 
 // (channel, u, w) of a float offset inside a run of (channels, V, V), and the step to the next float
@@ -93,8 +73,8 @@ __global__ __launch_bounds__(NT) void k_dynplain_fwd(PlainDims d, const float* _
   if (VT) d.V = VT;
   const int tid = threadIdx.x, m = d.mid, V = d.V, VV = V * V;
   const int b = blockIdx.x, n = b / d.K, k = b - n * d.K;
-  const int pc0 = (m * (int)blockIdx.y) / (int)gridDim.y;
-  const int pm = (m * ((int)blockIdx.y + 1)) / (int)gridDim.y - pc0;
+  int pc0, pm;
+  kb_window(m, (int)blockIdx.y, (int)gridDim.y, pc0, pm);
   float* X1 = lds;
   const float* X2 = X1 + m * V;
   float* S = lds + up4(2 * m * V);
@@ -149,7 +129,7 @@ __global__ __launch_bounds__(NT) void k_dynplain_bwd(PlainDims d, const float* _
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ float red[2][NW];
   if (VT) d.V = VT;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int m = d.mid, V = d.V, VV = V * V, K = d.K;
   const int b = blockIdx.x, n = b / K, k = b - n * K;
   float* X1 = lds;
@@ -247,13 +227,7 @@ __global__ __launch_bounds__(NT) void k_dynplain_bwd(PlainDims d, const float* _
     pbe = fmaf(S[r], sc, pbe);
   }
   __syncthreads();
-  // softmax backward per column w: SC <- dG = S * (beta*SC - sum_u S*beta*SC)
-  if (tid < V) {
-    const int w = tid;
-    float dot = 0.f;
-    for (int u = 0; u < V; ++u) dot = fmaf(S[u * V + w], bk * SC[u * V + w], dot);
-    for (int u = 0; u < V; ++u) SC[u * V + w] = S[u * V + w] * (bk * SC[u * V + w] - dot);
-  }
+  if (tid < V) kb_softmax_bwd(V, tid, S, SC, bk);
   __syncthreads();
   // this subset's dproj rows: Gram backward + the row / column sums of dD; thread = (x1 | x2, c, joint), padding zero
   {
@@ -276,17 +250,9 @@ __global__ __launch_bounds__(NT) void k_dynplain_bwd(PlainDims d, const float* _
       dp_n[((size_t)(second * K + k) * m + c) * ld + j] = val;
     }
   }
-  // block-reduce the two scalar partials (waves in order)
-  {
-    const float ra = wave_sum(pal), rb = wave_sum(pbe);
-    if (lane == 0) { red[0][wave] = ra; red[1][wave] = rb; }
-    __syncthreads();
-    if (tid < 2) {
-      float r = 0.f;
-      for (int i = 0; i < NW; ++i) r += red[tid][i];
-      par[K * VV + tid * K + k] = r;
-    }
-  }
+  kb_reduce2_put(pal, pbe, red);
+  __syncthreads();
+  kb_reduce2_get(red, par, K * VV + k, K);
 }
 
 bool dims_ok(int n, int K, int mid, int V, int ld) {
@@ -294,11 +260,6 @@ bool dims_ok(int n, int K, int mid, int V, int ld) {
 }
 
 }  // namespace
-
-#define PLAIN_DISPATCH(L) \
-  if (V == 25) L(25)      \
-  else if (V == 17) L(17) \
-  else L(0)
 
 extern "C" {
 
@@ -316,7 +277,7 @@ int dsgcn_dynplain_fwd(const float* proj, const float* A, const float* alpha, co
 #define PLAIN_FWD(VT)                                                                                                  \
   hipLaunchKernelGGL((k_dynplain_fwd<VT>), dim3(n * K, windows), dim3(NT), lds, (hipStream_t)stream, d, proj, A, alpha, \
                      beta, ahat);
-  PLAIN_DISPATCH(PLAIN_FWD)
+  KB_DISPATCH_V(PLAIN_FWD)
 #undef PLAIN_FWD
   DSGCN_LAUNCH_CHECK();
   return 0;
@@ -333,7 +294,7 @@ int dsgcn_dynplain_bwd(const float* proj, const float* alpha, const float* beta,
 #define PLAIN_BWD(VT)                                                                                                  \
   hipLaunchKernelGGL((k_dynplain_bwd<VT>), dim3(n * K), dim3(NT), lds, (hipStream_t)stream, d, proj, alpha, beta, dahat, \
                      dproj, ppar, pstride);
-  PLAIN_DISPATCH(PLAIN_BWD)
+  KB_DISPATCH_V(PLAIN_BWD)
 #undef PLAIN_BWD
   DSGCN_LAUNCH_CHECK();
   return 0;

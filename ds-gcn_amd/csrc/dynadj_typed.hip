@@ -11,19 +11,17 @@
 //                x1[k,c,u] - x2[k,c,w] without edge attention
 //   Ahat[k,c,u,w] = A[k,u,w] + alpha_k tanh(D) + beta_k softmax_u(sum_c x1[k,c,u] x2[k,c,w])
 //
-// Forward: workgroup = (sample, subset, channel window); it recomputes the subset's Gram + softmax (mid*V*V fmas) and
-// writes the window's Ahat rows.  Backward: workgroup = (sample, subset) over all channels (the softmax couples them):
-//   dD = alpha_k (1 - tanh^2) dAhat -> workspace dd (stays in L2);
-//   dP_e[c,u] = sum_{w: eps(u,w)=e} dD, dQ_e[c,w] = -sum_{u: eps(u,w)=e} dD (per-thread class bins in LDS) -> dpq, whose
-//   K-C backward gives We^T dP / We^T dQ and dWe; the direct path (no edge attention, or add_type) and the softmax-Gram
-//   backward -> dx12.  Parameter partials per sample [sum_c dAhat (K*V*V) | dalpha (K) | dbeta (K) | dbe (E*K*mid)], summed
-//   over samples by dsgcn_colsum: no float atomics, every output element has one writer, every sum runs in a fixed order.
-#include "common.h"
+// Forward: workgroup = (sample, subset, channel window).  Backward: workgroup = (sample, subset) over all channels; dD goes
+// to the workspace dd (stays in L2), the class bins give dpq (its K-C backward gives We^T dP / We^T dQ and dWe), the direct
+// path (no edge attention, or add_type) and the Gram backward give dx12.  Partials per sample [sum_c dAhat (K*V*V) |
+// dalpha (K) | dbeta (K) | dbe (E*K*mid)], summed by dsgcn_colsum.  The passes themselves are dynadj_common.h's; this file
+// has the node-typed select, D and CH = 8.
+#include "dynadj_common.h"
 
 namespace {
 
 constexpr int KSUB = 3;
-constexpr int LDT = 32;          // joint stride of the x12 / pq rows
+constexpr int LDT = KB_LDT;
 constexpr int NTF = 256;         // forward workgroup
 constexpr int NTB = 1024;        // backward workgroup: thread = joint pair (V*V <= 1024)
 constexpr int NWB = NTB / DSGCN_WAVE;
@@ -73,35 +71,15 @@ __global__ __launch_bounds__(256) void k_dyntyped_select_bwd(const float* __rest
 // X1 / X2 of subset k (mid x V, LDS) from x12, then S = softmax_u(sum_c X1[c,u] X2[c,w]) (fixed c order)
 __device__ __forceinline__ void typed_prepare(int m, int V, int nt, const float* __restrict__ xs, float* X1, float* X2,
                                               float* S, float* cmx, float* cinv) {
-  const int tid = threadIdx.x, VV = V * V;
-  for (int o = tid; o < m * V; o += nt) {
+  for (int o = threadIdx.x; o < m * V; o += nt) {
     const int c = o / V, v = o - c * V;
     X1[o] = xs[c * 2 * LDT + v];
     X2[o] = xs[c * 2 * LDT + LDT + v];
   }
   __syncthreads();
-  for (int i = tid; i < VV; i += nt) {
-    const int u = i / V, w = i - u * V;
-    float g = 0.f;
-    for (int c = 0; c < m; ++c) g = fmaf(X1[c * V + u], X2[c * V + w], g);
-    S[i] = g;
-  }
+  kb_gram(m, V, nt, X1, X2, S);
   __syncthreads();
-  if (tid < V) {
-    const int w = tid;
-    float mx = -INFINITY;
-    for (int u = 0; u < V; ++u) mx = fmaxf(mx, S[u * V + w]);
-    float ssum = 0.f;
-    for (int u = 0; u < V; ++u) ssum += expf(S[u * V + w] - mx);
-    cmx[w] = mx;
-    cinv[w] = 1.f / ssum;
-  }
-  __syncthreads();
-  for (int i = tid; i < VV; i += nt) {
-    const int w = i % V;
-    S[i] = expf(S[i] - cmx[w]) * cinv[w];
-  }
-  __syncthreads();
+  kb_col_softmax(V, nt, S, cmx, cinv, 1);
 }
 
 // D of (c, u, w) for subset k
@@ -128,21 +106,15 @@ __global__ __launch_bounds__(NTF) void k_dyntyped_fwd(TypDims d, const float* __
   if (VT) d.V = VT;
   const int m = d.mid, V = d.V, VV = V * V;
   const int n = blockIdx.x, k = blockIdx.y;
-  const int pc0 = (m * (int)blockIdx.z) / (int)gridDim.z;
-  const int pm = (m * ((int)blockIdx.z + 1)) / (int)gridDim.z - pc0;
+  int pc0, pm;
+  kb_window(m, (int)blockIdx.z, (int)gridDim.z, pc0, pm);
   if (d.flags & F_EDGE)
     for (int i = threadIdx.x; i < VV; i += NTF) ET[i] = edge_type[i];
   typed_prepare(m, V, NTF, x12 + ((size_t)n * KSUB + k) * m * 2 * LDT, X1, X2, S, cmx, cinv);
   const float* pq_n = (d.flags & F_EDGE) ? pq + (size_t)n * d.E * KSUB * m * 2 * LDT : nullptr;
-  float* out = ahat + ((size_t)n * KSUB + k) * m * VV;
-  const float al = alpha[k], bt = beta[k];
-  const float* Ak = A + k * VV;
-  for (int i = threadIdx.x; i < pm * VV; i += NTF) {
-    const int cl = i / VV, r = i - cl * VV;
-    const int u = r / V, w = r - u * V, c = pc0 + cl;
-    const float dk = typed_D(d, k, c, u, w, (d.flags & F_EDGE) ? ET[r] : 0, X1, X2, pq_n, be);
-    out[(size_t)c * VV + r] = Ak[r] + al * tanhf(dk) + bt * S[r];
-  }
+  kb_ahat_window(V, NTF, pc0, pm, d.flags & F_EDGE, ET, A + k * VV, alpha[k], beta[k], S,
+                 ahat + ((size_t)n * KSUB + k) * m * VV,
+                 [&](int c, int u, int w, int e) { return typed_D(d, k, c, u, w, e, X1, X2, pq_n, be); });
 }
 
 // grid (n, 3): workgroup = (sample, subset), all channels
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(NTB) void k_dyntyped_bwd(TypDims d, const float* __
   __shared__ float bins[MAXE * CH * MAXV];
   __shared__ float red[2][NWB];
   if (VT) d.V = VT;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int m = d.mid, V = d.V, VV = V * V, E = d.E;
   const bool edge = d.flags & F_EDGE, direct = !edge || (d.flags & F_ADD);
   const int n = blockIdx.x, k = blockIdx.y;
@@ -171,31 +143,11 @@ __global__ __launch_bounds__(NTB) void k_dyntyped_bwd(TypDims d, const float* __
   float* par = ppar + (size_t)n * pstride;
   const float al = alpha[k], bk = beta[k];
 
-  // pass 1: thread = (u, w), channels in order: dD -> workspace, sum_c dAhat, dalpha partial
   float pal = 0.f, pbe = 0.f;
-  for (int r = tid; r < VV; r += NTB) {
-    const int u = r / V, w = r - u * V, e = edge ? ET[r] : 0;
-    float sc = 0.f, pa = 0.f;
-    for (int c = 0; c < m; ++c) {
-      const float gv = g_k[(size_t)c * VV + r];
-      const float th = tanhf(typed_D(d, k, c, u, w, e, X1, X2, pq_n, be));
-      sc += gv;
-      pa = fmaf(th, gv, pa);
-      dd_k[(size_t)c * VV + r] = al * (1.f - th * th) * gv;
-    }
-    SC[r] = sc;
-    par[k * VV + r] = sc;
-    pbe = fmaf(S[r], sc, pbe);
-    pal += pa;
-  }
+  kb_pass1(m, V, NTB, edge, ET, g_k, dd_k, al, S, SC, par, k * VV,
+           [&](int c, int u, int w, int e) { return typed_D(d, k, c, u, w, e, X1, X2, pq_n, be); }, pal, pbe);
   __syncthreads();                 // (also: the dd_k writes of this workgroup are visible to it below)
-  // softmax backward per column w: SC <- dG = S * (beta*SC - sum_u S*beta*SC)
-  if (tid < V) {
-    const int w = tid;
-    float dot = 0.f;
-    for (int u = 0; u < V; ++u) dot = fmaf(S[u * V + w], bk * SC[u * V + w], dot);
-    for (int u = 0; u < V; ++u) SC[u * V + w] = S[u * V + w] * (bk * SC[u * V + w] - dot);
-  }
+  if (tid < V) kb_softmax_bwd(V, tid, S, SC, bk);
   __syncthreads();
   // dx12 of this subset: Gram backward (+ the direct row / column sums of dD); thread = (c, j), padding columns zero
   float* dxs = dx12 + ((size_t)n * KSUB + k) * m * 2 * LDT;
@@ -203,70 +155,20 @@ __global__ __launch_bounds__(NTB) void k_dyntyped_bwd(TypDims d, const float* __
     const int c = o / LDT, j = o - c * LDT;
     float v1 = 0.f, v2 = 0.f;
     if (j < V) {
-      float rs = 0.f, cs = 0.f;
-      if (direct) {
-        const float* dk = dd_k + (size_t)c * VV;
-        for (int w = 0; w < V; ++w) rs += dk[j * V + w];
-        for (int u = 0; u < V; ++u) cs += dk[u * V + j];
-      }
-      float g1 = 0.f, g2 = 0.f;
-      for (int w = 0; w < V; ++w) g1 = fmaf(SC[j * V + w], X2[c * V + w], g1);
-      for (int u = 0; u < V; ++u) g2 = fmaf(SC[u * V + j], X1[c * V + u], g2);
+      float rs, cs, g1, g2;
+      kb_gram_bwd(V, c, j, direct, dd_k, SC, X1, X2, rs, cs, g1, g2);
       v1 = rs + g1;
       v2 = g2 - cs;
     }
     dxs[c * 2 * LDT + j] = v1;
     dxs[c * 2 * LDT + LDT + j] = v2;
   }
-  if (edge) {
-    // class-masked row (slot 0) / column (slot 1) sums of dD, CH channels per round; thread (cl, x) owns bins[*][cl][x]
-    float* dpq_n = dpq + (size_t)n * E * KSUB * m * 2 * LDT;
-    float* pbe_ = par + KSUB * VV + 2 * KSUB;
-    for (int c0 = 0; c0 < m; c0 += CH) {
-      for (int slot = 0; slot < 2; ++slot) {
-        if (tid < CH * V) {
-          const int cl = tid / V, x = tid - cl * V, c = c0 + cl;
-          for (int e = 0; e < E; ++e) bins[(e * CH + cl) * V + x] = 0.f;
-          if (c < m) {
-            const float* dk = dd_k + (size_t)c * VV;
-            if (slot == 0) {
-              for (int y = 0; y < V; ++y) bins[(ET[x * V + y] * CH + cl) * V + x] += dk[x * V + y];
-            } else {
-              for (int y = 0; y < V; ++y) bins[(ET[y * V + x] * CH + cl) * V + x] -= dk[y * V + x];
-            }
-          }
-        }
-        __syncthreads();
-        for (int o = tid; o < E * CH * LDT; o += NTB) {
-          const int x = o & (LDT - 1), q = o >> 5, e = q / CH, cl = q - e * CH, c = c0 + cl;
-          if (c < m)
-            dpq_n[((size_t)(k * E + e) * m + c) * 2 * LDT + slot * LDT + x] = x < V ? bins[(e * CH + cl) * V + x] : 0.f;
-        }
-        if (slot == 0) {           // dbe[k,e,c] = sum_u dP_e[c,u]
-          for (int o = tid; o < E * CH; o += NTB) {
-            const int e = o / CH, cl = o - e * CH, c = c0 + cl;
-            if (c < m) {
-              float acc = 0.f;
-              for (int x = 0; x < V; ++x) acc += bins[(e * CH + cl) * V + x];
-              pbe_[(k * E + e) * m + c] = acc;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-  // block-reduce the two scalar partials (waves in order)
-  {
-    const float ra = wave_sum(pal), rb = wave_sum(pbe);
-    if (lane == 0) { red[0][wave] = ra; red[1][wave] = rb; }
-    __syncthreads();
-    if (tid < 2) {
-      float r = 0.f;
-      for (int i = 0; i < NWB; ++i) r += red[tid][i];
-      par[KSUB * VV + tid * KSUB + k] = r;
-    }
-  }
+  if (edge)
+    kb_edge_bins<CH>(m, V, E, NTB, ET, dd_k, bins, dpq + (size_t)n * E * KSUB * m * 2 * LDT, par + KSUB * VV + 2 * KSUB,
+                     k * E);
+  kb_reduce2_put(pal, pbe, red);
+  __syncthreads();
+  kb_reduce2_get(red, par, KSUB * VV + k, KSUB);
 }
 
 int grid_1d(size_t total) {
@@ -280,11 +182,6 @@ bool dims_ok(int n, int mid, int V, int E, int flags) {
 }
 
 }  // namespace
-
-#define TYP_DISPATCH(L) \
-  if (V == 25) L(25)    \
-  else if (V == 17) L(17) \
-  else L(0)
 
 extern "C" {
 
@@ -323,7 +220,7 @@ int dsgcn_dyntyped_fwd(const float* x12, const float* pq, const float* be, const
 #define TYP_FWD(VT)                                                                                                    \
   hipLaunchKernelGGL((k_dyntyped_fwd<VT>), dim3(n, KSUB, windows), dim3(NTF), 0, (hipStream_t)stream, d, x12, pq, be, \
                      A, alpha, beta, edge_type, ahat);
-  TYP_DISPATCH(TYP_FWD)
+  KB_DISPATCH_V(TYP_FWD)
 #undef TYP_FWD
   DSGCN_LAUNCH_CHECK();
   return 0;
@@ -340,7 +237,7 @@ int dsgcn_dyntyped_bwd(const float* x12, const float* pq, const float* be, const
 #define TYP_BWD(VT)                                                                                                    \
   hipLaunchKernelGGL((k_dyntyped_bwd<VT>), dim3(n, KSUB), dim3(NTB), 0, (hipStream_t)stream, d, x12, pq, be, alpha,   \
                      beta, edge_type, dahat, dd_ws, dx12, dpq, ppar, pstride);
-  TYP_DISPATCH(TYP_BWD)
+  KB_DISPATCH_V(TYP_BWD)
 #undef TYP_BWD
   DSGCN_LAUNCH_CHECK();
   return 0;

@@ -124,6 +124,28 @@ def _check_act(act):
         raise NotImplementedError(f'activation {typ} is not fused by the HIP kernels (ReLU only)')
 
 
+def _adjacency_unit_chain(unit, x, xbar, x_res, pad, batch_tail=False):
+    """The plain chain of a dynamic-adjacency unit: adjacency -> `pre` conv -> K-A -> `post` (-> `down`) as a Deferred.
+    xbar None (first block): the time mean of x, its joint rows padded to 32 under ``pad``.  x_res: an alias of x for the
+    residual operand (see kernels.tee3).  The order of the conv_bn calls fixes the BatchNorm job batching; batch_tail:
+    `post` and `down` are independent of one another, their two finalizes are one launch (kernels.bn_batch)."""
+    ops = kernels.ops()
+    x_res = x if x_res is None else x_res
+    if xbar is None:
+        xbar = ops.tmean(x, 32) if pad else ops.tmean(x)
+    ahat = unit.adjacency(xbar)
+    zp, _, ap = conv_bn(x, None, None, None, False, unit.pre[0], 1, False, unit.pre[1])
+    y = ops.aggregate(zp, ap, True, ahat)
+    if unit.down is None:
+        zo, _, ao = conv_bn(y, None, None, None, False, unit.post, 1, False, unit.bn)
+        return Deferred(zo, ao, x_res, None, True)
+    batch = getattr(ops, 'bn_batch', None) if batch_tail else None
+    with (batch() if batch is not None else contextlib.nullcontext()):
+        zo, _, ao = conv_bn(y, None, None, None, False, unit.post, 1, False, unit.bn)
+        zd, _, ad = conv_bn(x_res, None, None, None, False, unit.down[0], 1, False, unit.down[1])
+    return Deferred(zo, ao, zd, ad, True)
+
+
 class dgphgcn1(nn.Module):
     """Dynamic-semantic graph conv (reference: pyskl/models/gcns/utils/gcn.py:2074-2370).  The flag set every shipped
     DS-STGCN config selects (configs/dsstgcn/DSSTGCN_model.py:10-27: decompose + node/edge attention + subset-wise
@@ -256,16 +278,15 @@ class dgphgcn1(nn.Module):
     def forward_deferred(self, x, xbar=None, x_res=None):
         """x_res: an alias of x for the residual operand (lets the caller route the gradients of the two uses of x
         separately, see kernels.tee3)."""
+        if not self._shipped:                     # the ablation arms (V <= 32): K-B, then the `pre` conv (dghgcn's chain)
+            return _adjacency_unit_chain(self, x, xbar, x_res, pad=True, batch_tail=True)
         ops = kernels.ops()
         x_res = x if x_res is None else x_res
         if xbar is None:                          # first block: joint rows padded to 32 like fuse_out(want_tmean=32)'s
             xbar = ops.tmean(x, 32) if x.shape[-1] <= 32 else ops.tmean(x)
         fork = getattr(ops, 'side_branch', None)
         batch = getattr(ops, 'bn_batch', None)
-        if not self._shipped:                     # the ablation arms: K-B, then the `pre` conv (dghgcn's chain)
-            ahat = self.adjacency(xbar)
-            zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
-        elif batch is not None and not getattr(ops, 'OVERLAP', False):
+        if batch is not None and not getattr(ops, 'OVERLAP', False):
             # `pre` conv first, K-B behind it: K-B (and its projection conv) read nothing of the `pre` BatchNorm, so its
             # finalize rides in K-B's launch as extra workgroups (kernels.bn_batch) instead of a launch of its own between
             # the conv and K-A; the backward mirrors it (K-A's rows -> the coefficient job hosted by K-B's backward)
@@ -393,18 +414,7 @@ class dggcn(nn.Module):
         return torch.cat([first[:, :2 * m], second[:, :m]], 1)
 
     def forward_deferred(self, x, xbar=None, x_res=None):
-        ops = kernels.ops()
-        x_res = x if x_res is None else x_res
-        if xbar is None:
-            xbar = ops.tmean(x)
-        ahat = self.adjacency(xbar)
-        zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
-        y = ops.aggregate(zp, ap, True, ahat)
-        zo, _, ao = conv_bn(y, None, None, None, False, self.post, 1, False, self.bn)
-        if self.down is None:
-            return Deferred(zo, ao, x_res, None, True)
-        zd, _, ad = conv_bn(x_res, None, None, None, False, self.down[0], 1, False, self.down[1])
-        return Deferred(zo, ao, zd, ad, True)
+        return _adjacency_unit_chain(self, x, xbar, x_res, pad=False)
 
     def forward(self, x, A=None):
         out = self.forward_deferred(x).materialize()
@@ -498,18 +508,7 @@ class dghgcn(nn.Module):
 
     def forward_deferred(self, x, xbar=None, x_res=None):
         """xbar: the time mean of x, joint rows padded to 32 (the previous block's fuse_out); computed here otherwise."""
-        ops = kernels.ops()
-        x_res = x if x_res is None else x_res
-        if xbar is None:
-            xbar = ops.tmean(x, 32)
-        ahat = self.adjacency(xbar)
-        zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
-        y = ops.aggregate(zp, ap, True, ahat)
-        zo, _, ao = conv_bn(y, None, None, None, False, self.post, 1, False, self.bn)
-        if self.down is None:
-            return Deferred(zo, ao, x_res, None, True)
-        zd, _, ad = conv_bn(x_res, None, None, None, False, self.down[0], 1, False, self.down[1])
-        return Deferred(zo, ao, zd, ad, True)
+        return _adjacency_unit_chain(self, x, xbar, x_res, pad=True)
 
     def forward(self, x, A=None):
         out = self.forward_deferred(x).materialize()

@@ -841,22 +841,26 @@ class _DynAdj(torch.autograd.Function):
         return dproj, dA, dalpha, dbeta, dwe, dbe, None, None, None, None
 
 
-def dynadj(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, node_type, edge_type, single_use=True, host=None):
-    """Dynamic adjacency.  The three mean-pooled projections (conv1/conv2/conv1_se) are one K-C launch on xbar — viewed
-    as a (n, Ci, 1, 32) "clip" with the joint rows zero-padded to 32, so that forward, data gradient and weight gradient
-    all take the 16-byte-per-lane K-C kernels (an unpadded 25-joint row is odd-sized: it fell to the scalar-load kernels,
-    ~35 us per launch for 0.1 GFLOP) — and the rest is K-B reading / writing the padded rows."""
-    n, Ci, _ = xbar.shape
-    V = A.shape[-1]
-    w_all = cat_rows([w1, w2, wse])
-    b_all = cat_rows([b1, b2, bse])
-    # xbar arrives zero-padded to 32 joints from the previous block's fuse_out (want_tmean=32); the first block pads here
+def _kb_projections(xbar, V, weights, biases):
+    """The mean-pooled projections of a K-B front -> proj (n, rows, ld): one K-C launch over the stacked weights on xbar —
+    viewed as a (n, Ci, 1, 32) "clip" with the joint rows zero-padded to 32, so that forward, data gradient and weight
+    gradient all take the 16-byte-per-lane K-C kernels (an unpadded 25-joint row is odd-sized: it fell to the scalar-load
+    kernels, ~35 us per launch for 0.1 GFLOP).  xbar arrives padded from the previous block's fuse_out (want_tmean=32);
+    the first block pads here."""
+    w_all = cat_rows(weights)
+    b_all = cat_rows(biases)
     xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
     proj = pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
+    return proj.view(xbar.shape[0], w_all.shape[0], xpad.shape[-1])
+
+
+def dynadj(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, node_type, edge_type, single_use=True, host=None):
+    """Dynamic adjacency: the three projections (conv1 / conv2 / conv1_se, ``_kb_projections``), then K-B reading / writing
+    the padded rows."""
+    proj = _kb_projections(xbar, A.shape[-1], [w1, w2, wse], [b1, b2, bse])
     # single_use: every parameter passed here is used by this call only in the step (their gradient partials may then join
     # the end-of-backward sum, see param_colsum); dggcn feeds A to two calls and says so
-    return _DynAdj.apply(proj.view(n, w_all.shape[0], xpad.shape[-1]), A, alpha, beta, we, be, node_type, edge_type,
-                         bool(single_use), host)
+    return _DynAdj.apply(proj, A, alpha, beta, we, be, node_type, edge_type, bool(single_use), host)
 
 
 class _TypedSelect(torch.autograd.Function):
@@ -931,15 +935,9 @@ def dynadj_typed(xbar, A, alpha, beta, w1, b1, w2, b2, we, be, node_type, edge_t
     xbar padded to 32 joints (as in ``dynadj``), the node-typed select one small launch, the edge linear one K-C launch over
     [x1 | x2] viewed as a (n, 3*mid, 2, 32) clip, then the typed K-B.  The gradients of x12 from K-B and from the edge
     linear's K-C backward meet in autograd; the parameter partials are ordered column sums."""
-    n = xbar.shape[0]
     V = A.shape[-1]
-    R = w1.shape[0]
-    KM = R // P
-    w_all = cat_rows([w1, w2])
-    b_all = cat_rows([b1, b2])
-    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
-    proj = pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
-    x12 = _TypedSelect.apply(proj.view(n, 2 * R, xpad.shape[-1]), node_type, KM, P, V)
+    proj = _kb_projections(xbar, V, [w1, w2], [b1, b2])
+    x12 = _TypedSelect.apply(proj, node_type, w1.shape[0] // P, P, V)
     pq, flags = None, 0
     if we is not None:
         pq = pwconv(x12, None, None, None, False, we, None, 1, False)[0]

@@ -6,14 +6,7 @@ import torch
 
 from . import native
 from . import kernels as _K
-
-
-def _f32c(t):
-    return _K._f32c(t)
-
-
-def _ptr(t):
-    return _K._ptr(t)
+from .kernels import _f32c, _ptr
 
 
 class _FlagAdj(torch.autograd.Function):
@@ -85,17 +78,11 @@ def dynadj_flags(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, wa, ba,
     (``we`` (E*mid, mid), ``be``; None: no edge attention — no product, no partials) is one K-C launch over [x1_1 | x2_1]
     viewed as a (n, mid, 2, 32) clip; ``wa`` (3E, 3) / ``ba``: ada_linears, the class mix of the Gram (None: off).  The
     rest is one flag-specialised K-B launch each way; parameter partials are ordered column sums."""
-    n = xbar.shape[0]
-    V = A.shape[-1]
     sem = 0 if wse is None else (2 if P > 1 else 1)
     mid = w1.shape[0] // (3 if sem == 0 else 2)
     if we is not None and sem == 0:
         raise ValueError('dynadj_flags: the edge linear needs the decomposed layout')
-    w_all = _K.cat_rows([w1, w2] + ([wse] if sem else []))
-    b_all = _K.cat_rows([b1, b2] + ([bse] if sem else []))
-    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
-    proj = _K.pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
-    proj = proj.view(n, w_all.shape[0], xpad.shape[-1])
+    proj = _K._kb_projections(xbar, A.shape[-1], [w1, w2] + ([wse] if sem else []), [b1, b2] + ([bse] if sem else []))
     pq = None
     flags = sem | (16 if subset_wise else 0)
     if we is not None:

@@ -6,6 +6,7 @@ import torch
 
 from . import native
 from . import kernels as _K
+from .kernels import _f32c, _ptr
 
 MAX_SUBSETS, MAX_MID, MAX_JOINTS = 16, 64, 32      # csrc/dynadj_plain.hip: MAXK, MAXM, MAXV
 
@@ -27,13 +28,13 @@ class _PlainAdj(torch.autograd.Function):
     @staticmethod
     def forward(ctx, proj, A, alpha, beta, defer_ok):
         _K._require_cuda(proj, A)
-        proj, A, alpha, beta = [_K._f32c(t) for t in (proj, A, alpha, beta)]
+        proj, A, alpha, beta = [_f32c(t) for t in (proj, A, alpha, beta)]
         n, R, ld = proj.shape
         K, V = A.shape[0], A.shape[-1]
         mid = R // (2 * K)
         assert R == 2 * K * mid and alpha.numel() == K and beta.numel() == K, (R, K, alpha.shape, beta.shape)
         ahat = torch.empty((n, K * mid, V, V), device=proj.device, dtype=torch.float32)
-        rc = native.lib().dsgcn_dynplain_fwd(_K._ptr(proj), _K._ptr(A), _K._ptr(alpha), _K._ptr(beta), _K._ptr(ahat), n, K,
+        rc = native.lib().dsgcn_dynplain_fwd(_ptr(proj), _ptr(A), _ptr(alpha), _ptr(beta), _ptr(ahat), n, K,
                                              mid, V, ld, _K._stream())
         native.check(rc, 'dsgcn_dynplain_fwd')
         ctx.save_for_backward(proj, alpha, beta)
@@ -45,13 +46,13 @@ class _PlainAdj(torch.autograd.Function):
     def backward(ctx, dahat):
         proj, alpha, beta = ctx.saved_tensors
         n, K, mid, V, ld = ctx.dims
-        dahat = _K._f32c(dahat)
+        dahat = _f32c(dahat)
         lib = native.lib()
         dproj = torch.empty_like(proj)
         pstride = lib.dsgcn_dynplain_partial_stride(K, V)
         ppar = torch.empty((n, pstride), device=proj.device, dtype=torch.float32)      # per-sample parameter partials
-        rc = lib.dsgcn_dynplain_bwd(_K._ptr(proj), _K._ptr(alpha), _K._ptr(beta), _K._ptr(dahat), _K._ptr(dproj),
-                                    _K._ptr(ppar), pstride, n, K, mid, V, ld, _K._stream())
+        rc = lib.dsgcn_dynplain_bwd(_ptr(proj), _ptr(alpha), _ptr(beta), _ptr(dahat), _ptr(dproj),
+                                    _ptr(ppar), pstride, n, K, mid, V, ld, _K._stream())
         native.check(rc, 'dsgcn_dynplain_bwd')
         red = _K.param_colsum(ppar, bool(ctx.defer_ok))                                # ordered sum over samples: deterministic
         o = K * V * V
@@ -63,15 +64,11 @@ def dynadj_plain(xbar, A, alpha, beta, w1, b1, w2, b2, single_use=True):
     conv1 / conv2 (``w1`` / ``w2`` (K*mid, Ci)) are one K-C launch on xbar padded to 32 joints (as in ``dynadj``); the rest
     is one plain K-B launch each way.  ``alpha`` / ``beta`` hold K values (a unit without subset_wise passes
     ``alpha[0].expand(K)``: autograd adds the K sums).  Parameter partials are ordered column sums."""
-    n = xbar.shape[0]
     K, V = A.shape[0], A.shape[-1]
     mid = w1.shape[0] // K
     if w1.shape[0] != K * mid or w2.shape[0] != K * mid:
         raise ValueError(f'dynadj_plain: {w1.shape[0]} / {w2.shape[0]} projection rows for {K} subsets')
     check_range('dynadj_plain', K, mid, V)
-    w_all = _K.cat_rows([w1, w2])
-    b_all = _K.cat_rows([b1, b2])
-    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
-    proj = _K.pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
+    proj = _K._kb_projections(xbar, V, [w1, w2], [b1, b2])
     defer_ok = bool(single_use) and _K._leafish(A, alpha, beta)
-    return _PlainAdj.apply(proj.view(n, w_all.shape[0], xpad.shape[-1]), A, alpha, beta, defer_ok)
+    return _PlainAdj.apply(proj, A, alpha, beta, defer_ok)

@@ -118,6 +118,48 @@ def test_typed_kb_full_size_vs_fp64(case, flags):
     KG.check_typed_kb(case, flags)
 
 
+def _small_graph(V, P, E, seed):
+    """A (3, V, V), node_type (V), edge_type (V*V) of a graph that is not NTU's."""
+    gen = torch.Generator().manual_seed(seed)
+    A = torch.randn(3, V, V, generator=gen) * 0.1
+    return A, (torch.arange(V) % P).to(torch.int32), torch.randint(E, (V * V,), generator=gen).to(torch.int32)
+
+
+# (n, Ci, mid, V, P, E): V = 17 is the second V-specialised instantiation; V = 32 fills the 1024-thread pair grid and the
+# LDS maxima; V = 7 with mid = 11 is the generic one with a partial last round of the class bins (mid % 8 != 0)
+SMALL = [(2, 8, 5, 17, 3, 4), (3, 16, 1, 32, 1, 16), (2, 8, 11, 7, 2, 3)]
+
+
+@pytest.mark.parametrize('add_type', [False, True], ids=['node_edge', 'add_type'])
+@pytest.mark.parametrize('shape', SMALL)
+def test_typed_kb_small_shapes_vs_fp64(shape, add_type):
+    """``kernels.dynadj_typed`` with hand-made weights at joint counts other than 25: Ahat (1e-5), the input gradient
+    and every parameter gradient (1e-4) against the fp64 restatement, the bounds of the full-size test."""
+    n, ci, mid, V, P, E = shape
+    A, nt, et = _small_graph(V, P, E, 5)
+    gen = torch.Generator().manual_seed(11)
+    r = lambda *sh, scale=1.0: (torch.randn(*sh, generator=gen) * scale).cuda().requires_grad_()
+    KM = 3 * mid
+    p = dict(A=A.cuda().requires_grad_(), alpha=r(3, scale=.5), beta=r(3, scale=.5), w1=r(KM * P, ci, scale=ci ** -.5),
+             b1=r(KM * P, scale=.1), w2=r(KM * P, ci, scale=ci ** -.5), b2=r(KM * P, scale=.1),
+             we=r(E * KM, KM, scale=KM ** -.5), be=r(E * KM, scale=.1))
+    xbar = r(n, ci, V)
+    dah = torch.randn(n, KM, V, V, generator=gen).cuda()
+    ahat = D.kernels.dynadj_typed(xbar, p['A'], p['alpha'], p['beta'], p['w1'], p['b1'], p['w2'], p['b2'], p['we'],
+                                  p['be'], nt.cuda(), et.cuda(), P, add_type)
+    (ahat * dah).sum().backward()
+    p64 = {k: v.detach().double().requires_grad_() for k, v in p.items()}
+    x64 = xbar.detach().double().requires_grad_()
+    want = F.adjacency(x64, p64['A'], p64['alpha'], p64['beta'], p64['w1'], p64['b1'], p64['w2'], p64['b2'], p64['we'],
+                       p64['be'], nt, et, P, add_type, True)
+    (want * dah.double()).sum().backward()
+    errs = dict(ahat=rel(ahat.detach().cpu(), want.detach().cpu()), xbar=rel(xbar.grad.cpu(), x64.grad.cpu()),
+                **{k: rel(p[k].grad.cpu(), p64[k].grad.cpu()) for k in p})
+    assert errs['ahat'] < 1e-5, errs['ahat']
+    del errs['ahat']
+    assert all(e < 1e-4 for e in errs.values()), errs
+
+
 DGH_CFG = dict(
     type='RecognizerGCN',
     backbone=dict(

@@ -172,6 +172,55 @@ def test_flag_kb_full_size_vs_fp64(case, word):
         assert e < 1e-4, (k, e)
 
 
+# (n, Ci, mid, V, P, E, columns of xbar): V = 17 / 32 / 11 take the generic-V instantiations (32: the full pair grid and the
+# LDS maxima), mid = 5 / 3 / 9 leave a partial last round of the class bins (8 channels, 4 under ADA); 40 columns: ld > 32
+SMALL = [(2, 8, 5, 17, 3, 4, 17), (2, 8, 3, 32, 16, 16, 32), (3, 8, 9, 11, 2, 3, 11), (2, 8, 5, 17, 3, 4, 40)]
+
+
+@pytest.mark.parametrize('word', [6, 14, 17])
+@pytest.mark.parametrize('shape', SMALL)
+def test_flag_kb_small_shapes_vs_fp64(shape, word):
+    """``kernels.dynadj_flags`` with hand-made weights on a graph that is not NTU's: Ahat (1e-5), the input gradient and
+    every parameter gradient (1e-4) against the fp64 restatement, the bounds of the full-size test.  Words without SEM 2
+    run untyped (P = 1)."""
+    n, ci, mid, V, P, E, cols = shape
+    kw = _word_flags(word)
+    P = P if kw['node_attention'] else 1
+    gen = torch.Generator().manual_seed(5)
+    A = torch.randn(3, V, V, generator=gen) * 0.1
+    nt = (torch.arange(V) % P).to(torch.int32)
+    et = torch.randint(E, (V, V), generator=gen).to(torch.int32)
+    r = lambda *sh, scale=1.0: (torch.randn(*sh, generator=gen) * scale).cuda().requires_grad_()
+    p = {'A': A.cuda().requires_grad_(), 'alpha': r(3, scale=.5), 'beta': r(3, scale=.5),
+         'conv1.weight': r(2 * mid, ci, scale=ci ** -.5), 'conv1.bias': r(2 * mid, scale=.1),
+         'conv2.weight': r(2 * mid, ci, scale=ci ** -.5), 'conv2.bias': r(2 * mid, scale=.1),
+         'conv1_se.weight': r(mid * P, ci, scale=ci ** -.5), 'conv1_se.bias': r(mid * P, scale=.1)}
+    if kw['edge_attention']:
+        p.update({'edge_linears.weight': r(E * mid, mid, scale=mid ** -.5), 'edge_linears.bias': r(E * mid, scale=.1)})
+    if kw['ada_attention']:
+        p.update({'ada_linears.weight': r(3 * E, 3, scale=3 ** -.5), 'ada_linears.bias': r(3 * E, scale=.1)})
+    xbar = r(n, ci, V)
+    dah = torch.randn(n, 3 * mid, V, V, generator=gen).cuda()
+    ahat = D.kernels.dynadj_flags(
+        torch.nn.functional.pad(xbar, (0, cols - V)), p['A'], p['alpha'], p['beta'], p['conv1.weight'], p['conv1.bias'],
+        p['conv2.weight'], p['conv2.bias'], p['conv1_se.weight'], p['conv1_se.bias'], p.get('edge_linears.weight'),
+        p.get('edge_linears.bias'), p.get('ada_linears.weight'), p.get('ada_linears.bias'), nt.cuda(), et.reshape(-1).cuda(),
+        P, E, kw['subset_wise'])
+    (ahat * dah).sum().backward()
+    p64 = {k: v.detach().double().requires_grad_() for k, v in p.items()}
+    x64 = xbar.detach().double().requires_grad_()
+    want = F.adjacency(x64, p64, nt, et, F.effective_flags(num_types=P, edge_num=E, **kw))
+    (want * dah.double()).sum().backward()
+    errs = dict(ahat=rel(ahat.detach().cpu(), want.detach().cpu()), xbar=rel(xbar.grad.cpu(), x64.grad.cpu()))
+    for k in p:
+        if not kw['subset_wise'] and k in ('alpha', 'beta'):
+            assert float(p[k].grad[1:].abs().max()) == 0.0
+        errs[k] = rel(p[k].grad.cpu(), p64[k].grad.cpu())
+    assert errs['ahat'] < 1e-5, errs['ahat']
+    del errs['ahat']
+    assert all(e < 1e-4 for e in errs.values()), errs
+
+
 WATCHED = ('dsgcn_dynadj_fwd_jobs', 'dsgcn_dynadj_bwd_jobs', 'dsgcn_dynadj_fwd', 'dsgcn_dynadj_bwd', 'dsgcn_dynflag_fwd',
            'dsgcn_dynflag_bwd', 'dsgcn_dyntyped_fwd', 'dsgcn_dyntyped_bwd')
 
