@@ -20,10 +20,12 @@ resident in HBM, host decisions, one launch per batch — or from any map-style 
 every ``evaluation.interval`` epochs the val split goes through ``forward_test`` rank-sharded in dataset order, the parts
 are gathered (``gather_results``), rank 0 computes ``evaluation.metrics`` (top-k / mean-class accuracy) and keeps
 ``best_<key>_epoch_<n>.pth`` (``save_best='auto'``: the first metric returned).  ``lr_config`` policies: ``CosineAnnealing``
-by iteration (the DS-GCN configs), ``step`` by epoch (configs/stgcn/stgcn_vanilla_ntu60_xsub_3dkp/j.py:35), ``fixed``.
+by iteration (the DS-GCN configs), ``step`` by epoch (configs/stgcn/stgcn_vanilla_ntu60_xsub_3dkp/j.py:35), ``fixed``; each
+with mmcv's ``warmup`` ('constant' / 'linear' / 'exp', ``warmup_iters``, ``warmup_ratio``, ``warmup_by_epoch``).
+``optimizer_config.grad_clip=dict(max_norm=..., norm_type=2 | inf)`` (configs/_init_/lr_schedual.py:24) clips the averaged
+gradient by its total norm inside the update's hipGraph; ``grad_norm`` (before clipping) joins the log scalars.
 
-Not reproduced: TensorBoard logging, multi-optimizer configs, gradient clipping (the shipped configs set
-``grad_clip=None``, configs/_init_/lr_schedual.py:12).
+Not reproduced: TensorBoard logging, multi-optimizer configs.
 """
 import math
 import os
@@ -38,7 +40,7 @@ from .checkpoint import find_resume, load_checkpoint, resume, save_checkpoint
 from .engine import TrainEngine
 from .evaluation import mean_class_accuracy, top_k_accuracy
 from .recognizers import gather_results, reduce_log_vars
-from .train import cosine_lr, step_lr
+from .train import cosine_lr, step_lr, warmup_lr
 
 
 def _rank_world():
@@ -142,8 +144,16 @@ class EpochRunner:
             raise NotImplementedError('CosineAnnealing by_epoch=True is not used by the skeleton configs')
         if lr_cfg['policy'] in ('step', 'Step') and not lr_cfg.get('by_epoch', True):
             raise NotImplementedError('step policy by_epoch=False is not used by the skeleton configs')
-        if lr_cfg.get('warmup'):
-            raise NotImplementedError('lr warm-up is not used by the skeleton configs')
+        # mmcv LrUpdaterHook: warmup None | 'constant' | 'linear' | 'exp' over the first warmup_iters iterations
+        # (warmup_by_epoch: warmup_iters counts epochs and is converted below, once iters_per_epoch is known)
+        self.warmup = lr_cfg.get('warmup')
+        if self.warmup is not None:
+            if self.warmup not in ('constant', 'linear', 'exp'):
+                raise ValueError(f'"{self.warmup}" is not a supported type for warming up, valid types are "constant", '
+                                 '"linear" and "exp"')
+            self.warmup_ratio = float(lr_cfg.get('warmup_ratio', 0.1))
+            if int(lr_cfg.get('warmup_iters', 0)) <= 0 or not 0 < self.warmup_ratio <= 1.0:
+                raise ValueError('lr warm-up needs warmup_iters > 0 and 0 < warmup_ratio <= 1')
         self.lr_cfg = lr_cfg
         self.log_interval = int((_get(cfg, 'log_config', None) or {}).get('interval', 20))
         ck = _get(cfg, 'checkpoint_config', None)          # None = no CheckpointHook (mmcv register_checkpoint_hook)
@@ -153,8 +163,18 @@ class EpochRunner:
         per_rank = int(math.ceil(len(source) / self.world))
         self.iters_per_epoch = per_rank // self.batch_size if self.drop_last else int(math.ceil(per_rank / self.batch_size))
         self.max_iters = self.max_epochs * self.iters_per_epoch
+        if self.warmup is not None:
+            self.warmup_iters = int(lr_cfg['warmup_iters']) * (self.iters_per_epoch if lr_cfg.get('warmup_by_epoch') else 1)
 
     def current_lr(self):
+        """The rate of iteration ``self.iter``: the policy's regular rate, scaled by the warm-up rule during the first
+        ``warmup_iters`` iterations (counted from the start of the run: a resumed run continues where it stopped)."""
+        lr = self.regular_lr()
+        if self.warmup is not None and self.iter < self.warmup_iters:
+            lr = warmup_lr(lr, self.iter, self.warmup, self.warmup_iters, self.warmup_ratio)
+        return lr
+
+    def regular_lr(self):
         base = self.engine.opt.base_lr
         if self.lr_cfg['policy'] == 'CosineAnnealing':
             return cosine_lr(base, self.iter, self.max_iters, float(self.lr_cfg.get('min_lr', 0) or 0))
@@ -404,7 +424,8 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     """Train ``model`` on ``dataset`` the way the reference's ``train_model`` does for the skeleton configs; returns the
     ``EpochRunner`` (its ``.log`` holds the interval records, ``.engine`` the optimizer state).
 
-    cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer`` (SGD), ``lr_config``,
+    cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer`` (SGD),
+    ``optimizer_config.grad_clip``, ``lr_config`` (policy + warm-up),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
     ``auto_resume``; with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
     overrides ``data.val``: a map-style dataset or a (``SkeletonStore``, ``SkeletonBatcher``) pair built for the val
@@ -415,14 +436,12 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     opt_cfg = dict(_get(cfg, 'optimizer', None) or dict(type='SGD', lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True))
     if opt_cfg.pop('type', 'SGD') != 'SGD':
         raise NotImplementedError('the skeleton configs train with SGD (configs/_init_/lr_schedual.py:11)')
-    oc = _get(cfg, 'optimizer_config', None) or {}
-    if oc.get('grad_clip'):
-        raise NotImplementedError('grad_clip is None in the shipped configs; clipping is not implemented')
+    grad_clip = (_get(cfg, 'optimizer_config', None) or {}).get('grad_clip')
     model = model.to(device)
     world = _rank_world()[1]
     engine = TrainEngine(model, lr=opt_cfg.get('lr', 0.1), momentum=opt_cfg.get('momentum', 0),
                          weight_decay=opt_cfg.get('weight_decay', 0), nesterov=opt_cfg.get('nesterov', False),
-                         use_graph=use_graph, strict_graph=world > 1)
+                         use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip)
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)
     work_dir = _get(cfg, 'work_dir', None)
     runner = EpochRunner(model, engine, source, cfg, work_dir=work_dir, meta=meta, logger=logger)

@@ -9,6 +9,7 @@
 //       forward in one launch (torch.nn.functional.batch_norm's training-mode buffer update, momentum form)
 // All sums run in a fixed order (no atomics): the step stays bit-reproducible.
 #include "common.h"
+#include "sgd_update.h"
 
 namespace {
 
@@ -219,15 +220,7 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float*
                                              long n) {
   const float rate = lr[0];
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  auto one = [&](float pv, float gv, float& bv) {
-    gv = gv + wd * pv;
-    float st = gv;
-    if (buf) {
-      bv = bv * mom + gv;
-      st = nesterov ? gv + mom * bv : bv;
-    }
-    return pv - rate * st;
-  };
+  auto one = [&](float pv, float gv, float& bv) { return sgd_update(pv, gv, bv, buf != nullptr, rate, mom, wd, nesterov); };
   if (i < n4) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];

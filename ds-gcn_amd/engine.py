@@ -6,7 +6,8 @@ the log scalars and a bucketed NCCL all-reduce.  Here:
 
     graph A (hipGraph replay): zero-grad + forward + backward + pack gradients into the flat buffer
     one RCCL all-reduce of the flat gradient buffer (N > 1; between the graphs, never captured)
-    graph B (hipGraph replay): SGD-nesterov update on the flat buffers, rate read from a device scalar
+    graph B (hipGraph replay): SGD-nesterov update on the flat buffers, rate read from a device scalar; with
+                               ``grad_clip`` the total-norm clip of the averaged gradient rides in the same graph
 
 ``bench.py`` times exactly this object, ``apis.train_model`` drives it epoch by epoch.
 """
@@ -21,15 +22,19 @@ from .train import FlatSGD
 class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
-                 warmup_eager=2, strict_graph=False, extra_allreduce=False):
-        """strict_graph: a failed capture raises instead of falling back to eager launches (multi-GPU runs: ranks must not
+                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None):
+        """grad_clip: mmcv's ``optimizer_config.grad_clip`` dict (``max_norm``, ``norm_type`` 2 or inf) or None.  The clip
+        runs with the update, AFTER the all-reduce (the reference's order: backward, DDP average, clip_grads, step): every
+        rank holds the same averaged buffer and the norm is reduced in a fixed order, so every rank applies the same
+        coefficient without a second collective.  ``step()`` then also returns ``grad_norm`` (before clipping).
+        strict_graph: a failed capture raises instead of falling back to eager launches (multi-GPU runs: ranks must not
         silently differ).  extra_allreduce: issue the gradient all-reduce even at world size 1 (measurement of the N > 1
         call sequence under a 1-rank RCCL group)."""
         self.model = model
         self.flat = FlatParams(model, gather=True)
         self.dp = FlatDataParallel(self.flat, process_group)
         self.opt = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                           capturable=True)
+                           capturable=True, grad_clip=grad_clip)
         self.use_graph = bool(use_graph) and self.flat.flat_p.is_cuda
         self.strict_graph = strict_graph
         self.extra_allreduce = extra_allreduce
@@ -81,11 +86,19 @@ class TrainEngine:
         with torch.cuda.graph(g_b, capture_error_mode='thread_local'):
             self.opt.step()
         torch.cuda.synchronize()
-        return g_a, g_b, skp, slb, logs
+        return g_a, g_b, skp, slb, self._with_grad_norm(logs, static=True)
+
+    def _with_grad_norm(self, logs, static=False):
+        """The optimizer's one-float norm as a log scalar: the static tensor itself beside a replayed graph's other static
+        outputs, a copy of it after an eager step (whose other log tensors are fresh every step too)."""
+        if self.opt.grad_norm is None:
+            return logs
+        return dict(logs, grad_norm=self.opt.grad_norm[0] if static else self.opt.grad_norm[0].clone())
 
     # ---- the step ------------------------------------------------------------------------------------------
     def step(self, keypoint, label, lr=None):
-        """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc): no host sync here."""
+        """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc; grad_norm with grad_clip): no host
+        sync here."""
         if lr is not None:
             self.opt.set_lr(lr)
         key = (tuple(keypoint.shape), tuple(label.shape))
@@ -108,6 +121,7 @@ class TrainEngine:
             logs = self._fwd_bwd(keypoint, label)
             self._exchange()
             self.opt.step()
+            logs = self._with_grad_norm(logs)
             self._seen[key] = self._seen.get(key, 0) + 1
         self.iter += 1
         return logs

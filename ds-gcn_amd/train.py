@@ -15,9 +15,15 @@ class FlatSGD:
     ``capturable=True`` keeps the learning rate in a one-element device tensor (``set_lr`` fills it): a ``step()`` captured
     in a hipGraph then follows the per-iteration schedule on replay instead of freezing the rate of the capture.  The
     momentum buffer is allocated once and only ever written in place (``load_state_dict`` included), so a captured
-    ``step()`` keeps updating the live buffer after a resume."""
+    ``step()`` keeps updating the live buffer after a resume.
 
-    def __init__(self, flat, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, capturable=False):
+    ``grad_clip``: mmcv's ``optimizer_config.grad_clip`` dict (``max_norm``, ``norm_type`` 2 or inf) — ``step()`` then clips
+    the flat gradient by its total norm first, the way ``torch.nn.utils.clip_grad_norm_`` does before ``optimizer.step()``
+    (the flat buffer has no padding: its elements are exactly the parameters' elements).  ``flat_g`` holds the clipped
+    gradient afterwards and ``grad_norm`` (one device float, allocated here) the total norm BEFORE clipping.  On the device
+    that is two launches (csrc/clip.hip) in place of ``dsgcn_sgd_step``; clipping adds no optimizer state."""
+
+    def __init__(self, flat, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, capturable=False, grad_clip=None):
         self.flat = flat
         self.lr = lr
         self.base_lr = lr
@@ -29,16 +35,51 @@ class FlatSGD:
         self.lr_t = torch.full((1,), float(lr), device=flat.flat_p.device, dtype=flat.flat_p.dtype) if capturable else None
         if capturable and momentum:
             self.buf = torch.zeros_like(flat.flat_p)       # torch's first step sets buf = g; momentum * 0 + g is the same value
+        self.clip = parse_grad_clip(grad_clip)             # None | (max_norm, 2 or 0 = inf)
+        self.grad_norm = self.clip_partial = None
+        if self.clip is not None:
+            # both workspaces here, never inside step(): an allocation inside a captured step is replayed as garbage
+            dev = flat.flat_p.device
+            self.grad_norm = torch.zeros(1, device=dev, dtype=torch.float32)
+            if capturable and dev.type == 'cuda' and flat.flat_p.dtype == torch.float32:
+                rows = native.lib().dsgcn_grad_norm_rows(flat.flat_p.numel())
+                native.check(min(rows, 0), 'dsgcn_grad_norm_rows')
+                self.clip_partial = torch.zeros(rows, device=dev, dtype=torch.float64)
 
     def set_lr(self, lr):
         self.lr = float(lr)
         if self.lr_t is not None:
             self.lr_t.fill_(self.lr)
 
+    def _fused(self):
+        p = self.flat.flat_p
+        return self.capturable and p.is_cuda and p.dtype == torch.float32 and kernels.FUSED_ENDS
+
     @torch.no_grad()
     def step(self):
         p, g = self.flat.flat_p, self.flat.flat_g
-        if self.capturable and p.is_cuda and p.dtype == torch.float32 and kernels.FUSED_ENDS:
+        if self.clip is not None and self._fused():
+            # norm partials, then clip + update in one launch (csrc/clip.hip): one extra read of the flat gradient
+            max_norm, norm_type = self.clip
+            st = torch.cuda.current_stream().cuda_stream
+            rc = native.lib().dsgcn_grad_norm_partials(g.data_ptr(), g.numel(), norm_type, self.clip_partial.data_ptr(), st)
+            native.check(rc, 'dsgcn_grad_norm_partials')
+            rc = native.lib().dsgcn_sgd_step_clip(p.data_ptr(), g.data_ptr(), self.buf.data_ptr() if self.momentum else None,
+                                                  self.lr_t.data_ptr(), self.clip_partial.data_ptr(),
+                                                  self.clip_partial.numel(), norm_type, max_norm, self.grad_norm.data_ptr(),
+                                                  float(self.momentum), float(self.weight_decay),
+                                                  int(bool(self.nesterov)), p.numel(), st)
+            native.check(rc, 'dsgcn_sgd_step_clip')
+            return
+        if self.clip is not None:
+            # the same arithmetic with torch ops: fp64 sum of squares (max |g|), fp32 total, fp32 coefficient
+            max_norm, norm_type = self.clip
+            total = (g.abs().max() if norm_type == 0 else g.double().square().sum().sqrt()).to(torch.float32)
+            coef = max_norm / (total + 1e-6)
+            coef = torch.where(coef < 1.0, coef, torch.ones_like(coef))
+            g.mul_(coef.to(g.dtype))
+            self.grad_norm.copy_(total.reshape(1))
+        if self._fused():
             # one launch (csrc/head.hip k_sgd) instead of five elementwise passes over the flat buffers
             rc = native.lib().dsgcn_sgd_step(p.data_ptr(), g.data_ptr(), self.buf.data_ptr() if self.momentum else None,
                                              self.lr_t.data_ptr(), float(self.momentum), float(self.weight_decay),
@@ -103,6 +144,45 @@ class FlatSGD:
                 off, n = self.flat.slices[i]
                 buf[off:off + n].copy_(mb.reshape(-1))
         self.buf = buf
+
+
+def parse_grad_clip(grad_clip):
+    """mmcv's ``optimizer_config.grad_clip`` (the keyword arguments of ``torch.nn.utils.clip_grad_norm_``) ->
+    ``None`` or ``(max_norm, norm_type)`` with ``norm_type`` 2 or 0 (= inf, the C ABI's code)."""
+    if grad_clip is None:
+        return None
+    cfg = dict(grad_clip)
+    if 'max_norm' not in cfg:
+        raise ValueError(f'grad_clip needs max_norm (got {sorted(cfg)})')
+    max_norm = float(cfg.pop('max_norm'))
+    if not max_norm >= 0.0:
+        raise ValueError(f'grad_clip max_norm must be >= 0, got {max_norm}')
+    norm_type = cfg.pop('norm_type', 2)
+    if cfg:
+        raise NotImplementedError(f'grad_clip options {sorted(cfg)} are not supported (max_norm, norm_type)')
+    if isinstance(norm_type, str):
+        if norm_type != 'inf':
+            raise NotImplementedError(f'grad_clip norm_type {norm_type!r}: 2 and inf are implemented')
+        norm_type = math.inf
+    norm_type = float(norm_type)
+    if norm_type == 2.0:
+        return max_norm, 2
+    if norm_type == math.inf:
+        return max_norm, 0
+    raise NotImplementedError(f'grad_clip norm_type {norm_type!r}: 2 and inf are implemented')
+
+
+def warmup_lr(regular_lr, cur_iter, warmup, warmup_iters, warmup_ratio=0.1):
+    """mmcv LrUpdaterHook.get_warmup_lr for ``cur_iter < warmup_iters`` (from ``warmup_iters`` on the caller keeps the
+    regular rate): constant ``r * ratio``; linear ``r * (1 - (1 - cur/iters) * (1 - ratio))``; exp
+    ``r * ratio ** (1 - cur/iters)``."""
+    if warmup == 'constant':
+        return regular_lr * warmup_ratio
+    if warmup == 'linear':
+        return regular_lr * (1 - (1 - cur_iter / warmup_iters) * (1 - warmup_ratio))
+    if warmup == 'exp':
+        return regular_lr * warmup_ratio ** (1 - cur_iter / warmup_iters)
+    raise ValueError(f'"{warmup}" is not a supported type for warming up, valid types are "constant", "linear" and "exp"')
 
 
 def cosine_lr(base_lr, it, total_iters, min_lr=0.0):

@@ -631,6 +631,26 @@ int dsgcn_data_bn_bwd(const float* x, const float* dy, const float* save_mean, c
 int dsgcn_sgd_step(float* p, const float* g, float* buf, const float* lr, float momentum, float weight_decay,
                    int nesterov, long long n, void* stream);
 
+/* Gradient clipping by total norm over a flat fp32 buffer, folded into the SGD step (torch.nn.utils.clip_grad_norm_ +
+ * optimizer.step(), mmcv's OptimizerHook with grad_clip=dict(max_norm=..., norm_type=...); configs/_init_/lr_schedual.py:24).
+ * norm_type: 2, or 0 for the infinity norm.  Everything is reduced in a fixed order on a grid that depends on n only: the
+ * same bits on every run and every device.
+ *   dsgcn_grad_norm_rows      number of partial rows for n elements (one per 8192-element slice).
+ *   dsgcn_grad_norm_partials  partial[r] (fp64) = sum of g*g (each square exact in fp64) resp. max |g| over slice r of g
+ *                             (16-byte aligned).  One launch.
+ *   dsgcn_sgd_step_clip       total = sqrt(sum of the rows) resp. their max, rounded to fp32 -> grad_norm_out[0] (the norm
+ *                             BEFORE clipping, the value mmcv logs);  coef = min(1, max_norm / (total + 1e-6)) in fp32;
+ *                             then dsgcn_sgd_step's update with g * coef in place of g, and g * coef written back to g (as
+ *                             clip_grad_norm_ leaves the .grad tensors).  With coef == 1 p and buf come out bit-identical
+ *                             to dsgcn_sgd_step.  A non-finite total gets no special case (error_if_nonfinite=False); a NaN
+ *                             total leaves coef at 1.  rows / partial: as written by dsgcn_grad_norm_partials for the same
+ *                             n.  One launch. */
+int dsgcn_grad_norm_rows(long long n);
+int dsgcn_grad_norm_partials(const float* g, long long n, int norm_type, double* partial, void* stream);
+int dsgcn_sgd_step_clip(float* p, float* g, float* buf, const float* lr, const double* partial, int rows, int norm_type,
+                        float max_norm, float* grad_norm_out, float momentum, float weight_decay, int nesterov,
+                        long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
