@@ -2950,3 +2950,6 @@ from .kernels_plain import dynadj_plain  # noqa: E402,F401
 
 # the ops of the test pass (csrc/head_test.hip's front, the engine-owned weight-image table) live in a module of their own
 from .kernels_infer import head_test, head_test_fits, private_weight_images  # noqa: E402,F401
+
+# the head with class weights / soft labels / multi-label BCE (csrc/head_target.hip) likewise
+from .kernels_head import head_target  # noqa: E402,F401

@@ -144,6 +144,8 @@ SIGNATURES = {
     'dsgcn_dynadj_bwd_jobs': [c_f] * 5 + [c_i, c_i] + [c_f] * 4 + [c_int] * 7 + [ctypes.c_void_p, c_int, c_st],
     'dsgcn_head_loss_fwd': [c_f, c_f, c_f, c_i] + [c_int] * 4 + [ctypes.c_float] + [c_f] * 6 + [c_st],
     'dsgcn_head_loss_bwd': [c_f, c_f, c_f, c_i, c_f] + [c_int] * 4 + [ctypes.c_float] + [c_f] * 3 + [c_st],
+    'dsgcn_head_target_fwd': [c_f] * 4 + [ctypes.c_void_p] + [c_int] * 5 + [ctypes.c_float] + [c_f] * 7 + [c_st],
+    'dsgcn_head_target_bwd': [c_f] * 5 + [c_int] * 4 + [ctypes.c_float] + [c_f] * 3 + [c_st],
     'dsgcn_head_test_fwd': [c_f, c_f, c_f] + [c_int] * 6 + [c_f, c_f, c_st],
     'dsgcn_data_bn_fwd': [c_f] * 10 + [c_int] * 7 + [ctypes.c_float, ctypes.c_float, c_st],
     'dsgcn_data_bn_bwd': [c_f] * 6 + [c_int] * 6 + [c_st],

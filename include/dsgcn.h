@@ -585,6 +585,30 @@ int dsgcn_head_loss_fwd(const float* feat, const float* w, const float* b, const
 int dsgcn_head_loss_bwd(const float* prob, const float* pooled, const float* w, const long long* label, const float* gloss,
                         int N, int M, int C, int K, float loss_weight, float* dfeat, float* dw, float* db, void* stream);
 
+/* The same head for the reference's other loss options (csrc/head_target.hip), again two launches forward and one
+ * backward, no host sync.  class_weight (K) or NULL (all 1).  mode selects the target and the loss; s = score,
+ * p = softmax(s), w = class_weight, per clip a numerator L_n and a denominator D_n:
+ *   0  target (N) int64 labels:  L = w_y (logsumexp(s) - s_y),  D = w_y                  F.cross_entropy(weight=)
+ *      (cross_entropy_loss.py:76-82); a label outside [0, K) gives a NaN loss and its weight is not read;
+ *      acc (2) fp64 as dsgcn_head_loss_fwd.
+ *   1  target (N, K) float soft labels q:  L = -sum_k q_k w_k log p_k,  D = sum_k q_k w_k with class_weight, else 1
+ *      (cross_entropy_loss.py:53-74).
+ *   2  target (N, K) float multi-hot labels q:  L = sum_k w_k (max(s_k, 0) - s_k q_k + log1p(exp(-|s_k|))),  D = K
+ *      F.binary_cross_entropy_with_logits(weight=) (cross_entropy_loss.py:118-123).
+ *   loss (1) = loss_weight * sum_n L_n / sum_n D_n (NaN when the denominator is 0, as F.cross_entropy);  den (1) =
+ *   sum_n D_n, read by the backward on the device;  dscore (N, K) = d(sum_n L_n) / d score;  pooled (N, C), score (N, K)
+ *   as above;  clip (N, 4): scratch.  acc is written in mode 0 only and may be NULL otherwise (the reference reports no
+ *   accuracy when label and score have the same shape, heads/base.py:66).  All sums in a fixed order: repeated launches
+ *   are bit-identical.
+ * dsgcn_head_target_bwd: gradients for g = gloss * loss_weight / den: dfeat (N*M, C), dw (K, C), db (K).
+ * DSGCN_EINVAL: a NULL pointer (b, class_weight and, outside mode 0, acc excepted), a non-positive size, mode outside
+ * 0..2.  DSGCN_EUNSUPPORTED: (C + K) floats (forward) or max(N, K) floats (backward) above 60 KB of LDS. */
+int dsgcn_head_target_fwd(const float* feat, const float* w, const float* b, const float* class_weight, const void* target,
+                          int mode, int N, int M, int C, int K, float loss_weight, float* pooled, float* score,
+                          float* dscore, float* clip, float* loss, float* den, double* acc, void* stream);
+int dsgcn_head_target_bwd(const float* dscore, const float* pooled, const float* w, const float* gloss, const float* den,
+                          int N, int M, int C, int K, float loss_weight, float* dfeat, float* dw, float* db, void* stream);
+
 /* The test-time head: simple_head.py:88-98 (person mean + fc_cls) followed by recognizergcn.py's average_clips step —
  * about eight framework launches and an (N*clips, K) round trip.  ONE launch, one workgroup per video.
  *   feat (N*clips*M, C): per-person plane means, clip-major within a video (what dsgcn_fuse_out_fwd_drop writes for a
