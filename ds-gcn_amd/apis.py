@@ -24,6 +24,10 @@ by iteration (the DS-GCN configs), ``step`` by epoch (configs/stgcn/stgcn_vanill
 with mmcv's ``warmup`` ('constant' / 'linear' / 'exp', ``warmup_iters``, ``warmup_ratio``, ``warmup_by_epoch``).
 ``optimizer_config.grad_clip=dict(max_norm=..., norm_type=2 | inf)`` (configs/_init_/lr_schedual.py:24) clips the averaged
 gradient by its total norm inside the update's hipGraph; ``grad_norm`` (before clipping) joins the log scalars.
+``optimizer_config=dict(type='GradientCumulativeOptimizerHook', cumulative_iters=k)`` makes every iteration a
+micro-iteration and every k-th one an update on the mean of the k gradients (``TrainEngine(accumulate=k)``): the schedule
+and the log count micro-iterations as mmcv's ``runner.iter`` does, the last ``max_iters % k`` iterations form a short group
+divided by their own count, and a group that an epoch end cuts short is closed there (checkpoints hold no accumulator).
 
 Not reproduced: TensorBoard logging, multi-optimizer configs.
 """
@@ -199,6 +203,14 @@ class EpochRunner:
             if (b + 1) % self.log_interval == 0 or b + 1 == self.iters_per_epoch:
                 self._flush_log(pending, lr, b + 1, time.perf_counter() - t0)
                 pending, t0 = [], time.perf_counter()
+        if getattr(self.engine, 'pending', 0):
+            # a group never straddles an epoch end: what a checkpoint or a validation pass sees there is a model whose
+            # every gradient has been applied, and a resumed run starts with an empty accumulator as this one continues
+            short = self.engine.pending
+            self.engine.flush(short)
+            if self.logger is not None and self.rank == 0:
+                self.logger.info('Epoch [%d] ends inside a group of %d accumulated iterations: updated on the mean of the '
+                                 'first %d', self.epoch + 1, self.engine.accumulate, short)
         self.epoch += 1
         if self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0 and self.rank == 0:
             self.save_checkpoint()
@@ -419,13 +431,29 @@ class EvalLoop:
         return rec
 
 
+def parse_optimizer_config(opt_hook):
+    """mmcv's ``optimizer_config`` -> (grad_clip, accumulate).  Without ``type`` (or ``OptimizerHook``): an update per
+    iteration.  ``GradientCumulativeOptimizerHook``: an update per ``cumulative_iters`` iterations (mmcv's default 1)."""
+    opt_hook = dict(opt_hook or {})
+    kind = opt_hook.get('type', 'OptimizerHook')
+    if kind == 'OptimizerHook':
+        return opt_hook.get('grad_clip'), 1
+    if kind == 'GradientCumulativeOptimizerHook':
+        k = opt_hook.get('cumulative_iters', 1)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f'cumulative_iters only accepts positive int, but got {k!r} instead.')
+        return opt_hook.get('grad_clip'), k
+    raise NotImplementedError(f'optimizer_config type {kind!r}: OptimizerHook and GradientCumulativeOptimizerHook are '
+                              'implemented')
+
+
 def train_model(model, dataset, cfg, distributed=None, validate=False, test=None, timestamp=None, meta=None,
                 device='cuda', logger=None, use_graph=True, val_dataset=None, prefetch=True):
     """Train ``model`` on ``dataset`` the way the reference's ``train_model`` does for the skeleton configs; returns the
     ``EpochRunner`` (its ``.log`` holds the interval records, ``.engine`` the optimizer state).
 
     cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer`` (SGD),
-    ``optimizer_config.grad_clip``, ``lr_config`` (policy + warm-up),
+    ``optimizer_config`` (``grad_clip``; ``type`` + ``cumulative_iters``), ``lr_config`` (policy + warm-up),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
     ``auto_resume``; with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
     overrides ``data.val``: a map-style dataset or a (``SkeletonStore``, ``SkeletonBatcher``) pair built for the val
@@ -436,12 +464,12 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     opt_cfg = dict(_get(cfg, 'optimizer', None) or dict(type='SGD', lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True))
     if opt_cfg.pop('type', 'SGD') != 'SGD':
         raise NotImplementedError('the skeleton configs train with SGD (configs/_init_/lr_schedual.py:11)')
-    grad_clip = (_get(cfg, 'optimizer_config', None) or {}).get('grad_clip')
+    grad_clip, accumulate = parse_optimizer_config(_get(cfg, 'optimizer_config', None))
     model = model.to(device)
     world = _rank_world()[1]
     engine = TrainEngine(model, lr=opt_cfg.get('lr', 0.1), momentum=opt_cfg.get('momentum', 0),
                          weight_decay=opt_cfg.get('weight_decay', 0), nesterov=opt_cfg.get('nesterov', False),
-                         use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip)
+                         use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip, accumulate=accumulate)
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)
     work_dir = _get(cfg, 'work_dir', None)
     runner = EpochRunner(model, engine, source, cfg, work_dir=work_dir, meta=meta, logger=logger)

@@ -9,6 +9,10 @@ the log scalars and a bucketed NCCL all-reduce.  Here:
     graph B (hipGraph replay): SGD-nesterov update on the flat buffers, rate read from a device scalar; with
                                ``grad_clip`` the total-norm clip of the averaged gradient rides in the same graph
 
+With ``accumulate=k > 1`` (mmcv GradientCumulativeOptimizerHook) a call of ``step()`` is one micro-iteration: graph A ends
+in ``acc += g`` on k - 1 calls out of k (graph M, no exchange, no update) and in ``g = (acc + g) / k, acc = 0`` on the k-th
+(graph S), which the exchange and graph B follow unchanged.
+
 ``bench.py`` times exactly this object, ``apis.train_model`` drives it epoch by epoch.
 """
 import torch
@@ -22,31 +26,40 @@ from .train import FlatSGD
 class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
-                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None):
+                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1):
         """grad_clip: mmcv's ``optimizer_config.grad_clip`` dict (``max_norm``, ``norm_type`` 2 or inf) or None.  The clip
         runs with the update, AFTER the all-reduce (the reference's order: backward, DDP average, clip_grads, step): every
         rank holds the same averaged buffer and the norm is reduced in a fixed order, so every rank applies the same
         coefficient without a second collective.  ``step()`` then also returns ``grad_norm`` (before clipping).
         strict_graph: a failed capture raises instead of falling back to eager launches (multi-GPU runs: ranks must not
         silently differ).  extra_allreduce: issue the gradient all-reduce even at world size 1 (measurement of the N > 1
-        call sequence under a 1-rank RCCL group)."""
+        call sequence under a 1-rank RCCL group).
+        accumulate: mmcv's ``GradientCumulativeOptimizerHook.cumulative_iters``.  With k > 1 every ``step()`` is one
+        micro-iteration — forward, backward (its own BatchNorm statistics, its own dropout masks), gradient added to the
+        accumulator — and every k-th one also averages the k gradients, exchanges, clips and updates, at the rate passed
+        on THAT call: k micro-batches on one GPU are the reference's k ranks.  ``flush()`` closes a short last group."""
         self.model = model
         self.flat = FlatParams(model, gather=True)
         self.dp = FlatDataParallel(self.flat, process_group)
         self.opt = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                           capturable=True, grad_clip=grad_clip)
+                           capturable=True, grad_clip=grad_clip, accumulate=accumulate)
+        self.accumulate = self.opt.accumulate
+        self.pending = 0           # gradients in the accumulator: micro-iterations since the last update
         self.use_graph = bool(use_graph) and self.flat.flat_p.is_cuda
         self.strict_graph = strict_graph
         self.extra_allreduce = extra_allreduce
         self.warmup_eager = warmup_eager
-        self._graphs = {}          # batch shape -> (graph A, graph B, static keypoint, static label, static outputs)
-        self._seen = {}            # batch shape -> eager steps taken
+        # batch shape [+ 'micro' | 'step' with accumulate > 1] -> (graph A, graph B or None, static keypoint, static label,
+        # static outputs)
+        self._graphs = {}
+        self._seen = {}            # the same key -> eager steps taken
         self.capture_error = None
         self._seed = None
         self.iter = 0
 
     # ---- pieces --------------------------------------------------------------------------------------------
-    def _fwd_bwd(self, keypoint, label):
+    def _fwd_bwd(self, keypoint, label, kind=None):
+        """kind: None (accumulate == 1) | 'micro' | 'step' — what follows the gradient collection."""
         self.opt.zero_grad()
         kernels.reset_leaf_uses()
         try:
@@ -61,6 +74,10 @@ class TrainEngine:
             else:
                 loss.backward(self._seed)
             self.flat.collect_grads()
+            if kind == 'micro':
+                self.opt.accum_add()
+            elif kind == 'step':
+                self.opt.accum_finish()
             kernels.dropout_step_advance()       # (fused dropout: the next step draws other masks; no-op without it)
         finally:
             # the update that follows rewrites the weights through raw pointers: cached weight images are stale from here
@@ -72,7 +89,7 @@ class TrainEngine:
         if self.extra_allreduce and self.dp.world == 1 and dist.is_available() and dist.is_initialized():
             dist.all_reduce(self.flat.flat_g)
 
-    def _capture(self, keypoint, label):
+    def _capture(self, keypoint, label, kind=None):
         # no extra warm-up pass here: the eager steps that precede the capture (warmup_eager) already ran this shape —
         # allocator pools, the pinned pointer table of dsgcn_pack, the momentum buffer — and a pass that is not a real
         # step would move the BatchNorm running statistics once too often
@@ -81,10 +98,12 @@ class TrainEngine:
         g_a = torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread polls its events while we capture (N > 1); neither graph holds a collective
         with torch.cuda.graph(g_a, capture_error_mode='thread_local'):
-            logs = self._fwd_bwd(skp, slb)
-        g_b = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_b, capture_error_mode='thread_local'):
-            self.opt.step()
+            logs = self._fwd_bwd(skp, slb, kind)
+        g_b = None
+        if kind != 'micro':
+            g_b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_b, capture_error_mode='thread_local'):
+                self.opt.step()
         torch.cuda.synchronize()
         return g_a, g_b, skp, slb, self._with_grad_norm(logs, static=True)
 
@@ -98,13 +117,18 @@ class TrainEngine:
     # ---- the step ------------------------------------------------------------------------------------------
     def step(self, keypoint, label, lr=None):
         """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc; grad_norm with grad_clip): no host
-        sync here."""
+        sync here.  With accumulate > 1: one micro-iteration; grad_norm is the one of the last update."""
         if lr is not None:
             self.opt.set_lr(lr)
         key = (tuple(keypoint.shape), tuple(label.shape))
+        kind = None
+        if self.accumulate > 1:
+            # a micro-iteration and a stepping iteration are two captures per batch shape, each after eager calls of its own
+            kind = 'step' if self.pending + 1 == self.accumulate else 'micro'
+            key = key + (kind,)
         if self.use_graph and key not in self._graphs and self._seen.get(key, 0) >= self.warmup_eager:
             try:
-                self._graphs[key] = self._capture(keypoint, label)
+                self._graphs[key] = self._capture(keypoint, label, kind)
             except Exception as exc:       # noqa: BLE001 — report and fall back (or raise) below
                 self.capture_error = f'{type(exc).__name__}: {exc}'
                 if self.strict_graph:
@@ -115,16 +139,43 @@ class TrainEngine:
             skp.copy_(keypoint)
             slb.copy_(label)
             g_a.replay()
-            self._exchange()
-            g_b.replay()
+            if kind != 'micro':
+                self._exchange()
+                g_b.replay()
         else:
-            logs = self._fwd_bwd(keypoint, label)
-            self._exchange()
-            self.opt.step()
+            logs = self._fwd_bwd(keypoint, label, kind)
+            if kind != 'micro':
+                self._exchange()
+                self.opt.step()
             logs = self._with_grad_norm(logs)
             self._seen[key] = self._seen.get(key, 0) + 1
+        if kind is not None:
+            self.pending = self.pending + 1 if kind == 'micro' else 0
         self.iter += 1
         return logs
 
+    def flush(self, remainder=None, lr=None):
+        """Close a short group early: average the ``remainder`` gradients in the accumulator (all of them; None = however
+        many there are), exchange, clip and update — mmcv's rule for the last ``max_iters % k`` iterations of a run, which
+        it divides by their own count.  The rate is ``lr`` or the one of the last call.  Eager launches (once per run or
+        epoch); no forward runs, so no BatchNorm statistic and no dropout counter moves.  -> {} or {'grad_norm': ...}."""
+        if self.accumulate == 1:
+            raise RuntimeError('flush(): this engine does not accumulate (accumulate=1)')
+        if remainder is None:
+            remainder = self.pending
+        if remainder != self.pending or remainder < 1:
+            raise ValueError(f'flush({remainder}): the accumulator holds {self.pending} gradient(s)')
+        if lr is not None:
+            self.opt.set_lr(lr)
+        self.flat.flat_g.zero_()                   # the group's gradients are all in the accumulator already
+        self.opt.accum_finish(remainder)
+        self._exchange()
+        self.opt.step()
+        self.pending = 0
+        return self._with_grad_norm({})
+
     def graphed(self, keypoint, label):
-        return (tuple(keypoint.shape), tuple(label.shape)) in self._graphs
+        key = (tuple(keypoint.shape), tuple(label.shape))
+        if self.accumulate > 1:
+            return all(key + (kind,) in self._graphs for kind in ('micro', 'step'))
+        return key in self._graphs

@@ -154,6 +154,8 @@ SIGNATURES = {
     'dsgcn_grad_norm_partials': [c_f, ctypes.c_longlong, c_int, ctypes.c_void_p, c_st],
     'dsgcn_sgd_step_clip': [c_f, c_f, c_f, c_f, ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_float,
                             ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_grad_accum': [c_f, c_f, ctypes.c_longlong, c_st],
+    'dsgcn_grad_accum_finish': [c_f, c_f, c_f, ctypes.c_longlong, c_st],
     'dsgcn_bn_running_multi': [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
                                ctypes.POINTER(ctypes.c_float), c_int, c_st],
 }

@@ -21,9 +21,16 @@ class FlatSGD:
     the flat gradient by its total norm first, the way ``torch.nn.utils.clip_grad_norm_`` does before ``optimizer.step()``
     (the flat buffer has no padding: its elements are exactly the parameters' elements).  ``flat_g`` holds the clipped
     gradient afterwards and ``grad_norm`` (one device float, allocated here) the total norm BEFORE clipping.  On the device
-    that is two launches (csrc/clip.hip) in place of ``dsgcn_sgd_step``; clipping adds no optimizer state."""
+    that is two launches (csrc/clip.hip) in place of ``dsgcn_sgd_step``; clipping adds no optimizer state.
 
-    def __init__(self, flat, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, capturable=False, grad_clip=None):
+    ``accumulate=k > 1``: mmcv's ``GradientCumulativeOptimizerHook(cumulative_iters=k)`` — k backward passes per update.
+    ``accum_add()`` adds the flat gradient to ``acc`` (a buffer of its own, allocated here); ``accum_finish()`` leaves
+    ``(acc + g) * (1 / k)`` in the flat gradient and ``acc`` at zero, and ``step()`` follows as ever.  One launch each
+    (csrc/accum.hip); off the fused path the same two operations with torch ops.  ``acc`` is no optimizer state: it is
+    empty between groups and not part of ``state_dict()``."""
+
+    def __init__(self, flat, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, capturable=False, grad_clip=None,
+                 accumulate=1):
         self.flat = flat
         self.lr = lr
         self.base_lr = lr
@@ -45,6 +52,16 @@ class FlatSGD:
                 rows = native.lib().dsgcn_grad_norm_rows(flat.flat_p.numel())
                 native.check(min(rows, 0), 'dsgcn_grad_norm_rows')
                 self.clip_partial = torch.zeros(rows, device=dev, dtype=torch.float64)
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f'accumulate must be an integer >= 1, got {accumulate!r}')
+        self.accumulate = accumulate
+        self.acc = self.acc_factor = self.acc_tail_factor = None
+        if accumulate > 1:
+            # here for the same reason as the clip's workspaces; the factors are device floats so that a captured
+            # accum_finish() and an eager one for a short last group read theirs the same way
+            self.acc = torch.zeros_like(flat.flat_g)
+            self.acc_factor = torch.full((1,), 1.0 / accumulate, device=flat.flat_g.device, dtype=flat.flat_g.dtype)
+            self.acc_tail_factor = torch.ones_like(self.acc_factor)
 
     def set_lr(self, lr):
         self.lr = float(lr)
@@ -99,6 +116,42 @@ class FlatSGD:
             p.addcmul_(g, self.lr_t, value=-1.0)
         else:
             p.add_(g, alpha=-self.lr)
+
+    def _accum_ready(self):
+        if self.acc is None:
+            raise RuntimeError('FlatSGD was built with accumulate=1: there is no accumulation buffer')
+        return self.flat.flat_g
+
+    @torch.no_grad()
+    def accum_add(self):
+        """acc += flat gradient (a micro-iteration: no update follows)."""
+        g = self._accum_ready()
+        if self._fused():
+            rc = native.lib().dsgcn_grad_accum(self.acc.data_ptr(), g.data_ptr(), g.numel(),
+                                               torch.cuda.current_stream().cuda_stream)
+            native.check(rc, 'dsgcn_grad_accum')
+            return
+        self.acc.add_(g)
+
+    @torch.no_grad()
+    def accum_finish(self, count=None):
+        """flat gradient = (acc + flat gradient) * (1 / count), acc = 0.  count None: the group is full (1 / accumulate, the
+        only form a captured step uses); an int: a short last group of that many gradients (mmcv divides the tail of a run
+        by its own length)."""
+        g = self._accum_ready()
+        factor = self.acc_factor
+        if count is not None:
+            if not 1 <= int(count) <= self.accumulate:
+                raise ValueError(f'accum_finish: a group holds 1..{self.accumulate} gradients, got {count}')
+            factor = self.acc_tail_factor
+            factor.fill_(1.0 / int(count))
+        if self._fused():
+            rc = native.lib().dsgcn_grad_accum_finish(self.acc.data_ptr(), g.data_ptr(), factor.data_ptr(), g.numel(),
+                                                      torch.cuda.current_stream().cuda_stream)
+            native.check(rc, 'dsgcn_grad_accum_finish')
+            return
+        g.add_(self.acc).mul_(factor)
+        self.acc.zero_()
 
     def zero_grad(self):
         self.flat.zero_grad()

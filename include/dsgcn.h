@@ -675,6 +675,20 @@ int dsgcn_sgd_step_clip(float* p, float* g, float* buf, const float* lr, const d
                         float max_norm, float* grad_norm_out, float momentum, float weight_decay, int nesterov,
                         long long n, void* stream);
 
+/* Gradient accumulation over flat fp32 buffers of n elements (csrc/accum.hip): mmcv's GradientCumulativeOptimizerHook, k
+ * backward passes per optimizer step, with the sum kept in a buffer of its own.
+ *   dsgcn_grad_accum         acc[i] += g[i]                                       (a micro-iteration; g is only read)
+ *   dsgcn_grad_accum_finish  g[i] = (acc[i] + g[i]) * factor[0];  acc[i] = 0      (the stepping iteration)
+ * factor: ONE device float (1 / k; 1 / remainder for a short last group).  finish leaves the averaged gradient where
+ * dsgcn_sgd_step[_clip] and the all-reduce read it and acc clean for the next group.  Each element is one rounded fp32
+ * add (and one rounded multiply) by exactly one thread: no atomics, bit-identical from run to run.  One launch each, no
+ * allocation, no sync.  The buffers need 4-byte alignment only: elements before the first 16-byte boundary and the
+ * n % 4 rest go one float at a time, the others 16 bytes at a time (acc and g at different distances from a 16-byte
+ * boundary: every element one float at a time).  DSGCN_EINVAL: a NULL pointer, n <= 0, a pointer that is not 4-byte
+ * aligned, acc and g overlapping. */
+int dsgcn_grad_accum(float* acc, const float* g, long long n, void* stream);
+int dsgcn_grad_accum_finish(float* acc, float* g, const float* factor, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
