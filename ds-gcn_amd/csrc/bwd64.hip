@@ -12,7 +12,7 @@
 // the data gradient then takes its B operand (dz_eff, k = co, j = position) from the SAME tile and its A operand (W^T)
 // from a 64x64 weight image in LDS.  Work unit = (sample, 64 positions); K-splits over the grid, every split writes
 // its partial dW / db / ipart row (ordered sums later: dsgcn_colsum).
-#include "common.h"
+#include "pw4_block.h"
 
 namespace {
 
@@ -47,10 +47,24 @@ __device__ long long g_bf_stamp[64];
 #define BF_STAMP() do {} while (0)
 #endif
 
+// Guest blocks (pw4_block.h): the two instantiations the shipped DS-STGCN step runs for the narrow `pre` convs (plain
+// input, batch-statistics terms: block 1 on the fp32 form, blocks 2-5 on the bf16 form) carry the data gradient of the
+// dynamic-adjacency projections in their LEADING workgroups; the splits follow.  No other instantiation has the code.
+template <bool HASC, bool AFF, bool HAS2>
+constexpr bool bf_hosts = HASC && !AFF && !HAS2;
+
 // HASC: batch-statistics terms (A0, B0);  AFF: the input carries an affine and / or a ReLU;  HAS2: second input stream.
 template <bool HASC, bool AFF, bool HAS2>
-__global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a) {
+__global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_hosts<HASC, AFF, HAS2>> guest) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  int bid = blockIdx.x;
+  if constexpr (bf_hosts<HASC, AFF, HAS2>) {
+    if (bid < guest.nblk) {
+      p4_block<1, 2, 0, 16, 1>(guest.a, bid, lds);
+      return;
+    }
+    bid -= guest.nblk;
+  }
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -65,7 +79,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   const int Ci = a.Ci, Co = a.Co, L = a.L, L4 = L * 4;
-  const int split = blockIdx.x;
+  const int split = bid;
   const int ch0 = split * a.cps, ch1 = min(a.total_chunks, ch0 + a.cps);
 
   for (int i = tid; i < 64 * 65; i += BF_NT) {
@@ -316,8 +330,16 @@ constexpr int BB_DK = 0, BB_XK = 3 * 64 * BB_RB, BB_DT = 2 * 3 * 64 * BB_RB, BB_
               BB_OSO = BB_WT + 3 * 64 * BB_RT, BB_LDS = BB_OSO + 64 * BB_OS * 4;
 
 template <bool HASC, bool AFF>
-__global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a) {
+__global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a, P4GuestArg<bf_hosts<HASC, AFF, false>> guest) {
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
+  int bid = blockIdx.x;
+  if constexpr (bf_hosts<HASC, AFF, false>) {      // guest blocks: see k_bwd64
+    if (bid < guest.nblk) {
+      p4_block<1, 2, 0, 16, 1>(guest.a, bid, reinterpret_cast<float*>(ldsb));
+      return;
+    }
+    bid -= guest.nblk;
+  }
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -331,7 +353,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   const int Ci = a.Ci, Co = a.Co, L = a.L, L4 = L * 4;
-  const int split = blockIdx.x;
+  const int split = bid;
   const int ch0 = split * a.cps, ch1 = min(a.total_chunks, ch0 + a.cps);
   // staging role: row (a dz row AND an input row), positions 8*q ..+7 of the unit
   const int row = tid >> 2, q = tid & 3;
@@ -595,8 +617,10 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
                                                        const float* s2, const float* h2, int relu, const float* w,
                                                        const float* z, const float* gz, const float* A0, const float* B0,
                                                        float* dx, float* dx2, float* dwp, float* dbp, int pstride,
-                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st) {
+                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
+                                                       const dsgcn_guest_conv* guest, int* hosted) {
   BfPlan p;
+  if (hosted) *hosted = 0;
   if (!bf_plan(n, Ci, Co, L, &p)) return 0;
   BfArgs a = {};
   a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu; a.w = w; a.z = z; a.gz = gz;
@@ -609,8 +633,17 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
     a.cps = (a.total_chunks + p.splits - 1) / p.splits;
   }
   const size_t lds = b3 ? (size_t)BB_LDS : (size_t)(192 * BF_LS + 64 * 65 + 2 * 64 + 4 * 64) * sizeof(float);
-  const dim3 grid((unsigned)p.splits), blk(BF_NT);
   const bool hasc = A0 != nullptr, has2 = x2 != nullptr, aff = s1 != nullptr || s2 != nullptr || relu != 0 || has2;
+  // a guest (the projections' data gradient) rides in the leading workgroups of the two hosting instantiations; its body
+  // needs less LDS than either form of this pass
+  P4Hosted hg;
+  const P4Hosted* h = nullptr;
+  if (guest && hasc && !aff && !has2 && dsgcn_p4_guest_plan(guest, 1, &hg) && hg.lds <= lds) h = &hg;
+  const dim3 blk(BF_NT);
+  // set by the instantiation launched: it is a host (compile-time predicate) and carries h — the grid and the answer in
+  // *hosted follow from that, never from the run-time test above alone
+  bool took = false;
+#define BF_GRID() dim3((unsigned)p.splits + (took ? (unsigned)h->g.nblk : 0u))
   if (b3) {
 #define BB_LAUNCH(HC, AF)                                                                                               \
   {                                                                                                                   \
@@ -621,7 +654,9 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
       if (e != hipSuccess) return (int)e;                                                                             \
       raised = true;                                                                                                  \
     }                                                                                                                 \
-    hipLaunchKernelGGL((k_bwd64b<HC, AF>), grid, blk, lds, st, a);                                                \
+    took = bf_hosts<HC, AF, false> && h;                                                                            \
+    hipLaunchKernelGGL((k_bwd64b<HC, AF>), BF_GRID(), blk, lds, st, a,                                              \
+                       p4_guest_arg<bf_hosts<HC, AF, false>>(took ? h : nullptr));                                  \
   }
     if (hasc) {
       if (aff) BB_LAUNCH(true, true) else BB_LAUNCH(true, false)
@@ -630,6 +665,7 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
     }
 #undef BB_LAUNCH
     DSGCN_LAUNCH_CHECK();
+    if (hosted && took) *hosted = 1;
     return 1;
   }
   // the LDS image (69 KB) is above the default dynamic limit: raised once per instantiation (not a stream operation:
@@ -643,7 +679,9 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
       if (e != hipSuccess) return (int)e;                                                                             \
       raised = true;                                                                                                  \
     }                                                                                                                 \
-    hipLaunchKernelGGL((k_bwd64<HC, AF, H2>), grid, blk, lds, st, a);                                                 \
+    took = bf_hosts<HC, AF, H2> && h;                                                                                 \
+    hipLaunchKernelGGL((k_bwd64<HC, AF, H2>), BF_GRID(), blk, lds, st, a,                                             \
+                       p4_guest_arg<bf_hosts<HC, AF, H2>>(took ? h : nullptr));                                       \
   }
   if (has2) {
     if (hasc) BF_LAUNCH(true, true, true) else BF_LAUNCH(false, true, true)
@@ -653,8 +691,17 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
     if (aff) BF_LAUNCH(false, true, false) else BF_LAUNCH(false, false, false)
   }
 #undef BF_LAUNCH
+#undef BF_GRID
   DSGCN_LAUNCH_CHECK();
+  if (hosted && took) *hosted = 1;
   return 1;
+}
+
+// 1 = the one-pass backward of a plain-input (Ci -> Co) conv with batch-statistics terms hosts `guest`
+__attribute__((visibility("hidden"))) int dsgcn_bwd64_hosts(int n, int Ci, int Co, int L, const dsgcn_guest_conv* guest) {
+  BfPlan p;
+  P4Hosted hg;
+  return (guest && bf_plan(n, Ci, Co, L, &p) && dsgcn_p4_guest_plan(guest, 1, &hg)) ? 1 : 0;
 }
 
 __attribute__((visibility("hidden"))) int dsgcn_bwd64_tuning(int value) { g_bf_b3 = value; return 0; }

@@ -16,511 +16,38 @@
 // (v_mfma_f32_32x32x2_f32), with PD k-steps of operand prefetch in flight and no barrier inside the K loop (the whole
 // weight block of the workgroup's 32*MT output channels sits in LDS).  Sample base folded into the buffer resource:
 // offsets stay 32-bit for any batch size and channels past K read as zero through the bounds check.
-#include "common.h"
-#include <type_traits>
+#include "pw4_block.h"
 
 namespace {
 
-constexpr int P4_NT = 256;
-constexpr int P4_OOB = 0x7ffffff0;
-constexpr int P4_NT_STORE = 2;                   // cache-policy bits of the output stores: non-temporal (written once, read by a later launch)
+// The hosts: what the shipped DS-STGCN step runs for the `pre` conv.  Forward: the plain-operand narrow conv (blocks 1-7)
+// and its GEMM form (blocks 8-10); data gradient (dz_eff with the batch-statistics terms: MODE 2): the narrow form with two
+// row tiles per wave (blocks 6-7) and both GEMM forms (blocks 8-10).  The guest runs the host's direction (EPI).  The
+// one-pass backward of blocks 1-5: bwd64.hip.
+template <int MT, int NQ, int MODE, int PD, int EPI, bool KSP>
+constexpr bool p4_hosts = !KSP && NQ == 4 && PD == 8 && ((MT == 1 && MODE == 0 && EPI == 0) || (MT == 2 && MODE == 2 && EPI == 1));
+template <int MODE, int EPI, int MT>
+constexpr bool pwg3_hosts = (MODE == 0 && EPI == 0 && MT == 1) || (MODE == 2 && EPI == 1);
 
-struct Pw4Args {
-  const float* b1; const float* b2;                                        // B streams (n, K, L); b2 NULL unless MODE 2
-  const float* ps1; const float* ph1; const float* ps2; const float* ph2;  // per-k affine (NULL = 1 / 0)
-  int relu;
-  const float* w; int w_ldm, w_ldk;                                        // A[m][k] = w[m*w_ldm + k*w_ldk]
-  const float* bias;                                                       // per m, NULL ok
-  float* out;                                                              // (n, M, L)
-  float* partial;                                                          // EPI 0: [ngrp][M][2] or NULL
-  const float* ex1; const float* ex2;                                      // EPI 1: forward operands at (n, M, L)
-  const float* es1; const float* eh1; const float* es2; const float* eh2;
-  int erelu;
-  float* out2; float* ipart;                                               // EPI 1: d x2 or NULL; [ngrp][M][3] or NULL
-  int n, K, M, L, span, WT, cc, Kpad;
-  int Lq;                                                                  // positions per plane rounded up to a multiple of NQ (ragged planes)
-  // (round 6) up to three convs of ONE shape in a launch (blockIdx.y = which): CTR-GCN refines its topology with three
-  // conv4's per unit, each too small to fill the chip (k_pw4 only; the GEMM forms ignore it)
-  int ngroup;
-  struct Grp { const float* b1; const float* ps1; const float* ph1; const float* w; float* out;
-               const float* ex1; const float* es1; const float* eh1; float* ipart; } g[3];
-};
-
-template <int NQ> struct VQ;
-template <> struct VQ<4> { typedef float T __attribute__((ext_vector_type(4))); };
-template <> struct VQ<2> { typedef float T __attribute__((ext_vector_type(2))); };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t p4_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
-}
-
-template <int NQ>
-__device__ __forceinline__ typename VQ<NQ>::T p4_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  if constexpr (NQ == 4) {
-    return __builtin_bit_cast(typename VQ<4>::T, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-  } else {
-    return __builtin_bit_cast(typename VQ<2>::T, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-  }
-}
-
-__device__ __forceinline__ int p4_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// Vector offset of row `row` (rowoff = row * plane bytes) for the epilogue's per-row accesses.  The row depends on the
-// lane's half, so it must NOT go into the scalar offset: hipcc then wraps every access in a readfirstlane loop that runs
-// once per distinct value (two passes with half the lanes each — found in the round-4 disassembly: 35-195 such loops per
-// kernel).  An invalid row / position keeps an out-of-range offset (unsigned sum: no wrap below 2^32).
-__device__ __forceinline__ int p4_rowoff(bool ok, int ooff, int rowoff) {
-  return (int)((unsigned)(ok ? ooff : P4_OOB) + (unsigned)rowoff);
-}
-
-template <int NQ>
-__device__ __forceinline__ void p4_store(typename VQ<NQ>::T v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  if constexpr (NQ == 4) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, P4_NT_STORE);
-  } else {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, P4_NT_STORE);
-  }
-}
-
-// Sum of half of row l31 of a wave's [32][36] LDS tile (lane (half, l31); the caller adds the two halves).
-template <typename ACC>
-__device__ __forceinline__ ACC p4_rowread(const float* Tw, int half, int l31) {
-  const f32x4* rowp = reinterpret_cast<const f32x4*>(Tw + l31 * 36 + half * 16);
-  ACC s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x4 v = rowp[q];
-    s += ((ACC)v.x + (ACC)v.y) + ((ACC)v.z + (ACC)v.w);
-  }
-  return s;
-}
-
-// MODE 0: B' = b1;  1: relu?(b1*s1+h1);  2: relu?(b1*s1+h1 + b2*s2+h2).   EPI 0: forward (bias, statistics);  1: data gradient.
-struct P4Tile { int wave, half, l31, tid, mBase, n, nrem, ds, pos, grp; bool wlive, pok; int skip; };
-
-// Epilogue of a wave's (32*MT rows) x (32*NQ positions, lane-owned runs of NQ) accumulator tile, shared by k_pw4 and
-// k_pwg.  OWNROWS = false: the workgroup's four waves hold the SAME rows at different positions (their per-row sums are
-// added through LDS, one partial row per workgroup); true: the waves hold different rows of one position tile (each wave
-// writes its rows of the workgroup's partial row itself).
-// EPD > 0 (data gradient): the forward operands of the ReLU mask / affine sums are fetched EPD row groups (4 rows each)
-// ahead of the group being finished, X2 saying at compile time whether a second stream exists — left to itself the loop
-// is load -> wait -> compute -> store per group, eight dependent memory round trips per wave (the 15-27 us epilogue of the
-// lab stamps, profiles/r03 / r04).  EPD = 0: the original form (the compiler's own schedule).
-template <int MT, int NQ, int EPI, bool OWNROWS, int NWV = 4, int EPD = 0, bool X2 = true>
-__device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][NQ], float* lds, const P4Tile& t) {
-  typedef typename VQ<NQ>::T vq;
-  const int wave = t.wave, half = t.half, l31 = t.l31, tid = t.tid, mBase = t.mBase, n = t.n, nrem = t.nrem, ds = t.ds,
-            pos = t.pos, grp = t.grp;
-  const bool wlive = t.wlive, pok = t.pok;
-  const int M = a.M, L = a.L, L4 = L * 4;
-  (void)L;
-  const int skip = t.skip;                         // leading elements of the lane's run that the previous run also holds (0
-                                                   // except for the last run of a ragged plane): stored, not summed
-  // Epilogue.  Stores go through a per-sample buffer resource (invalid rows / positions get an out-of-range offset
-  // and are dropped by the bounds check: no branches); per-channel sums through LDS transposes of the wave's tiles.
-  constexpr int NTL = EPI == 0 ? 2 : 3;            // transposed tiles per wave
-  float* Tw = lds + wave * (NTL * 32 * 36);
-  const __amdgpu_buffer_rsrc_t ro = p4_rsrc(a.out + (size_t)n * M * L, wlive ? nrem * M * L4 : 0);
-  const int ooff = pok ? ds * M * L4 + pos * 4 : P4_OOB;
-  if (EPI == 0) {
-    double* Ss = reinterpret_cast<double*>(lds + NWV * NTL * 32 * 36);  // [waves][MT*32][2]
-    const bool stats = a.partial != nullptr;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = p4_row32(r, half);
-        const int co = mBase + 32 * m + row;
-        vq val;
-        float s = 0.f, qq = 0.f;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          val[q] = acc[m][q][r];
-          if (q >= skip) {
-            s += val[q];
-            qq = fmaf(val[q], val[q], qq);
-          }
-        }
-        p4_store<NQ>(val, ro, p4_rowoff(co < M, ooff, co * L4), 0);
-        if (stats) {
-          const bool ok = co < M && pok;
-          Tw[row * 36 + l31] = ok ? s : 0.f;
-          Tw[32 * 36 + row * 36 + l31] = ok ? qq : 0.f;
-        }
-      }
-      if (stats) {
-        wave_lds_sync();
-        double sd = p4_rowread<double>(Tw, half, l31);
-        double qd = p4_rowread<double>(Tw + 32 * 36, half, l31);
-        wave_lds_sync();
-        sd += __shfl_xor(sd, 32, 64);
-        qd += __shfl_xor(qd, 32, 64);
-        if (half == 0) {
-          if constexpr (OWNROWS) {
-            const int co = mBase + 32 * m + l31;
-            if (co < M) {
-              a.partial[((size_t)grp * M + co) * 2 + 0] = (float)sd;
-              a.partial[((size_t)grp * M + co) * 2 + 1] = (float)qd;
-            }
-          } else {
-            Ss[((wave * MT + m) * 32 + l31) * 2 + 0] = sd;
-            Ss[((wave * MT + m) * 32 + l31) * 2 + 1] = qd;
-          }
-        }
-      }
-    }
-    if (stats && !OWNROWS) {
-      __syncthreads();
-      if (tid < 32 * MT) {
-        const int co = mBase + tid;
-        if (co < M) {
-          double s4 = 0.0, q4 = 0.0;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) { s4 += Ss[((w * MT * 32) + tid) * 2]; q4 += Ss[((w * MT * 32) + tid) * 2 + 1]; }
-          a.partial[((size_t)grp * M + co) * 2 + 0] = (float)s4;
-          a.partial[((size_t)grp * M + co) * 2 + 1] = (float)q4;
-        }
-      }
-    }
-  } else {
-    float* Ss = lds + NWV * NTL * 32 * 36;                               // [waves][MT*32][3]
-    f32x4* Es = reinterpret_cast<f32x4*>(Ss + NWV * MT * 32 * 3);        // [MT*32] (s1, h1, s2, h2) of the block's rows
-    const bool need_x = a.erelu || a.es1 != nullptr || a.ex2 != nullptr;
-    const bool has2 = a.ex2 != nullptr;
-    const bool sums = a.ipart != nullptr;
-    if constexpr (OWNROWS) Es += wave * 32 * MT;       // every wave its own rows
-    const int et = OWNROWS ? (tid & 63) : tid;
-    if (et < 32 * MT) {
-      const int ci = mBase + et;
-      f32x4 p = {1.f, 0.f, 1.f, 0.f};
-      if (ci < M) {
-        if (a.es1) { p.x = a.es1[ci]; p.y = a.eh1[ci]; }
-        if (a.es2) { p.z = a.es2[ci]; p.w = a.eh2[ci]; }
-      }
-      Es[et] = p;
-    }
-    __syncthreads();
-    const __amdgpu_buffer_rsrc_t rx1 = p4_rsrc(a.ex1 + (size_t)n * M * L, (wlive && need_x) ? nrem * M * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rx2 = p4_rsrc((has2 ? a.ex2 : a.ex1) + (size_t)n * M * L, (wlive && has2) ? nrem * M * L4 : 0);
-    const __amdgpu_buffer_rsrc_t ro2 = p4_rsrc((a.out2 ? a.out2 : a.out) + (size_t)n * M * L, (wlive && a.out2) ? nrem * M * L4 : 0);
-    constexpr int G = MT * 4;                       // row groups of the wave's tile
-    constexpr int PD = EPD > 0 ? (EPD < G ? EPD : G) : 1;
-    vq xa[PD][4], xb[(X2 || EPD == 0) ? PD : 1][4];
-    auto fetch = [&](int g, int slot) {
-      const int m = g >> 2, rb = (g & 3) * 4;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int ci = mBase + 32 * m + p4_row32(rb + rr, half);
-        xa[slot][rr] = p4_load<NQ>(rx1, p4_rowoff(ci < M, ooff, ci * L4), 0);      // zeros when the input is not needed
-        if constexpr (X2 || EPD == 0) xb[slot][rr] = p4_load<NQ>(rx2, p4_rowoff(ci < M, ooff, ci * L4), 0);
-      }
-    };
-    if constexpr (EPD > 0) {
-#pragma unroll
-      for (int g = 0; g < PD; ++g) fetch(g, g);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const int m = g >> 2, rb = (g & 3) * 4;
-      const int slot = EPD > 0 ? g % PD : 0;
-      if constexpr (EPD == 0) fetch(g, 0);
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int r = rb + rr;
-        const int row = p4_row32(r, half);
-        const int ci = mBase + 32 * m + row;
-        const f32x4 e = Es[32 * m + row];
-        float u0 = 0.f, u1 = 0.f, u2 = 0.f;
-        vq d1, d2;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          float pre = fmaf(xa[slot][rr][q], e.x, e.y);
-          float xbq = 0.f;
-          if constexpr (X2 || EPD == 0) {
-            xbq = xb[slot][rr][q];
-            if (has2) pre += fmaf(xbq, e.z, e.w);
-          }
-          const float dv = (!a.erelu || pre > 0.f) ? acc[m][q][r] : 0.f;
-          d1[q] = dv * e.x;
-          d2[q] = dv * e.z;
-          if (q >= skip) {
-            u0 = fmaf(dv, xa[slot][rr][q], u0);
-            u1 += dv;
-            u2 = fmaf(dv, xbq, u2);
-          }
-        }
-        p4_store<NQ>(d1, ro, p4_rowoff(ci < M, ooff, ci * L4), 0);
-        if constexpr (X2 || EPD == 0) p4_store<NQ>(d2, ro2, p4_rowoff(ci < M, ooff, ci * L4), 0);   // zero-sized resource when there is no dx2
-        if (sums) {
-          const bool ok = ci < M && pok;
-          Tw[row * 36 + l31] = ok ? u0 : 0.f;
-          Tw[32 * 36 + row * 36 + l31] = ok ? u1 : 0.f;
-          Tw[2 * 32 * 36 + row * 36 + l31] = ok ? u2 : 0.f;
-        }
-      }
-      if constexpr (EPD > 0) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (g + PD < G) fetch(g + PD, slot);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if ((g & 3) == 3 && sums) {
-        wave_lds_sync();
-        float s0 = p4_rowread<float>(Tw, half, l31);
-        float s1 = p4_rowread<float>(Tw + 32 * 36, half, l31);
-        float s2 = p4_rowread<float>(Tw + 2 * 32 * 36, half, l31);
-        wave_lds_sync();
-        s0 += __shfl_xor(s0, 32, 64);
-        s1 += __shfl_xor(s1, 32, 64);
-        s2 += __shfl_xor(s2, 32, 64);
-        if (half == 0) {
-          if constexpr (OWNROWS) {
-            const int ci = mBase + 32 * m + l31;
-            if (ci < M) {
-              float* o = a.ipart + ((size_t)grp * M + ci) * 3;
-              o[0] = s0; o[1] = s1; o[2] = s2;
-            }
-          } else {
-            float* q = Ss + ((wave * MT + m) * 32 + l31) * 3;
-            q[0] = s0; q[1] = s1; q[2] = s2;
-          }
-        }
-      }
-    }
-    if (sums && !OWNROWS) {
-      __syncthreads();
-      if (tid < 32 * MT) {
-        const int ci = mBase + tid;
-        if (ci < M) {
-          float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) {
-            const float* q = Ss + ((w * MT * 32) + tid) * 3;
-            v0 += q[0]; v1 += q[1]; v2 += q[2];
-          }
-          float* o = a.ipart + ((size_t)grp * M + ci) * 3;
-          o[0] = v0; o[1] = v1; o[2] = v2;
-        }
-      }
-    }
-  }
-}
-
-// KSP (round 6): the four waves of a workgroup share ONE position tile and split the K loop (whole prefetch rounds each);
-// their accumulators meet in LDS and wave 0 runs the epilogue.  For the tiny-plane launches (the dynamic-adjacency
-// projections: n x 32 positions, K = 128 .. 288): 64 wave tiles x 9 row blocks left the chip at 576 waves each walking
-// K / 2 dependent k-steps (18-21 us for 0.6 GFLOP); split four ways the chain is a quarter as long on four times the waves.
 template <int MT, int NQ, int MODE, int PD, int EPI, bool KSP = false>
-__global__ __launch_bounds__(P4_NT, (MT * NQ >= 6 ? 2 : (MT * NQ >= 4 ? 3 : 4))) void k_pw4(Pw4Args a_) {
-  typedef typename VQ<NQ>::T vq;
+__global__ __launch_bounds__(P4_NT, (MT * NQ >= 6 ? 2 : (MT * NQ >= 4 ? 3 : 4))) void k_pw4(
+    Pw4Args a_, P4GuestArg<p4_hosts<MT, NQ, MODE, PD, EPI, KSP>> guest) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  int bid = blockIdx.x;
+  if constexpr (p4_hosts<MT, NQ, MODE, PD, EPI, KSP>) {
+    if (bid < guest.nblk) {                        // (blocks past the guest's own grid return inside)
+      p4_block<1, 2, 0, 16, EPI>(guest.a, bid, lds);
+      return;
+    }
+    bid -= guest.nblk;
+  }
   Pw4Args a = a_;
   if (a_.ngroup > 1) {                             // grouped launch: this workgroup's conv
     const Pw4Args::Grp& q = a_.g[blockIdx.y];
     a.b1 = q.b1; a.ps1 = q.ps1; a.ph1 = q.ph1; a.w = q.w; a.out = q.out;
     a.ex1 = q.ex1; a.es1 = q.es1; a.eh1 = q.eh1; a.ipart = q.ipart;
   }
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5, l31 = lane & 31;
-  // XCD-aware decode: the cc workgroups that read the same position tiles (one per 32*MT output channels) take
-  // consecutive slots of one XCD (blockIdx % 8), so the re-reads are served by that XCD's L2
-  const int ngrp = KSP ? a.WT : (a.WT + 3) >> 2;
-  const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-  const int cz = slot % a.cc;
-  const int grp = (slot / a.cc) * 8 + xcd;
-  if (grp >= ngrp) return;
-  const int mBase = cz * 32 * MT;
-  const int K = a.K, M = a.M, L = a.L;
-  const int Kpad = a.Kpad, KP = Kpad + 1;
-  float* Ws = lds;                                                       // [32*MT][KP], zero beyond (M, K)
-  f32x4* Ps = reinterpret_cast<f32x4*>(lds + ((32 * MT * KP + 2 + 3) & ~3));  // [Kpad + 2] (s1, h1, s2, h2)
-
-  // Position tiles run over the planes of all samples back to back (a tile may straddle samples: L % NQ == 0, so a lane's
-  // NQ positions never do): no per-sample tail tile — at L = 400 (256 channels, 16 frames) per-sample tiling left
-  // 22 % of the MFMA work on padding.  The wave's buffer resources start at its first sample n; a lane adds ds sample
-  // strides in its vector offset.
-  const int wt = KSP ? grp : grp * 4 + wave;
-  const bool wlive = wt < a.WT;
-  // Ragged planes (L % NQ != 0: K400's 25 x 17 and CTR-GCN's 25 x 25 planes): the tile walks Lq = L rounded up to NQ
-  // positions per plane, and the plane's last run is moved back to END at the plane's end — it overlaps the run before it
-  // by `skip` positions, which both lanes compute and store identically and only the earlier one adds to the per-channel
-  // sums.  No load or store ever leaves the plane (a run reaching into the next row would need a per-element bounds
-  // check: a 16-byte buffer load that straddles the end of its resource returns zeros from its second dword on, measured),
-  // at the price of dword-aligned 16-byte accesses (legal and within 4 % of aligned ones on gfx950:
-  // tools/probes/unaligned_b128.hip).
-  const int Lq = a.Lq;
-  const int g0 = (wlive ? wt : 0) * (32 * NQ);          // < 2^31 (p4_plan)
-  const int n = g0 / Lq;
-  int pos = g0 - n * Lq + l31 * NQ;
-  int ds = 0;
-  while (pos >= Lq) { pos -= Lq; ++ds; }
-  const bool pok = wlive && n + ds < a.n;
-  int skip = 0;
-  if (L - pos < NQ) { skip = NQ - (L - pos); pos = L - NQ; }
-  const int L4 = L * 4;
-  const int nrem = a.n - n < a.span ? a.n - n : a.span;     // samples the wave can touch
-  const int voff = pok ? ds * K * L4 + (half * L + pos) * 4 : P4_OOB;
-  const __amdgpu_buffer_rsrc_t r1 = p4_rsrc(a.b1 + (size_t)n * K * L, wlive ? nrem * K * L4 : 0);
-  const __amdgpu_buffer_rsrc_t r2 = p4_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, (wlive && MODE == 2) ? nrem * K * L4 : 0);
-
-  f32x16 acc[MT][NQ];
-  const float lo = a.relu ? 0.f : -__builtin_inff();
-  // this wave's k-steps: all of them, or (KSP) its share of the Kpad / (2 PD) prefetch rounds
-  const int KS = a.Kpad >> 1;                      // k-steps (2 channels each), a multiple of PD
-  const int KSr = (K + 1) >> 1;                    // k-steps that hold real channels
-  int ks0 = 0, ks1 = KS;
-  if constexpr (KSP) {
-    const int U = KS / PD;
-    ks0 = (U * wave / 4) * PD;
-    ks1 = (U * (wave + 1) / 4) * PD;
-  }
-  const int kse = ks1 < KSr ? ks1 : KSr;           // loads past it: out of range (zeros, no traffic)
-  // ---- weights: global -> registers (all loads of a batch issued together), operand prefetch, then LDS ----
-  constexpr int WB = 16;
-  const bool mfast = a.w_ldm == 1;                 // A = W^T (data gradient): m is the contiguous index of w
-  // element e of this thread: k fast: (r, k) = ((tid>>4) + 16*(e % (2*MT)), (tid&15) + 16*(e / (2*MT)))
-  //                           m fast: (r, k) = ((tid&31) + 32*(e % MT),     (tid>>5) + 8*(e / MT))
-  const int nel = mfast ? (Kpad >> 3) * MT : (Kpad >> 4) * 2 * MT;
-  vq buf1[PD], buf2[MODE == 2 ? PD : 1];
-  for (int e0 = 0; e0 < nel; e0 += WB) {
-    float tmp[WB];
-#pragma unroll
-    for (int j = 0; j < WB; ++j) {
-      const int e = e0 + j;
-      int r, k;
-      if (mfast) { r = (tid & 31) + 32 * (e % MT); k = (tid >> 5) + 8 * (e / MT); }
-      else { r = (tid >> 4) + 16 * (e % (2 * MT)); k = (tid & 15) + 16 * (e / (2 * MT)); }
-      const int m = mBase + r;
-      tmp[j] = (e < nel && m < M && k < K) ? a.w[(size_t)m * a.w_ldm + (size_t)k * a.w_ldk] : 0.f;
-    }
-    if (e0 == 0) {
-#pragma unroll
-      for (int u = 0; u < PD; ++u) {
-        const int s0 = ks0 + u < kse ? 2 * (ks0 + u) * L4 : P4_OOB;   // (channels past K: out of range, zeros)
-        buf1[u] = p4_load<NQ>(r1, voff, s0);
-        if constexpr (MODE == 2) buf2[u] = p4_load<NQ>(r2, voff, s0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < WB; ++j) {
-      const int e = e0 + j;
-      int r, k;
-      if (mfast) { r = (tid & 31) + 32 * (e % MT); k = (tid >> 5) + 8 * (e / MT); }
-      else { r = (tid >> 4) + 16 * (e % (2 * MT)); k = (tid & 15) + 16 * (e / (2 * MT)); }
-      if (e < nel) Ws[r * KP + k] = tmp[j];
-    }
-  }
-  // accumulators start at the bias of their output row (forward), so the epilogue has no per-row loads
-  // (loaded here, with the affine table: after the barrier they were a memory round trip of their own)
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = mBase + 32 * m + p4_row32(i, half);
-      const float b0 = (EPI == 0 && a.bias && row < M && (!KSP || wave == 0)) ? a.bias[row] : 0.f;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) acc[m][q][i] = b0;
-    }
-
-  if (MODE != 0) {
-    for (int i = tid; i < Kpad; i += P4_NT) {
-      f32x4 p = {0.f, 0.f, 0.f, 0.f};
-      if (i < K) {
-        p.x = a.ps1 ? a.ps1[i] : 1.f;
-        p.y = a.ph1 ? a.ph1[i] : 0.f;
-        p.z = a.ps2 ? a.ps2[i] : 1.f;
-        p.w = a.ph2 ? a.ph2[i] : 0.f;
-      }
-      Ps[i] = p;
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                    // raw barrier: the operand prefetch stays in flight
-
-  // Software pipeline, pinned with scheduling barriers.  Step ks: start the LDS reads of step ks+1 (A fragment, affine
-  // row; double-buffered by step parity), apply the affine to the operand loaded PD steps ago, run the MT*NQ MFMAs, then
-  // re-issue that operand buffer's load for step ks+PD (after the MFMAs: the buffer registers are dead by then, so the
-  // load lands in place).  Left to itself the compiler sinks all PD loads to the end of the unrolled body and waits for
-  // the first of them at the top of the next one — or, with the load ahead of the MFMAs, rotates the PD buffers through
-  // v_mov chains behind a vmcnt(0) (profiles/r02: matrix pipe 61 % busy at 256 -> 256 channels).
-  float avb[2][MT];
-  f32x4 pb[2] = {{1.f, 0.f, 1.f, 0.f}, {1.f, 0.f, 1.f, 0.f}};
-#pragma unroll
-  for (int m = 0; m < MT; ++m) avb[0][m] = Ws[(32 * m + l31) * KP + 2 * ks0 + half];
-  if (MODE != 0) pb[0] = Ps[2 * ks0 + half];
-  for (int base = ks0; base < ks1; base += PD) {
-#pragma unroll
-    for (int u = 0; u < PD; ++u) {
-      const int ks = base + u;
-      const int cur = u & 1, nxt = cur ^ 1;                              // PD is even: the parity survives the back edge
-      const int kn = 2 * (ks + 1) + half;                                // last step: reads the LDS pad, never used
-#pragma unroll
-      for (int m = 0; m < MT; ++m) avb[nxt][m] = Ws[(32 * m + l31) * KP + kn];
-      if (MODE != 0) pb[nxt] = Ps[kn];
-      vq b = buf1[u];
-      if (MODE != 0) {
-        const f32x4 p = pb[cur];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          float v = fmaf(b[q], p.x, p.y);
-          if constexpr (MODE == 2) v += fmaf(buf2[u][q], p.z, p.w);
-          b[q] = fmaxf(v, lo);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(avb[cur][m], b[q], acc[m][q], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      // past K: the scalar offset jumps out of the buffer's range (zeros, no traffic: the bounds check covers it)
-      const int sn = ks + PD < kse ? 2 * (ks + PD) * L4 : P4_OOB;
-      buf1[u] = p4_load<NQ>(r1, voff, sn);
-      if constexpr (MODE == 2) buf2[u] = p4_load<NQ>(r2, voff, sn);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  __syncthreads();                                 // every wave is done with Ws / Ps: LDS is reused below
-
-  if constexpr (KSP) {
-    // the K shares meet: waves 1..3 park their accumulators ([wave][register][lane]: conflict-free), wave 0 adds them in
-    // a fixed order (deterministic) and alone runs the epilogue — the others go through it as dead waves (no stores,
-    // zero sums: what a partly empty last workgroup's waves do)
-    float* Rs = lds;                               // [3][MT * NQ * 16][64]
-    if (wave != 0) {
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) Rs[(((wave - 1) * MT * NQ + m * NQ + q) * 16 + i) * 64 + lane] = acc[m][q][i];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int w = 0; w < 3; ++w)
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][q][i] += Rs[((w * MT * NQ + m * NQ + q) * 16 + i) * 64 + lane];
-    }
-    __syncthreads();
-  }
-  const bool elive = KSP ? (wlive && wave == 0) : wlive;
-  const P4Tile tile = {wave, half, l31, tid, mBase, n, nrem, ds, pos, grp, elive, KSP ? (pok && wave == 0) : pok, skip};
-  if constexpr (EPI == 1) {
-    // (operand prefetch of the data-gradient epilogue: two row groups ahead — k_pw4's waves keep their PD operand slots
-    // next to MT*NQ accumulator tiles, there is room for two)
-    if (a.ex2) p4_epilogue<MT, NQ, EPI, false, 4, (MT * NQ >= 8 || (MT == 2 && NQ == 2) ? 1 : 2), true>(a, acc, lds, tile);
-    else p4_epilogue<MT, NQ, EPI, false, 4, (MT * NQ >= 8 || (MT == 2 && NQ == 2) ? 1 : 2), false>(a, acc, lds, tile);
-  } else {
-    p4_epilogue<MT, NQ, EPI, false>(a, acc, lds, tile);
-  }
+  p4_block<MT, NQ, MODE, PD, EPI, KSP>(a, bid, lds);
 }
 
 
@@ -756,9 +283,18 @@ __device__ int g_pwg_stamp_block = 0;            // which workgroup stamps (dsgc
 constexpr int G3_BBUF = 3 * PG_T * PG_RB;          // one activation buffer: [3 terms][128 position slots][RB]
 
 template <int MODE, int EPI, int MT>
-__global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short* __restrict__ wfr, int RT) {
+__global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short* __restrict__ wfr, int RT,
+                                                 P4GuestArg<pwg3_hosts<MODE, EPI, MT>> guest) {
   typedef VQ<4>::T vq;
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  int bid = blockIdx.x;
+  if constexpr (pwg3_hosts<MODE, EPI, MT>) {       // guest blocks (see P4Guest): the leading workgroups
+    if (bid < guest.nblk) {
+      p4_block<1, 2, 0, 16, EPI>(guest.a, bid, lds);
+      return;
+    }
+    bid -= guest.nblk;
+  }
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -769,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
   const int ngrp = a.WT;
-  const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
+  const int id = bid, xcd = id & 7, slot = id >> 3;
   const int cz = slot % a.cc;
   const int grp = (slot / a.cc) * 8 + xcd;
   if (grp >= ngrp) return;
@@ -1142,22 +678,44 @@ bool p4_plan(int n, int K, int M, int L, P4Plan* p, int epi = 0) {
   return true;
 }
 
+// The launch helpers return whether the instantiation they chose TOOK the guest `h` (a host kernel by its compile-time
+// predicate): the entry points report "hosted" from that, so a guest no kernel carried is launched on its own.
+template <int MT, int NQ, int MODE, int PD, int EPI>
+bool p4_launch_one(const Pw4Args& a, const P4Plan& p, hipStream_t st, const P4Hosted* h) {
+  constexpr bool HOST = p4_hosts<MT, NQ, MODE, PD, EPI, false>;
+  const bool hosted = HOST && h;
+  const dim3 grid(p.grid + (hosted ? (unsigned)h->g.nblk : 0u), a.ngroup > 1 ? (unsigned)a.ngroup : 1u), blk(P4_NT);
+  const size_t lds = (hosted && h->lds > p.lds) ? h->lds : p.lds;
+  hipLaunchKernelGGL((k_pw4<MT, NQ, MODE, PD, EPI>), grid, blk, lds, st, a, p4_guest_arg<HOST>(hosted ? h : nullptr));
+  return hosted;
+}
+
 template <int MT, int NQ, int PD>
-void p4_launch_cfg(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStream_t st) {
-  const dim3 grid(p.grid, a.ngroup > 1 ? (unsigned)a.ngroup : 1u), blk(P4_NT);
+bool p4_launch_cfg(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStream_t st, const P4Hosted* h = nullptr) {
   if (epi == 0) {
-    if (mode == 0) hipLaunchKernelGGL((k_pw4<MT, NQ, 0, PD, 0>), grid, blk, p.lds, st, a);
-    else if (mode == 1) hipLaunchKernelGGL((k_pw4<MT, NQ, 1, PD, 0>), grid, blk, p.lds, st, a);
-    else hipLaunchKernelGGL((k_pw4<MT, NQ, 2, PD, 0>), grid, blk, p.lds, st, a);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((k_pw4<MT, NQ, 0, PD, 1>), grid, blk, p.lds, st, a);
-    else hipLaunchKernelGGL((k_pw4<MT, NQ, 2, PD, 1>), grid, blk, p.lds, st, a);
+    if (mode == 0) return p4_launch_one<MT, NQ, 0, PD, 0>(a, p, st, h);
+    if (mode == 1) return p4_launch_one<MT, NQ, 1, PD, 0>(a, p, st, h);
+    return p4_launch_one<MT, NQ, 2, PD, 0>(a, p, st, h);
   }
+  if (mode == 0) return p4_launch_one<MT, NQ, 0, PD, 1>(a, p, st, h);
+  return p4_launch_one<MT, NQ, 2, PD, 1>(a, p, st, h);
 }
 
 // the fragment-image form: MT = 2 (256 rows per workgroup) when the conv has more than 128 output rows
+template <int MODE, int EPI, int MT>
+bool pwg3_launch_one(const Pw4Args& a, const dim3 grid, size_t lds, hipStream_t st, const unsigned short* wfr, int RT,
+                     const P4Hosted* h) {
+  constexpr bool HOST = pwg3_hosts<MODE, EPI, MT>;
+  const bool hosted = HOST && h;
+  const dim3 g(grid.x + (hosted ? (unsigned)h->g.nblk : 0u));
+  if (hosted && h->lds > lds) lds = h->lds;
+  hipLaunchKernelGGL((k_pwg3<MODE, EPI, MT>), g, dim3(256), lds, st, a, wfr, RT, p4_guest_arg<HOST>(hosted ? h : nullptr));
+  return hosted;
+}
+
 template <int MT>
-void pwg3_launch(Pw4Args a, int mode, int epi, const P4Plan& p, const unsigned short* wfr, int Mp, hipStream_t st) {
+bool pwg3_launch(Pw4Args a, int mode, int epi, const P4Plan& p, const unsigned short* wfr, int Mp, hipStream_t st,
+                 const P4Hosted* h = nullptr) {
   constexpr int TA = 128 * MT;
   a.cc = (a.M + TA - 1) / TA;
   const size_t main_b = (size_t)2 * G3_BBUF + (size_t)p.Kpad * 16;
@@ -1171,25 +729,27 @@ void pwg3_launch(Pw4Args a, int mode, int epi, const P4Plan& p, const unsigned s
     for (const void* f : fs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     raised = true;
   }
-  const dim3 grid((unsigned)((p.ngrp + 7) / 8 * 8 * a.cc)), blk(256);
+  const dim3 grid((unsigned)((p.ngrp + 7) / 8 * 8 * a.cc));
   const int RT = Mp / 32;
   if (epi == 0) {
-    if (mode == 0) hipLaunchKernelGGL((k_pwg3<0, 0, MT>), grid, blk, lds, st, a, wfr, RT);
-    else if (mode == 1) hipLaunchKernelGGL((k_pwg3<1, 0, MT>), grid, blk, lds, st, a, wfr, RT);
-    else hipLaunchKernelGGL((k_pwg3<2, 0, MT>), grid, blk, lds, st, a, wfr, RT);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((k_pwg3<0, 1, MT>), grid, blk, lds, st, a, wfr, RT);
-    else hipLaunchKernelGGL((k_pwg3<2, 1, MT>), grid, blk, lds, st, a, wfr, RT);
+    if (mode == 0) return pwg3_launch_one<0, 0, MT>(a, grid, lds, st, wfr, RT, h);
+    if (mode == 1) return pwg3_launch_one<1, 0, MT>(a, grid, lds, st, wfr, RT, h);
+    return pwg3_launch_one<2, 0, MT>(a, grid, lds, st, wfr, RT, h);
   }
+  if (mode == 0) return pwg3_launch_one<0, 1, MT>(a, grid, lds, st, wfr, RT, h);
+  return pwg3_launch_one<2, 1, MT>(a, grid, lds, st, wfr, RT, h);
 }
 
 template <int PD>
 bool p4_launch_pd(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStream_t st, const unsigned short* wsp = nullptr,
-                  int Mp = 0) {
+                  int Mp = 0, const P4Hosted* h = nullptr, bool* took = nullptr) {
   const int key = p.MT * 10 + p.NQ;
+  bool t = false;                                  // the launch carried the guest h
+  if (took) *took = false;
   if (p.gemm && wsp && g_p4_ws == 2) {
-    if (a.M > 128 && !(g_p4_mt1 & (1 << epi))) pwg3_launch<2>(a, mode, epi, p, wsp, Mp, st);
-    else pwg3_launch<1>(a, mode, epi, p, wsp, Mp, st);
+    if (a.M > 128 && !(g_p4_mt1 & (1 << epi))) t = pwg3_launch<2>(a, mode, epi, p, wsp, Mp, st, h);
+    else t = pwg3_launch<1>(a, mode, epi, p, wsp, Mp, st, h);
+    if (took) *took = t;
     return true;
   }
   if (p.gemm) {
@@ -1217,8 +777,8 @@ bool p4_launch_pd(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStrea
   // quads: 16): the other combinations were never launched and compiled to 140-VGPR-spill code objects
   if constexpr (PD == 8) {
     switch (key) {
-      case 14: p4_launch_cfg<1, 4, PD>(a, mode, epi, p, st); return true;
-      case 24: p4_launch_cfg<2, 4, PD>(a, mode, epi, p, st); return true;
+      case 14: t = p4_launch_cfg<1, 4, PD>(a, mode, epi, p, st, h); if (took) *took = t; return true;
+      case 24: t = p4_launch_cfg<2, 4, PD>(a, mode, epi, p, st, h); if (took) *took = t; return true;
     }
   } else {
     switch (key) {
@@ -1231,7 +791,40 @@ bool p4_launch_pd(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStrea
   return false;
 }
 
+// A guest record (dsgcn_jobs.h) -> the arguments, grid and LDS of its body (the arguments dsgcn_p4_fwd / dsgcn_p4_dgrad
+// give the stand-alone launch of the same conv); false unless it is the <1, 2, 0, 16, epi> shape of the dynamic-adjacency
+// projections (plain operand, tiny planes, no K split).
+bool p4_guest_plan(const dsgcn_guest_conv& g, int epi, P4Hosted* h) {
+  if (!g.in || !g.w || !g.out || g.n <= 0 || g.Ci <= 0 || g.Co <= 0 || g.L <= 0) return false;
+  const int K = epi ? g.Co : g.Ci, M = epi ? g.Ci : g.Co;
+  P4Plan p;
+  if (!p4_plan(g.n, K, M, g.L, &p, epi) || p.gemm || p.ksp || p.MT != 1 || p.NQ != 2 || p.PD != 16) return false;
+  if (p.lds > 64 * 1024 || p.grid % 8 != 0) return false;
+  Pw4Args a = {};
+  a.b1 = g.in; a.w = g.w; a.out = g.out;
+  if (epi == 0) { a.w_ldm = g.Ci; a.w_ldk = 1; a.bias = g.bias; }
+  else { a.w_ldm = 1; a.w_ldk = g.Ci; }          // A = W^T; plain forward input: no mask, no affine sums
+  a.n = g.n; a.K = K; a.M = M; a.L = g.L; a.span = p.span; a.WT = p.WT; a.cc = p.cc; a.Kpad = p.Kpad; a.Lq = p.Lq;
+  h->g.a = a;
+  h->g.nblk = (int)p.grid;
+  h->lds = p.lds;
+  return true;
+}
+
+// does the launch of plan `p` take guest blocks?  Forward (epi 0): plain operand on k_pw4<1, 4, 0, 8, 0> or, with the
+// fragment-order weight image, on k_pwg3<0, 0, 1>; data gradient (epi 1): two-stream dz_eff on k_pw4<2, 4, 2, 8, 1> or
+// k_pwg3<2, 1, .>
+bool p4_hosts_guest(const P4Plan& p, int epi, int mode, int M, bool have_ws) {
+  if (mode != (epi ? 2 : 0)) return false;
+  if (p.gemm) return have_ws && g_p4_ws == 2 && (epi == 1 || !(M > 128 && !(g_p4_mt1 & 1)));
+  return !p.ksp && p.MT == (epi ? 2 : 1) && p.NQ == 4 && p.PD == 8;
+}
+
 }  // namespace
+
+__attribute__((visibility("hidden"))) int dsgcn_p4_guest_plan(const dsgcn_guest_conv* g, int epi, P4Hosted* h) {
+  return (g && p4_guest_plan(*g, epi, h)) ? 1 : 0;
+}
 
 // Internal (not part of the C ABI): called by dsgcn_pwconv_fwd / dsgcn_pwconv_dgrad when the shape qualifies
 // (stride 1, even plane size).  Return 1 = launched, 0 = not eligible, <0 / >0 = error codes as everywhere.
@@ -1258,8 +851,10 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_groups(int n, int K, int M, i
 __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const float* s1, const float* h1,
                                                         const float* x2, const float* s2, const float* h2, int relu,
                                                         const float* w, const float* bias, float* z, float* partial,
-                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws) {
+                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws,
+                                                        const dsgcn_guest_conv* guest, int* hosted) {
   P4Plan p;
+  if (hosted) *hosted = 0;
   if (!p4_plan(n, Ci, Co, L, &p)) return 0;
   const WsDims wd = ws_dims(Ci, Co);
   const unsigned short* wsp = static_cast<const unsigned short*>(ws);
@@ -1269,14 +864,32 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const fl
   a.n = n; a.K = Ci; a.M = Co; a.L = L; a.span = p.span; a.WT = p.WT; a.cc = p.cc; a.Kpad = p.Kpad; a.Lq = p.Lq;
   const int mode = x2 ? 2 : ((s1 || relu) ? 1 : 0);
   if (p.ksp && !p.gemm && mode == 0 && !partial) {
-    hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 0, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a);
+    hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 0, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a, P4NoGuest{});
     DSGCN_LAUNCH_CHECK();
     return 1;
   }
-  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 0, p, st, wsp, wd.MpN) : p4_launch_pd<16>(a, mode, 0, p, st, wsp, wd.MpN);
+  // a guest conv rides in the leading workgroups when both sides qualify; otherwise the caller launches it on its own
+  P4Hosted hg;
+  const P4Hosted* h = nullptr;
+  if (guest && p4_hosts_guest(p, 0, mode, Co, wsp != nullptr) && p4_guest_plan(*guest, 0, &hg)) h = &hg;
+  bool took = false;
+  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 0, p, st, wsp, wd.MpN, h, &took)
+                            : p4_launch_pd<16>(a, mode, 0, p, st, wsp, wd.MpN, h, &took);
   if (!ok) return 0;
   DSGCN_LAUNCH_CHECK();
+  if (hosted && took) *hosted = 1;
   return 1;
+}
+
+// 1 = the forward of a plain-operand (Ci -> Co) conv over n planes of L positions hosts `guest` (have_ws: the caller passes
+// the pre-split weight image the shape asks for)
+__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_hosts(int n, int Ci, int Co, int L, int have_ws,
+                                                              const dsgcn_guest_conv* guest) {
+  P4Plan p;
+  P4Hosted hg;
+  if (!guest || !p4_plan(n, Ci, Co, L, &p)) return 0;
+  if (p.ksp && !p.gemm) return 0;
+  return (p4_hosts_guest(p, 0, 0, Co, have_ws != 0) && p4_guest_plan(*guest, 0, &hg)) ? 1 : 0;
 }
 
 // dz_eff = gz + A0 + B0*z (either part may be absent);  x1/x2/s*/h*/relu describe the forward's virtual input.
@@ -1285,8 +898,9 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const 
                                                           const float* w, const float* z, const float* gz,
                                                           const float* A0, const float* B0, float* dx1, float* dx2,
                                                           float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                          const void* ws) {
+                                                          const void* ws, const dsgcn_guest_conv* guest, int* hosted) {
   P4Plan p;
+  if (hosted) *hosted = 0;
   if (!gz) return 0;                               // (a conv whose output has no direct gradient: not on the fast path)
   if (!p4_plan(n, Co, Ci, L, &p, 1)) return 0;
   Pw4Args a = {};
@@ -1298,16 +912,31 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const 
   a.n = n; a.K = Co; a.M = Ci; a.L = L; a.span = p.span; a.WT = p.WT; a.cc = p.cc; a.Kpad = p.Kpad; a.Lq = p.Lq;
   const int mode = A0 ? 2 : 0;
   if (p.ksp && !p.gemm && mode == 0 && !ipart) {
-    hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 1, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a);
+    hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 1, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a, P4NoGuest{});
     DSGCN_LAUNCH_CHECK();
     return 1;
   }
   const WsDims wd = ws_dims(Ci, Co);
   const unsigned short* wsp = ws ? static_cast<const unsigned short*>(ws) + (size_t)3 * wd.MpN * wd.KpN : nullptr;   // the T image
-  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 1, p, st, wsp, wd.MpT) : p4_launch_pd<16>(a, mode, 1, p, st, wsp, wd.MpT);
+  P4Hosted hg;
+  const P4Hosted* h = nullptr;
+  if (guest && p4_hosts_guest(p, 1, mode, Ci, wsp != nullptr) && p4_guest_plan(*guest, 1, &hg)) h = &hg;
+  bool took = false;
+  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 1, p, st, wsp, wd.MpT, h, &took)
+                            : p4_launch_pd<16>(a, mode, 1, p, st, wsp, wd.MpT, h, &took);
   if (!ok) return 0;
   DSGCN_LAUNCH_CHECK();
+  if (hosted && took) *hosted = 1;
   return 1;
+}
+
+// 1 = the data gradient of a (Ci -> Co) conv with batch-statistics terms (A0 / B0) hosts `guest`
+__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_hosts(int n, int Ci, int Co, int L, int have_ws,
+                                                                const dsgcn_guest_conv* guest) {
+  P4Plan p;
+  P4Hosted hg;
+  if (!guest || !p4_plan(n, Co, Ci, L, &p, 1)) return 0;
+  return (p4_hosts_guest(p, 1, 2, Ci, have_ws != 0) && p4_guest_plan(*guest, 1, &hg)) ? 1 : 0;
 }
 
 // Up to three convs of one shape in ONE launch (k_pw4 only: plain / affine operand, no second stream, no statistics).

@@ -1181,7 +1181,10 @@ __attribute__((visibility("hidden"))) int dsgcn_wg2_tuning(int key, int value);
 __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const float* s1, const float* h1,
                                                         const float* x2, const float* s2, const float* h2, int relu,
                                                         const float* w, const float* bias, float* z, float* partial,
-                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws);
+                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws,
+                                                        const dsgcn_guest_conv* guest, int* hosted);
+__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_hosts(int n, int Ci, int Co, int L, int have_ws,
+                                                              const dsgcn_guest_conv* guest);
 __attribute__((visibility("hidden"))) size_t dsgcn_p4_ws_bytes(int n, int Ci, int Co, int L);
 __attribute__((visibility("hidden"))) int dsgcn_bwd64_tuning(int value);
 __attribute__((visibility("hidden"))) int dsgcn_p4_wsplit(const float* w, int Ci, int Co, void* out, hipStream_t st);
@@ -1192,7 +1195,9 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const 
                                                           const float* w, const float* z, const float* gz,
                                                           const float* A0, const float* B0, float* dx1, float* dx2,
                                                           float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                          const void* ws);
+                                                          const void* ws, const dsgcn_guest_conv* guest, int* hosted);
+__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_hosts(int n, int Ci, int Co, int L, int have_ws,
+                                                                const dsgcn_guest_conv* guest);
 
 __attribute__((visibility("hidden"))) int dsgcn_p4_group_ok(int n, int Ci, int Co, int L);
 __attribute__((visibility("hidden"))) int dsgcn_p4_fwd_group(const float* const* x1, const float* const* s1,
@@ -1210,7 +1215,9 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
                                                        const float* s2, const float* h2, int relu, const float* w,
                                                        const float* z, const float* gz, const float* A0, const float* B0,
                                                        float* dx, float* dx2, float* dwp, float* dbp, int pstride,
-                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st);
+                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
+                                                       const dsgcn_guest_conv* guest, int* hosted);
+__attribute__((visibility("hidden"))) int dsgcn_bwd64_hosts(int n, int Ci, int Co, int L, const dsgcn_guest_conv* guest);
 
 // wgrad.hip
 __attribute__((visibility("hidden"))) int dsgcn_wg2_splits(int n, int Ci, int Co, int L);
@@ -1233,6 +1240,12 @@ static int pw_conv_rows(int n, int K, int M, int T, int V, int stride, int which
   }
   return n * ((L + 4 * 32 - 1) / (4 * 32));
 }
+
+// the forward behind dsgcn_pwconv_fwd_ws / _guest.  guest: a conv for the launch to carry (hosted: set to 1 when it did)
+static int pw_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
+                  int relu, const float* w, const float* bias, float* z, float* zaug, float* partial, int n, int Ci,
+                  int Co, int T, int V, int stride, int aug, int stats, const void* ws, const dsgcn_guest_conv* guest,
+                  int* hosted, void* stream);
 
 extern "C" {
 
@@ -1283,6 +1296,49 @@ int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const
                         const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
                         float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
                         const void* ws, void* stream) {
+  return pw_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats, ws, nullptr,
+                nullptr, stream);
+}
+
+// The same launch with a GUEST conv in its leading workgroups (csrc/pw4.hip: P4Guest).  guest NULL: exactly
+// dsgcn_pwconv_fwd_ws.  A pair that is not hosted (the host falls to a first-generation kernel or takes another form than
+// the `pre` conv's, the guest is not a tiny-plane plain conv, LDS) launches the guest on its own from this call: it is
+// never dropped.  *hosted (may be NULL) = 1 when the host's launch carried it, 0 when it went out alone.
+int dsgcn_pwconv_fwd_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                              const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
+                              float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
+                              const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
+  if (hosted) *hosted = 0;
+  if (guest && (!guest->in || !guest->w || !guest->out || guest->n <= 0 || guest->Ci <= 0 || guest->Co <= 0 || guest->L <= 0))
+    return DSGCN_EINVAL;
+  int took = 0;
+  const int rc = pw_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats, ws,
+                        guest, &took, stream);
+  if (rc != 0 || !guest) return rc;
+  if (hosted) *hosted = took;
+  if (took) return 0;
+  return pw_fwd(guest->in, nullptr, nullptr, nullptr, nullptr, nullptr, 0, guest->w, guest->bias, guest->out, nullptr,
+                nullptr, guest->n, guest->Ci, guest->Co, 1, guest->L, 1, 0, 0, nullptr, nullptr, nullptr, stream);
+}
+
+// 1 = the (Ci -> Co) conv of this shape hosts `guest` (with the weight image passed whenever dsgcn_pwconv_wsplit_bytes asks
+// for one), 0 = the guest would go out on its own.  dir 0: dsgcn_pwconv_fwd_ws_guest with a plain operand; dir 1: the
+// backward of a plain-input conv with batch-statistics terms (A0 / B0) — dsgcn_pwconv_bwd_guest where dsgcn_pwconv_bwd_rows
+// is non-zero, dsgcn_pwconv_dgrad_ws_guest otherwise.
+int dsgcn_pwconv_guest_hosted(int dir, int n, int Ci, int Co, int T, int V, int stride, const dsgcn_guest_conv* guest) {
+  if (!guest || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride != 1 || (dir != 0 && dir != 1)) return 0;
+  const int have_ws = (g_pw4 & 3) == 3 && dsgcn_p4_ws_bytes(n, Ci, Co, T * V) != 0;
+  if (dir == 0) return (g_pw4 & 1) ? dsgcn_p4_fwd_hosts(n, Ci, Co, T * V, have_ws, guest) : 0;
+  if ((g_pw4 & 8) && dsgcn_bwd64_splits(n, Ci, Co, T * V) > 0) return dsgcn_bwd64_hosts(n, Ci, Co, T * V, guest);
+  return (g_pw4 & 2) ? dsgcn_p4_dgrad_hosts(n, Ci, Co, T * V, have_ws, guest) : 0;
+}
+
+}  // extern "C"
+
+static int pw_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
+                  int relu, const float* w, const float* bias, float* z, float* zaug, float* partial, int n, int Ci,
+                  int Co, int T, int V, int stride, int aug, int stats, const void* ws, const dsgcn_guest_conv* guest,
+                  int* hosted, void* stream) {
   if (!x1 || !w || !z || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
   if ((aug && !zaug) || (stats && !partial) || (s1 && !h1) || (s2 && !h2)) return DSGCN_EINVAL;
   const int Tout = (T + stride - 1) / stride;
@@ -1297,7 +1353,8 @@ int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const
   const int conv_rows = pw_conv_rows(n, Ci, Co, T, V, stride, 1);
   int fast = 0;
   if (stride == 1 && (g_pw4 & 1)) {
-    fast = dsgcn_p4_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, stats ? partial : nullptr, n, Ci, Co, L, st, ws);
+    fast = dsgcn_p4_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, stats ? partial : nullptr, n, Ci, Co, L, st, ws, guest,
+                        hosted);
     if (fast != 0 && fast != 1) return fast;
   }
   if (!fast) {
@@ -1335,6 +1392,8 @@ int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const
   }
   return 0;
 }
+
+extern "C" {
 
 int dsgcn_pwconv_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                      const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
@@ -1539,11 +1598,59 @@ int dsgcn_pwconv_dgrad(const float* x1, const float* s1, const float* h1, const 
                                V, stride, aug, nullptr, stream);
 }
 
+}  // extern "C"
+
+// the data gradient behind dsgcn_pwconv_dgrad_ws / _guest (guest, hosted: as pw_fwd)
+static int pw_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
+                    int relu, const float* w, const float* z, const float* zaug, const float* gz, const float* gzaug,
+                    const float* A0, const float* B0, float* dx1, float* dx2, float* ipart, int n, int Ci, int Co, int T,
+                    int V, int stride, int aug, const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream);
+
+extern "C" {
+
 int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                           const float* h2, int relu, const float* w, const float* z, const float* zaug,
                           const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
                           float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, const void* ws,
                           void* stream) {
+  return pw_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T, V, stride, aug,
+                  ws, nullptr, nullptr, stream);
+}
+
+// The guest of a backward launch: the data gradient of a small plain conv — guest->in = gz (n, Co, L), guest->out = dx
+// (n, Ci, L), guest->bias unused.  Launched on its own from the same call when the pair is not hosted.
+static int pw_guest_dgrad(const dsgcn_guest_conv* g, void* stream) {
+  // (x1 only has to be non-NULL: a plain conv — no ReLU, no input affine, no second stream — never reads its forward input
+  // in the data gradient, so the record carries none and dx stands in for it)
+  return pw_dgrad(g->out, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g->w, nullptr, nullptr, g->in, nullptr, nullptr,
+                  nullptr, g->out, nullptr, nullptr, g->n, g->Ci, g->Co, 1, g->L, 1, 0, nullptr, nullptr, nullptr, stream);
+}
+static bool pw_guest_ok(const dsgcn_guest_conv* g) {
+  return !g || (g->in && g->w && g->out && g->n > 0 && g->Ci > 0 && g->Co > 0 && g->L > 0);
+}
+
+// dsgcn_pwconv_dgrad_ws with a guest data gradient in its leading workgroups (see dsgcn_pwconv_fwd_ws_guest)
+int dsgcn_pwconv_dgrad_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                                const float* h2, int relu, const float* w, const float* z, const float* zaug,
+                                const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1,
+                                float* dx2, float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug,
+                                const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
+  if (hosted) *hosted = 0;
+  if (!pw_guest_ok(guest)) return DSGCN_EINVAL;
+  int took = 0;
+  const int rc = pw_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T, V,
+                          stride, aug, ws, guest, &took, stream);
+  if (rc != 0 || !guest) return rc;
+  if (hosted) *hosted = took;
+  return took ? 0 : pw_guest_dgrad(guest, stream);
+}
+
+}  // extern "C"
+
+static int pw_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
+                    int relu, const float* w, const float* z, const float* zaug, const float* gz, const float* gzaug,
+                    const float* A0, const float* B0, float* dx1, float* dx2, float* ipart, int n, int Ci, int Co, int T,
+                    int V, int stride, int aug, const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
   if (!x1 || !w || !dx1 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
   if ((A0 && (!B0 || !z)) || (aug && A0 && !zaug) || (x2 && !dx2)) return DSGCN_EINVAL;
   // dsgcn_pwconv_ipart_rows sizes `ipart` for the wide-load plan, which needs gz: a NULL gz would drop to the scalar
@@ -1567,7 +1674,8 @@ int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, con
   a.roll = ((g_pw_roll & 2) && Co % KW == 0 && (Ci & 3) == 0) ? 1 : 0;
   const int L = Tout * V;
   if (stride == 1 && !aug && (g_pw4 & 2)) {
-    const int fast = dsgcn_p4_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, ipart, n, Ci, Co, L, st, ws);
+    const int fast = dsgcn_p4_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, ipart, n, Ci, Co, L, st, ws,
+                                    guest, hosted);
     if (fast == 1) return 0;
     if (fast != 0) return fast;
   }
@@ -1601,6 +1709,8 @@ int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, con
   DSGCN_LAUNCH_CHECK();
   return 0;
 }
+
+extern "C" {
 
 // k-split plan of the weight gradient: returns the number of splits (size of dim 0 of dwp / dbp).
 int dsgcn_pwconv_wgrad_splits(int n, int Ci, int Co, int T, int V, int stride) {
@@ -1757,9 +1867,27 @@ int dsgcn_pwconv_bwd(const float* x1, const float* s1, const float* h1, const fl
   if (!x1 || !w || !gz || !dx1 || !dwp || !dbp || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
   if ((A0 && (!B0 || !z)) || (s1 && !h1) || (s2 && !h2) || (x2 && !dx2) || pstride < Co * Ci) return DSGCN_EINVAL;
   const int rc = dsgcn_bwd64(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, dwp, dbp, pstride, ipart, n, Ci, Co,
-                             T * V, (hipStream_t)stream);
+                             T * V, (hipStream_t)stream, nullptr, nullptr);
   if (rc == 1) return 0;
   return rc == 0 ? DSGCN_EUNSUPPORTED : rc;
+}
+
+// dsgcn_pwconv_bwd with a guest data gradient in its leading workgroups (see dsgcn_pwconv_dgrad_ws_guest)
+int dsgcn_pwconv_bwd_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                           const float* h2, int relu, const float* w, const float* z, const float* gz, const float* A0,
+                           const float* B0, float* dx1, float* dx2, float* ipart, float* dwp, float* dbp, int pstride, int n,
+                           int Ci, int Co, int T, int V, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
+  if (hosted) *hosted = 0;
+  if (!x1 || !w || !gz || !dx1 || !dwp || !dbp || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
+  if ((A0 && (!B0 || !z)) || (s1 && !h1) || (s2 && !h2) || (x2 && !dx2) || pstride < Co * Ci) return DSGCN_EINVAL;
+  if (!pw_guest_ok(guest)) return DSGCN_EINVAL;
+  int took = 0;
+  const int rc = dsgcn_bwd64(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, dwp, dbp, pstride, ipart, n, Ci, Co,
+                             T * V, (hipStream_t)stream, guest, &took);
+  if (rc != 1) return rc == 0 ? DSGCN_EUNSUPPORTED : rc;
+  if (!guest) return 0;
+  if (hosted) *hosted = took;
+  return took ? 0 : pw_guest_dgrad(guest, stream);
 }
 
 }  // extern "C"

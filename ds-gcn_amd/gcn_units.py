@@ -95,17 +95,18 @@ def op_bn(bn, op, count):
     return op(None, None, bn.eps, False)[0], eval_affine(bn)
 
 
-def conv_bn(x1, a1, x2, a2, relu, conv, stride, aug, bn):
+def conv_bn(x1, a1, x2, a2, relu, conv, stride, aug, bn, guest=None):
     """1x1 conv (module ``conv``) of a virtual input followed by BatchNorm ``bn`` as a deferred affine.
-    -> (z, zaug, (scale, shift))"""
+    -> (z, zaug, (scale, shift)).  guest: a small conv for this conv's launch to carry (kernels._proj_guest_request)."""
     ops = kernels.ops()
     n, _, T, V = x1.shape
+    kw = {} if guest is None else dict(guest=guest)
     if _need_stats(bn):
         z, zaug, sc, sh, mean, var = ops.pwconv(x1, a1, x2, a2, relu, conv.weight, conv.bias, stride, aug,
-                                                bn.weight, bn.bias, bn.eps, bn.num_features, True)
+                                                bn.weight, bn.bias, bn.eps, bn.num_features, True, **kw)
         record_running(bn, mean, var, n * z.shape[2] * (V + (1 if aug else 0)))
         return z, zaug, (sc, sh)
-    z, zaug = ops.pwconv(x1, a1, x2, a2, relu, conv.weight, conv.bias, stride, aug)[:2]
+    z, zaug = ops.pwconv(x1, a1, x2, a2, relu, conv.weight, conv.bias, stride, aug, **kw)[:2]
     return z, zaug, eval_affine(bn)
 
 
@@ -253,9 +254,14 @@ class dgphgcn1(nn.Module):
         `down` are Sequential(conv, bn)."""
         return [(self.post, self.bn)]
 
-    def adjacency(self, xbar, host=None):
+    def _proj_operands(self):
+        c1, c2, cs = self.conv1, self.conv2, self.conv1_se
+        return ([c1.weight.flatten(1), c2.weight.flatten(1), cs.weight.flatten(1)], [c1.bias, c2.bias, cs.bias])
+
+    def adjacency(self, xbar, host=None, proj_req=None):
         """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V).  host: a kernels.bn_batch whose waiting
-        finalize jobs K-B's launch carries (shipped flag set only)."""
+        finalize jobs K-B's launch carries (shipped flag set only); proj_req: the projections' request that an earlier
+        launch has carried (kernels._proj_guest_request of the same xbar)."""
         c1, c2 = self.conv1, self.conv2
         if not self._shipped:
             cs = self.conv1_se if self.decompose else None
@@ -270,6 +276,8 @@ class dgphgcn1(nn.Module):
                 self.num_types if self.node_attention else 1, self.edge_num, self.subset_wise)
         cs, el = self.conv1_se, self.edge_linears
         kw = {} if host is None else dict(host=host)
+        if proj_req is not None:
+            kw['proj_req'] = proj_req
         return kernels.ops().dynadj(
             xbar, self.A, self.alpha, self.beta,
             c1.weight.flatten(1), c1.bias, c2.weight.flatten(1), c2.bias, cs.weight.flatten(1), cs.bias,
@@ -290,9 +298,13 @@ class dgphgcn1(nn.Module):
             # `pre` conv first, K-B behind it: K-B (and its projection conv) read nothing of the `pre` BatchNorm, so its
             # finalize rides in K-B's launch as extra workgroups (kernels.bn_batch) instead of a launch of its own between
             # the conv and K-A; the backward mirrors it (K-A's rows -> the coefficient job hosted by K-B's backward)
+            # the projections read only xbar: they ride in the `pre` conv's launch (kernels.PROJ_GUEST)
+            mk = getattr(ops, '_proj_guest_request', None)
+            req = mk(xbar, self.A.shape[-1], *self._proj_operands()) if mk is not None else None
             with batch() as q:
-                zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
-                ahat = self.adjacency(xbar, host=q)
+                zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1],
+                                    guest=req if (req is not None and req.t is not None) else None)
+                ahat = self.adjacency(xbar, host=q, proj_req=req)
             ctxbn = getattr(ap[0], '_dsgcn_bn', None)
             if ctxbn is not None:
                 ctxbn.host = True

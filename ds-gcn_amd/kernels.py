@@ -841,23 +841,130 @@ class _DynAdj(torch.autograd.Function):
         return dproj, dA, dalpha, dbeta, dwe, dbe, None, None, None, None
 
 
-def _kb_projections(xbar, V, weights, biases):
+# ---- the projections as GUEST workgroups of the `pre` conv's launch (csrc/pw4.hip: P4Guest) ------------------------------
+# The projection launch reads only xbar (the previous block's fuse_out wrote it) and its consumer K-B runs behind the `pre`
+# conv anyway (it hosts the `pre` BatchNorm's finalize): nothing but launch order kept its 7-19 us on the serial chain.  The
+# unit prepares the projection's operands BEFORE the `pre` conv (_proj_guest_request) and hands the request to that conv's
+# _PwConv call, whose launch carries the projection in its leading workgroups; _kb_projections then finds the output filled
+# and only records the autograd node.  Bit-identical to the two launches (the guest runs the stand-alone kernel's body).
+#
+# Backward: the projection's data gradient reads dproj (K-B's backward) and its output dxbar is first read by the producer
+# of xbar; the `pre` conv's backward, which autograd runs between the two, needs only K-A's dzp.  The two autograd nodes
+# share a token (_GuestToken): the projection's backward launches its weight gradient as before and PARKS its data gradient
+# on the token with dxbar allocated; the `pre` conv's backward takes the parked job and its launch carries it.
+# Ordering — nothing reads an unfilled dxbar: dxbar leaves the projection's node only through _DgradFence, an identity node
+# on the projection's input whose backward launches a job still parked (the host has not run, or never runs) before it
+# passes the gradient on; a host that runs after the fence finds nothing parked, and a projection whose host has already
+# run launches at once (token.host_done).  So whatever order autograd picks, the gradient is written, on the one stream,
+# ahead of every launch that reads it — the same contract as the _coef_wait queue (a job waits for a hosting launch and is
+# flushed by whoever needs its result first).  That the host normally comes first: once K-B's and the projection's nodes
+# have run, both the `pre` conv's node and the fence are ready, and autograd takes the node created later — the fence is
+# created with the request, ahead of the `pre` conv.
+# Bit 0: forward, bit 1: data gradient.  DSGCN_PROJ_GUEST=0 / tools/step_ab.py py:PROJ_GUEST=0 restore the stand-alone launches.
+PROJ_GUEST = int(_os.environ.get('DSGCN_PROJ_GUEST', '3'))
+# what the guest path did since import (calls, not replays of a captured graph): launches that carried a projection's
+# forward / data gradient (as the library reports it), guests that went out beside their host, data gradients parked, and
+# parked jobs the fence had to launch.  Read by the tests to see that the path is alive.
+PROJ_GUEST_COUNTS = dict(fwd_hosted=0, fwd_alone=0, dgrad_parked=0, dgrad_hosted=0, dgrad_alone=0, dgrad_flushed=0)
+
+
+class _GuestToken:
+    """shared by the autograd nodes of a projection conv and of the conv that hosts it"""
+    __slots__ = ('job', 'host_done')
+
+    def __init__(self):
+        self.job = None             # (native.GuestConv, stand-alone launch) of a parked data gradient
+        self.host_done = False      # the host's backward has run: nothing left to wait for
+
+    def take(self):
+        job, self.job = self.job, None
+        return job
+
+    def flush(self):
+        job = self.take()
+        if job is not None:
+            PROJ_GUEST_COUNTS['dgrad_flushed'] += 1
+            job[1]()
+
+
+class _DgradFence(torch.autograd.Function):
+    """identity on the projection's input; backward: a data gradient still parked on the token goes out before the
+    gradient it writes is passed on"""
+
+    @staticmethod
+    def forward(ctx, x, token):
+        ctx.token = token
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.token.flush()
+        return g, None
+
+
+class ProjGuest:
+    """A projection conv waiting for a hosting launch: operands (x (n, Ci, 1, ld), w (R, Ci), b (R)) and the output slot
+    ``t`` (n, R, 1, ld); ``filled``: a launch has written ``t``; ``token``: where its backward parks the data gradient
+    (None: not parked).  Passed as ``out=`` of the projection's own pwconv call.  ``t`` None: the prepared operands only
+    (a layout the kernels cannot read in place: nothing is hosted, the projection's own call takes them as they are)."""
+    __slots__ = ('t', 'x', 'w', 'b', 'filled', 'token')
+
+    def __init__(self, t, x, w, b, token=None):
+        self.t, self.x, self.w, self.b, self.filled, self.token = t, x, w, b, False, token
+
+    def record(self):
+        g = native.GuestConv(_ptr(self.x), _ptr(self.w), _ptr(self.b), _ptr(self.t), int(self.x.shape[0]),
+                             int(self.x.shape[1]), int(self.w.shape[0]), int(self.x.shape[3]))
+        g._keep = (self.x, self.w, self.b, self.t)
+        return g
+
+
+def _kb_operands(xbar, V, weights, biases):
+    w_all = cat_rows(weights)
+    b_all = cat_rows(biases)
+    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
+    return xpad.unsqueeze(2), w_all, b_all
+
+
+def _proj_guest_request(xbar, V, weights, biases):
+    """-> the projections of ``_kb_projections(xbar, V, weights, biases)`` as a request for a hosting launch (None: the
+    switch is off).  Operands that are not in the layout the kernels read directly give a request without an output slot:
+    the stand-alone call then takes the prepared operands and copies them as before."""
+    if not (PROJ_GUEST & 3):
+        return None
+    x4, w_all, b_all = _kb_operands(xbar, V, weights, biases)
+    for t in (x4, w_all, b_all):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+            return ProjGuest(None, x4, w_all, b_all)
+    token = None
+    if (PROJ_GUEST & 2) and torch.is_grad_enabled() and x4.requires_grad:
+        token = _GuestToken()
+        x4 = _DgradFence.apply(x4, token)
+    proj = torch.empty((x4.shape[0], w_all.shape[0], 1, x4.shape[3]), device=x4.device, dtype=torch.float32)
+    return ProjGuest(proj, x4, w_all, b_all, token)
+
+
+def _kb_projections(xbar, V, weights, biases, req=None):
     """The mean-pooled projections of a K-B front -> proj (n, rows, ld): one K-C launch over the stacked weights on xbar —
     viewed as a (n, Ci, 1, 32) "clip" with the joint rows zero-padded to 32, so that forward, data gradient and weight
     gradient all take the 16-byte-per-lane K-C kernels (an unpadded 25-joint row is odd-sized: it fell to the scalar-load
     kernels, ~35 us per launch for 0.1 GFLOP).  xbar arrives padded from the previous block's fuse_out (want_tmean=32);
-    the first block pads here."""
-    w_all = cat_rows(weights)
-    b_all = cat_rows(biases)
-    xpad = torch.nn.functional.pad(xbar, (0, 32 - V)) if xbar.shape[-1] < 32 else xbar
-    proj = pwconv(xpad.unsqueeze(2), None, None, None, False, w_all, b_all, 1, False)[0]
-    return proj.view(xbar.shape[0], w_all.shape[0], xpad.shape[-1])
+    the first block pads here.  req: the ``_proj_guest_request`` of the same arguments (its operands are reused; when a
+    hosting launch has filled its output, the call here launches nothing)."""
+    if req is not None:
+        x4, w_all, b_all = req.x, req.w, req.b
+    else:
+        x4, w_all, b_all = _kb_operands(xbar, V, weights, biases)
+    slot = req if (req is not None and req.t is not None) else None
+    proj = pwconv(x4, None, None, None, False, w_all, b_all, 1, False, out=slot)[0]
+    return proj.view(xbar.shape[0], w_all.shape[0], x4.shape[-1])
 
 
-def dynadj(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, node_type, edge_type, single_use=True, host=None):
+def dynadj(xbar, A, alpha, beta, w1, b1, w2, b2, wse, bse, we, be, node_type, edge_type, single_use=True, host=None,
+           proj_req=None):
     """Dynamic adjacency: the three projections (conv1 / conv2 / conv1_se, ``_kb_projections``), then K-B reading / writing
-    the padded rows."""
-    proj = _kb_projections(xbar, A.shape[-1], [w1, w2, wse], [b1, b2, bse])
+    the padded rows.  proj_req: ``_proj_guest_request(xbar, V, [w1, w2, wse], [b1, b2, bse])``, handed to an earlier conv."""
+    proj = _kb_projections(xbar, A.shape[-1], [w1, w2, wse], [b1, b2, bse], proj_req)
     # single_use: every parameter passed here is used by this call only in the step (their gradient partials may then join
     # the end-of-backward sum, see param_colsum); dggcn feeds A to two calls and says so
     return _DynAdj.apply(proj, A, alpha, beta, we, be, node_type, edge_type, bool(single_use), host)
@@ -966,9 +1073,12 @@ class _PwConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x1, s1, h1, x2, s2, h2, relu, weight, bias, stride, aug, gamma, beta, eps, n_affine, want_bn,
-                bn=None, out=None):
+                bn=None, out=None, guest=None):
+        """guest: a ``ProjGuest`` this conv's launch carries in its leading workgroups (or launches beside it)."""
         _require_cuda(x1, weight)
         ctx.bn, ctx.bn1, ctx.bn2 = bn, _bn_of(s1), _bn_of(s2)
+        ctx.park = getattr(out, 'token', None)                  # this conv's data gradient may wait there for a host
+        ctx.host_token = getattr(guest, 'token', None)          # ... and this conv's backward is that host
         x1, s1, h1, x2, s2, h2, bias, gamma, beta = [_f32c(t) for t in (x1, s1, h1, x2, s2, h2, bias, gamma, beta)]
         w2 = _f32c(weight.reshape(weight.shape[0], -1))
         n, Ci, T, V = x1.shape
@@ -994,10 +1104,23 @@ class _PwConv(torch.autograd.Function):
         wsb = lib.dsgcn_pwconv_wsplit_bytes(n, Ci, Co, T, V, stride)
         if wsb:
             ws = _wsplit_image(w2, Ci, Co, wsb)
-        rc = lib.dsgcn_pwconv_fwd_ws(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), int(relu), _ptr(w2),
-                                     _ptr(bias), _ptr(z), _ptr(zaug), _ptr(partial), n, Ci, Co, T, V, stride, int(aug),
-                                     int(want_bn), _ptr(ws), _stream())
-        native.check(rc, 'dsgcn_pwconv_fwd_ws')
+        if out is not None and getattr(out, 'filled', False):
+            pass                              # a hosting launch has written z (ProjGuest)
+        elif guest is not None and guest.t is not None and not guest.filled and (PROJ_GUEST & 1):
+            g = guest.record()
+            took = _ct.c_int(0)
+            rc = lib.dsgcn_pwconv_fwd_ws_guest(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), int(relu),
+                                               _ptr(w2), _ptr(bias), _ptr(z), _ptr(zaug), _ptr(partial), n, Ci, Co, T, V,
+                                               stride, int(aug), int(want_bn), _ptr(ws), _ct.addressof(g), _ct.byref(took),
+                                               _stream())
+            native.check(rc, 'dsgcn_pwconv_fwd_ws_guest')
+            PROJ_GUEST_COUNTS['fwd_hosted' if took.value else 'fwd_alone'] += 1
+            guest.filled = True               # hosted or launched beside the host: written either way
+        else:
+            rc = lib.dsgcn_pwconv_fwd_ws(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), int(relu), _ptr(w2),
+                                         _ptr(bias), _ptr(z), _ptr(zaug), _ptr(partial), n, Ci, Co, T, V, stride, int(aug),
+                                         int(want_bn), _ptr(ws), _stream())
+            native.check(rc, 'dsgcn_pwconv_fwd_ws')
         scale = shift = mean = var = None
         count = float(n * Tout * (V + (1 if aug else 0)))
         if want_bn:
@@ -1049,26 +1172,63 @@ class _PwConv(torch.autograd.Function):
         dx1 = torch.empty_like(x1)
         dx2 = torch.empty_like(x2) if x2 is not None else None
         pstride = Co * Ci + Co
+        tok = ctx.host_token
         rows = lib.dsgcn_pwconv_bwd_rows(n, Ci, Co, T, V, stride) if (not aug and gz is not None) else 0
         if rows > 0:
             # narrow conv: data gradient, weight gradient and the input-affine sums in one pass (csrc/bwd64.hip)
             wpart = torch.empty((rows, pstride), device=dev, dtype=torch.float32)
             ipart = (torch.empty((rows, Ci, 3), device=dev, dtype=torch.float32)
                      if (s1 is not None or s2 is not None) else None)
-            rc = lib.dsgcn_pwconv_bwd(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2), _ptr(z),
-                                      _ptr(gz), _ptr(A0), _ptr(B0), _ptr(dx1), _ptr(dx2), _ptr(ipart), wpart.data_ptr(),
-                                      wpart.data_ptr() + 4 * Co * Ci, pstride, n, Ci, Co, T, V, st)
-            native.check(rc, 'dsgcn_pwconv_bwd')
+            parked = tok.take() if tok is not None else None
+            took = _ct.c_int(0)
+            if parked is not None:                          # the projection's data gradient rides in this launch
+                rc = lib.dsgcn_pwconv_bwd_guest(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2),
+                                                _ptr(z), _ptr(gz), _ptr(A0), _ptr(B0), _ptr(dx1), _ptr(dx2), _ptr(ipart),
+                                                wpart.data_ptr(), wpart.data_ptr() + 4 * Co * Ci, pstride, n, Ci, Co, T, V,
+                                                _ct.addressof(parked[0]), _ct.byref(took), st)
+                native.check(rc, 'dsgcn_pwconv_bwd_guest')
+                PROJ_GUEST_COUNTS['dgrad_hosted' if took.value else 'dgrad_alone'] += 1
+            else:
+                rc = lib.dsgcn_pwconv_bwd(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2),
+                                          _ptr(z), _ptr(gz), _ptr(A0), _ptr(B0), _ptr(dx1), _ptr(dx2), _ptr(ipart),
+                                          wpart.data_ptr(), wpart.data_ptr() + 4 * Co * Ci, pstride, n, Ci, Co, T, V, st)
+                native.check(rc, 'dsgcn_pwconv_bwd')
+            if tok is not None:
+                tok.host_done = True
             return _PwConv._finish(wpart, ipart, dx1, dx2, s1, s2, Co, Ci, wshape, has_bias, dgamma, dbeta, gamma,
                                    has_beta, n_affine, ctx.defer_ok, ctx.bn1, ctx.bn2, ctx.sink is not None and bool(ctx.sink))
         ipart = None
         if s1 is not None or s2 is not None:
             rows = lib.dsgcn_pwconv_ipart_rows(n, Ci, Co, T, V, stride)
             ipart = torch.empty((rows, Ci, 3), device=dev, dtype=torch.float32)     # every row is written by dgrad
-        rc = lib.dsgcn_pwconv_dgrad_ws(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2),
-                                       _ptr(z), _ptr(zaug), _ptr(gz), _ptr(gzaug), _ptr(A0), _ptr(B0), _ptr(dx1),
-                                       _ptr(dx2), _ptr(ipart), n, Ci, Co, T, V, stride, aug, _ptr(ws), st)
-        native.check(rc, 'dsgcn_pwconv_dgrad_ws')
+        def dgrad_alone():
+            rc = lib.dsgcn_pwconv_dgrad_ws(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2),
+                                           _ptr(z), _ptr(zaug), _ptr(gz), _ptr(gzaug), _ptr(A0), _ptr(B0), _ptr(dx1),
+                                           _ptr(dx2), _ptr(ipart), n, Ci, Co, T, V, stride, aug, _ptr(ws), _stream())
+            native.check(rc, 'dsgcn_pwconv_dgrad_ws')
+
+        park = ctx.park
+        parked = tok.take() if tok is not None else None
+        took = _ct.c_int(0)
+        if parked is not None:                              # host: the projection's data gradient rides in this launch
+            rc = lib.dsgcn_pwconv_dgrad_ws_guest(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(w2),
+                                                 _ptr(z), _ptr(zaug), _ptr(gz), _ptr(gzaug), _ptr(A0), _ptr(B0), _ptr(dx1),
+                                                 _ptr(dx2), _ptr(ipart), n, Ci, Co, T, V, stride, aug, _ptr(ws),
+                                                 _ct.addressof(parked[0]), _ct.byref(took), st)
+            native.check(rc, 'dsgcn_pwconv_dgrad_ws_guest')
+            PROJ_GUEST_COUNTS['dgrad_hosted' if took.value else 'dgrad_alone'] += 1
+        elif (park is not None and not park.host_done and (PROJ_GUEST & 2) and ipart is None and x2 is None and A0 is None
+              and not aug and stride == 1 and not relu):
+            # guest: a plain conv's data gradient waits on the token for the host's launch (dx1 is allocated; see PROJ_GUEST
+            # for who fills it before anything reads it); the weight gradient below goes out now
+            rec = native.GuestConv(_ptr(gz), _ptr(w2), None, _ptr(dx1), n, Ci, Co, T * V)
+            rec._keep = (gz, w2, dx1)
+            park.job = (rec, dgrad_alone)
+            PROJ_GUEST_COUNTS['dgrad_parked'] += 1
+        else:
+            dgrad_alone()
+        if tok is not None:
+            tok.host_done = True
         # (the weight gradient on a second stream beside the data gradient was measured twice: round 2 17.65 vs 17.68
         # ms/step, round 3 13.33 vs 13.34 — it stays on the one stream)
         splits = lib.dsgcn_pwconv_wgrad_splits(n, Ci, Co, T, V, stride)
@@ -1103,7 +1263,7 @@ class _PwConv(torch.autograd.Function):
                 red = param_colsum(ipart.view(ipart.shape[0], -1), True).view(Ci, 3)
                 ds1, dh1 = red[:, 0], red[:, 1]
             return (dx1, ds1, dh1, dx2, None, None, None, wsum[:Co * Ci].view(wshape), None, None, None, None, None, None,
-                    None, None, None, None)
+                    None, None, None, None, None)
         fed = ipart is not None and (s1 is None or bn1 is not None) and (s2 is None or bn2 is not None)
         if fed and already_fed:
             ipart = None
@@ -1130,7 +1290,7 @@ class _PwConv(torch.autograd.Function):
         if dgamma is not None:
             dgamma = dgamma[:n_affine] if gamma is not None else None
             dbeta = dbeta[:n_affine] if has_beta else None
-        return (dx1, ds1, dh1, dx2, ds2, dh2, None, dw, db, None, None, dgamma, dbeta, None, None, None, None, None)
+        return (dx1, ds1, dh1, dx2, ds2, dh2, None, dw, db, None, None, dgamma, dbeta, None, None, None, None, None, None)
 
 
 class _PwConvGroup(torch.autograd.Function):
@@ -1245,15 +1405,16 @@ class OutSlot:
 
 
 def pwconv(x1, a1, x2, a2, relu, weight, bias, stride=1, aug=False, gamma=None, beta=None, eps=1e-5, n_affine=None,
-           want_bn=False, out=None):
-    """-> (z, zaug, scale, shift, mean, var); scale/shift/mean/var are None unless want_bn."""
+           want_bn=False, out=None, guest=None):
+    """-> (z, zaug, scale, shift, mean, var); scale/shift/mean/var are None unless want_bn.  guest: a ``ProjGuest`` for
+    this conv's launch to carry."""
     s1, h1 = a1 if a1 is not None else (None, None)
     s2, h2 = a2 if a2 is not None else (None, None)
     if n_affine is None:
         n_affine = weight.shape[0] if gamma is not None else 0
     bn = BNCtx() if want_bn else None
     out = _PwConv.apply(x1, s1, h1, x2, s2, h2, bool(relu), weight, bias, int(stride), bool(aug), gamma, beta,
-                        float(eps), int(n_affine), bool(want_bn), bn, out)
+                        float(eps), int(n_affine), bool(want_bn), bn, out, guest)
     if want_bn:
         Tout = out[0].shape[2]
         count = float(x1.shape[0] * Tout * (x1.shape[3] + (1 if aug else 0)))

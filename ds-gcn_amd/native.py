@@ -35,6 +35,13 @@ SIGNATURES = {
     'dsgcn_pwconv_fwd': [c_f] * 6 + [c_int] + [c_f] * 5 + [c_int] * 8 + [c_st],
     'dsgcn_bn_coef_rows': [c_f, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_f, ctypes.c_float, ctypes.c_double, c_int, c_f, c_int, c_st],
     'dsgcn_pwconv_fwd_ws': [c_f] * 6 + [c_int] + [c_f] * 5 + [c_int] * 8 + [c_f, c_st],
+    'dsgcn_pwconv_fwd_ws_guest': [c_f] * 6 + [c_int] + [c_f] * 5 + [c_int] * 8 + [c_f, ctypes.c_void_p,
+                                  ctypes.POINTER(ctypes.c_int), c_st],
+    'dsgcn_pwconv_dgrad_ws_guest': [c_f] * 6 + [c_int] + [c_f] * 10 + [c_int] * 7 + [c_f, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_int), c_st],
+    'dsgcn_pwconv_bwd_guest': [c_f] * 6 + [c_int] + [c_f] * 10 + [c_int] * 6 + [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                               c_st],
+    'dsgcn_pwconv_guest_hosted': [c_int] * 7 + [ctypes.c_void_p],
     'dsgcn_pwconv_wsplit': [c_f, c_int, c_int, c_f, c_st],
     'dsgcn_pwconv_wsplit_multi': [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_int), c_int, c_st],
@@ -180,6 +187,12 @@ class BnCoefJob(ctypes.Structure):
 
 
 BN_JOBS_MAX = 4
+
+
+class GuestConv(ctypes.Structure):
+    """include/dsgcn_jobs.h: dsgcn_guest_conv"""
+    _fields_ = [('inp', ctypes.c_void_p), ('w', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('out', ctypes.c_void_p),
+                ('n', ctypes.c_int), ('Ci', ctypes.c_int), ('Co', ctypes.c_int), ('L', ctypes.c_int)]
 
 
 class Dropout(ctypes.Structure):

@@ -322,6 +322,32 @@ int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const
                         const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
                         float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
                         const void* ws, void* stream);
+/* dsgcn_pwconv_fwd_ws with a GUEST: a small plain conv (dsgcn_jobs.h: dsgcn_guest_conv — the dynamic-adjacency
+ * projections on their (n, Ci, 1, 32) clip) that reads nothing the host writes rides in the leading workgroups of the host's
+ * launch instead of a launch of its own behind it.  Both results are bit-identical to the two separate launches.  A pair
+ * that is not hosted (the host is not a plain-operand stride-1 conv on the wide-load / fragment-image kernels, the guest is
+ * not a tiny-plane plain conv) launches the guest on its own from the same call.  guest NULL: dsgcn_pwconv_fwd_ws.
+ * *hosted (may be NULL): 1 = the host's launch carried the guest, 0 = it went out alone.
+ * Backward: dsgcn_pwconv_dgrad_ws_guest / dsgcn_pwconv_bwd_guest are dsgcn_pwconv_dgrad_ws / dsgcn_pwconv_bwd whose launch
+ * carries the guest's DATA GRADIENT (guest->in = gz (n, Co, L), guest->out = dx (n, Ci, L), guest->bias unused); hosted by
+ * the backward of a plain-input conv with batch-statistics terms (A0 / B0), launched on its own otherwise.
+ * dsgcn_pwconv_guest_hosted: the answer without a launch — dir 0: the forward of a plain-operand conv of this shape, dir 1:
+ * its backward (dsgcn_pwconv_bwd_guest where dsgcn_pwconv_bwd_rows is non-zero, dsgcn_pwconv_dgrad_ws_guest otherwise),
+ * the weight image passed whenever dsgcn_pwconv_wsplit_bytes asks for one. */
+int dsgcn_pwconv_fwd_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                              const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
+                              float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
+                              const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream);
+int dsgcn_pwconv_dgrad_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                                const float* h2, int relu, const float* w, const float* z, const float* zaug,
+                                const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1,
+                                float* dx2, float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug,
+                                const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream);
+int dsgcn_pwconv_bwd_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                           const float* h2, int relu, const float* w, const float* z, const float* gz, const float* A0,
+                           const float* B0, float* dx1, float* dx2, float* ipart, float* dwp, float* dbp, int pstride, int n,
+                           int Ci, int Co, int T, int V, const dsgcn_guest_conv* guest, int* hosted, void* stream);
+int dsgcn_pwconv_guest_hosted(int dir, int n, int Ci, int Co, int T, int V, int stride, const dsgcn_guest_conv* guest);
 int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                           const float* h2, int relu, const float* w, const float* z, const float* zaug,
                           const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,

@@ -71,4 +71,16 @@ typedef struct {
   int Ci, Co, KT, reserved;
 } dsgcn_tsplit_job;
 
+/* A small plain 1x1 conv that rides as GUEST workgroups of another conv's launch (dsgcn_pwconv_fwd_ws_guest, dsgcn.h):
+ * out (n, Co, L) = bias + w (Co, Ci) . in (n, Ci, L).  The dynamic-adjacency projections: L = 32 padded joints.
+ * As the guest of a backward launch (dsgcn_pwconv_dgrad_ws_guest / dsgcn_pwconv_bwd_guest) the record describes the conv's
+ * data gradient: in = gz (n, Co, L), out = dx (n, Ci, L) = w^T . gz, bias unused. */
+typedef struct {
+  const float* in;                 /* forward: (n, Ci, L);  backward: gz (n, Co, L) */
+  const float* w;                  /* (Co, Ci) */
+  const float* bias;               /* (Co) or NULL */
+  float* out;                      /* forward: (n, Co, L);  backward: dx (n, Ci, L) */
+  int n, Ci, Co, L;
+} dsgcn_guest_conv;
+
 #endif
