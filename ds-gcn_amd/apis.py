@@ -351,7 +351,9 @@ class EvalLoop:
 
     @torch.no_grad()
     def predict(self, model, rank, world):
-        """This rank's share of the val scores, in its sampler order."""
+        """This rank's share of the val scores, in its sampler order.  Under ``test_cfg['feat_ext']`` / ``['score_ext']``:
+        one float16 array per video, what ``forward_test`` returns for that video alone (mmcv's ``results.extend(result)``
+        would split that array on its first axis; not reproduced)."""
         if self.engine is not None and self.engine.model is not model:
             raise ValueError('EvalLoop(engine=...): the engine was built over another model')
         n = len(self.source)
@@ -359,6 +361,7 @@ class EvalLoop:
         was_training = model.training
         model.eval()
         part, on_device = [], []
+        ext = model.extraction() if hasattr(model, 'extraction') else None
         # the reference samples val clips in loader worker processes: the test-mode sampler's np.random.seed(255) never
         # touches the TRAINING process's stream.  Here both run in one process, so the stream is put back afterwards.
         rng = np.random.get_state()
@@ -367,12 +370,15 @@ class EvalLoop:
                 kp, _ = self.source.batch(order[b:b + self.batch_size])
                 if self.engine is not None:
                     on_device.append(self.engine(kp))
+                elif ext is not None:                             # forward_test extracts from one video per call
+                    part.extend(model(keypoint=kp[i:i + 1], return_loss=False) for i in range(len(kp)))
                 else:
                     part.extend(model(keypoint=kp, return_loss=False))
         finally:
             np.random.set_state(rng)
         if on_device:
-            part.extend(torch.cat(on_device).cpu().numpy())       # the pass's one device->host copy
+            rows = torch.cat(on_device).cpu().numpy()             # the pass's one device->host copy
+            part.extend((r[None] for r in rows) if ext is not None and ext[0] == 'score' else rows)
         model.train(was_training)
         return part
 
@@ -402,6 +408,8 @@ class EvalLoop:
     def after_train_epoch(self, runner):
         if not self.should_run(runner.epoch):
             return None
+        if hasattr(runner.model, 'extraction') and runner.model.extraction() is not None:
+            raise ValueError("validation scores classes: test_cfg['feat_ext'] / ['score_ext'] belong to test_model")
         self.sync_bn_buffers(runner.model, runner.world)
         part = self.predict(runner.model, runner.rank, runner.world)
         scores = gather_results(part, len(self.source))

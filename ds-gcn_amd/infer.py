@@ -8,7 +8,9 @@ pass (reference: ``RecognizerGCN.forward_test``, pyskl/models/recognizers/recogn
 
     one hipGraph replay per batch shape:  weight images of the wide convs  ->  backbone(x, pool=True)  ->  head_test
 
-and hands back DEVICE tensors: nothing in a call waits for the GPU, the caller reads back when it wants to (``test_model``:
+Under ``test_cfg['feat_ext']`` / ``['score_ext']`` the tail of the graph is ``kernels.feat_ext`` instead (the pooled last
+block when frames and joints are both averaged, the whole activation otherwise), any number of videos per call, each
+pooled by itself.  Either way the engine hands back DEVICE tensors: nothing in a call waits for the GPU, the caller reads back when it wants to (``test_model``:
 once per pass)."""
 import torch
 
@@ -41,7 +43,7 @@ class InferEngine:
 
     def reset(self):
         """Forget every captured graph, static buffer and weight image (after a structural change of the model)."""
-        self._graphs = {}          # (shape, dtype, average_clips) -> (graph, static input, static output)
+        self._graphs = {}          # (shape, dtype, average_clips, extraction) -> (graph, static input, static output)
         self._seen = {}            # same key -> eager calls taken
         self._images.clear()
         self.use_graph = self._want_graph
@@ -56,6 +58,8 @@ class InferEngine:
     # ---- pieces --------------------------------------------------------------------------------------------
     def _forward(self, x):
         model = self.model
+        if model.extraction() is not None:
+            return model.forward_extract(x)
         N, clips, M = x.shape[:3]
         mode = model.test_cfg['average_clips']
         head = model.cls_head
@@ -79,8 +83,11 @@ class InferEngine:
         torch.cuda.synchronize()
         return g, sx, out
 
+    def _key(self, x):
+        return tuple(x.shape), x.dtype, self.model.test_cfg['average_clips'], self.model.extraction()
+
     def _run(self, x):
-        key = (tuple(x.shape), x.dtype, self.model.test_cfg['average_clips'])
+        key = self._key(x)
         if self.use_graph and key not in self._graphs and self._seen.get(key, 0) >= self.warmup_eager:
             try:
                 self._graphs[key] = self._capture(x)
@@ -110,7 +117,8 @@ class InferEngine:
     @torch.no_grad()
     def __call__(self, keypoint):
         """keypoint (N, clips, M, T, V, C) on the device -> DEVICE tensor (N, classes) — (N, clips, classes) when the
-        model's ``test_cfg['average_clips']`` is None.  No host synchronisation."""
+        model's ``test_cfg['average_clips']`` is None; float16 (N, n', m', C | classes, t', v') under ``feat_ext`` /
+        ``score_ext`` (row i: what ``forward_test`` returns for video i alone).  No host synchronisation."""
         if keypoint.dim() != 6:
             raise ValueError(f'InferEngine expects (N, clips, M, T, V, C), got {tuple(keypoint.shape)}')
         if not keypoint.is_cuda:
@@ -128,5 +136,4 @@ class InferEngine:
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
     def graphed(self, keypoint):
-        key = (tuple(keypoint.shape), keypoint.dtype, self.model.test_cfg['average_clips'])
-        return key in self._graphs
+        return self._key(keypoint) in self._graphs

@@ -4,6 +4,10 @@
 * ``model(keypoint=(N,1,M,T,V,C), label=(N,1), return_loss=True)`` -> ``dict(top1_acc, top5_acc, loss_cls)``;
 * ``model(keypoint=(N,clips,M,T,V,C), return_loss=False)`` -> ``np.ndarray (N, classes)``: clip scores averaged as
   probabilities (``test_cfg['average_clips']`` = 'prob' default, 'score', or None for per-clip scores);
+* ``model(keypoint=(1,clips,M,T,V,C), return_loss=False)`` under ``test_cfg['feat_ext']`` / ``['score_ext']``
+  (recognizergcn.py:65-93) -> ``np.float16``: the last block's activation ``(n', m', C, t', v')``, averaged over the axes
+  named in ``test_cfg['pool_opt']`` (letters of n m t v, 'all', 'none'), or with ``score_ext`` ``cls_head.fc_cls`` at every
+  remaining position, ``(1, n', m', classes, t', v')`` — one launch, ``kernels.feat_ext``;
 * ``model.train_step(data_batch, optimizer)`` -> ``dict(loss, losses, log_vars, num_samples)`` (what mmcv's runner
   calls, core/local_runner/epoch_based_sparse_runner.py:33-34).
 
@@ -15,7 +19,7 @@ four ``.item()`` syncs per step on its log scalars, base.py:150-156):
 * ``train_step(..., sync_log_vars=False)``: no collective and no host read at all — ``log_vars`` are rank-local device
   tensors, safe inside a hipGraph capture; ``reduce_log_vars`` averages them over ranks whenever the caller logs.
 
-Necks, feature/score extraction and multi-view test batching are not reached by the skeleton configs and raise."""
+Necks and multi-view test batching (``max_testing_views``) are not reached by the skeleton configs and raise."""
 from collections import OrderedDict
 from itertools import zip_longest
 
@@ -59,9 +63,11 @@ class RecognizerGCN(nn.Module):
         self.cls_head = builder.build_head(cls_head) if cls_head else None
         self.train_cfg = dict(train_cfg or {})
         self.test_cfg = dict(test_cfg or {})
-        for key in ('feat_ext', 'score_ext', 'max_testing_views'):
-            if self.test_cfg.get(key):
-                raise NotImplementedError(f'test_cfg[{key!r}] is outside the hot path')
+        if self.test_cfg.get('max_testing_views'):
+            raise NotImplementedError("test_cfg['max_testing_views'] is outside the hot path")
+        ext = self.extraction()                # (AssertionError on a pool_opt letter outside n m t v, as the reference's)
+        if ext is not None and ext[0] == 'score' and not hasattr(self.cls_head, 'fc_cls'):
+            raise ValueError("test_cfg['score_ext'] projects with cls_head.fc_cls: the model has none")
         mode = self.test_cfg.setdefault('average_clips', 'prob')
         if mode not in ('score', 'prob', None):
             raise ValueError(f'{mode} is not supported. Supported: ["score", "prob", None]')
@@ -109,10 +115,41 @@ class RecognizerGCN(nn.Module):
     val_step = train_step
 
     # ---- inference -----------------------------------------------------------------------------------------
+    def extraction(self):
+        """``None`` when ``test_cfg`` asks for class scores, else ``(mode, pool mask)`` with mode 'score' or 'feat'
+        (``score_ext`` wins when both are set) — read from ``test_cfg`` at every call, as the reference does."""
+        score, feat = self.test_cfg.get('score_ext', False), self.test_cfg.get('feat_ext', False)
+        if not (score or feat):
+            return None
+        return ('score' if score else 'feat'), kernels.parse_pool_opt(self.test_cfg.get('pool_opt', 'all'))
+
+    @torch.no_grad()
+    def forward_extract(self, keypoint, want_fp32=False):
+        """The extraction branch on the device: keypoint (N, clips, M, T, V, C) -> float16 (N, n', m', C | classes, t', v'),
+        every video pooled by itself.  With frames and joints both pooled a backbone that can hand over plane means is asked
+        for those (``backbone(x, pool=True)``): the activation is then never written."""
+        mode, mask = self.extraction()
+        N, clips, M = keypoint.shape[:3]
+        x = keypoint.float().flatten(0, 1)
+        if mask & 12 == 12 and getattr(self.backbone, 'supports_pool', False):
+            feat = self.backbone(x, pool=True)
+        else:
+            feat = self.extract_feat(x)
+        if isinstance(feat, (tuple, list)):
+            feat = torch.cat(feat, dim=2)
+        fc = self.cls_head.fc_cls if mode == 'score' else None
+        return kernels.feat_ext(feat, N, clips, M, mask, None if fc is None else fc.weight, None if fc is None else fc.bias,
+                                want_fp32=want_fp32)
+
     @torch.no_grad()
     def forward_test(self, keypoint):
-        assert self.cls_head is not None
+        assert self.cls_head is not None or self.test_cfg.get('feat_ext', False)
         N, clips = keypoint.shape[:2]
+        ext = self.extraction()
+        if ext is not None:
+            assert N == 1, 'feature / score extraction takes one video per call (InferEngine batches videos)'
+            out = self.forward_extract(keypoint).cpu().numpy()
+            return out if ext[0] == 'score' else out[0]          # (1, n', m', K, t', v') / (n', m', C, t', v')
         feats = self.extract_feat(keypoint.float().flatten(0, 1))
         scores = self.cls_head(feats).view(N, clips, -1)
         mode = self.test_cfg['average_clips']

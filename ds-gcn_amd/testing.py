@@ -32,8 +32,12 @@ test_batch_size.__test__ = False          # (a library function, not a pytest ca
 
 def dump_results(results, out):
     """What ``dataset.dump_results`` writes (datasets/base.py:240-242): the list of per-video score arrays as ``.pkl``
-    (float32 arrays) or ``.json`` (nested lists), in dataset order."""
-    results = [np.asarray(r, dtype=np.float32) for r in results]
+    (float32 arrays) or ``.json`` (nested lists), in dataset order.  Extracted features / score maps (float16 arrays,
+    ``test_cfg['feat_ext']`` / ``['score_ext']``) keep their dtype and go to ``.pkl`` only."""
+    half = any(np.asarray(r).dtype == np.float16 for r in results)
+    if half and os.path.splitext(out)[1].lower() == '.json':
+        raise ValueError(f'dump_results: {out!r}: extracted features / score maps are float16 arrays and are written as .pkl')
+    results = [np.asarray(r) if half else np.asarray(r, dtype=np.float32) for r in results]
     folder = os.path.dirname(os.path.abspath(out))
     os.makedirs(folder, exist_ok=True)
     suffix = os.path.splitext(out)[1].lower()
@@ -49,6 +53,7 @@ def dump_results(results, out):
 
 
 def load_results(path):
+    """The list ``dump_results`` wrote: float32 score arrays; float16 features / score maps come back as float16."""
     suffix = os.path.splitext(path)[1].lower()
     if suffix in ('.pkl', '.pickle'):
         with open(path, 'rb') as f:
@@ -58,7 +63,7 @@ def load_results(path):
             data = json.load(f)
     else:
         raise ValueError(f'load_results: {path!r}: a result file is .pkl or .json')
-    return [np.asarray(r, dtype=np.float32) for r in data]
+    return [r if isinstance(r, np.ndarray) and r.dtype == np.float16 else np.asarray(r, dtype=np.float32) for r in data]
 
 
 def ensemble_results(files_or_lists, weights=None, labels=None, metrics=('top_k_accuracy', 'mean_class_accuracy')):
@@ -91,7 +96,11 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
 
     -> ``dict(results=[...], metrics=OrderedDict | None)``: the scores of every video in dataset order on every rank
     (``(classes,)`` float32 arrays; ``(clips, classes)`` when the model's ``average_clips`` is None, which has no metrics);
-    ``metrics`` on rank 0 only.  ``cfg.evaluation.metric_options`` is honoured.  The numpy RNG state is left as found."""
+    ``metrics`` on rank 0 only.  ``cfg.evaluation.metric_options`` is honoured.  The numpy RNG state is left as found.
+
+    Under ``test_cfg['feat_ext']`` / ``['score_ext']`` ``results`` holds one float16 array per video — what
+    ``forward_test`` returns for that video alone, ``(n', m', C, t', v')`` resp. ``(1, n', m', classes, t', v')`` — and
+    ``metrics`` is None; ``out`` must be a ``.pkl`` (checked before the pass)."""
     rank, world = _rank_world()
     data = _get(cfg, 'data', None) or {}
     if dataset is None:
@@ -103,6 +112,9 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
         dataset = dataset[0]
     if average_clips not in (None, 'prob', 'score'):
         raise ValueError(f'average_clips={average_clips!r}: "prob", "score" or None (keep the model\'s test_cfg)')
+    extraction = model.extraction()
+    if extraction is not None and out is not None and os.path.splitext(out)[1].lower() == '.json':
+        raise ValueError(f'test_model: {out!r}: extracted features / score maps are float16 arrays and are written as .pkl')
     work_dir = _get(cfg, 'work_dir', None)
     if checkpoint is None and work_dir and os.path.exists(os.path.join(work_dir, 'latest.pth')):
         checkpoint = os.path.join(work_dir, 'latest.pth')
@@ -125,7 +137,7 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
                         device=next(model.parameters()).device, engine=engine)
         part = loop.predict(model, rank, world)
         results = gather_results(part, len(loop.source))
-        per_clip = model.test_cfg['average_clips'] is None
+        per_clip = model.test_cfg['average_clips'] is None or extraction is not None
     finally:
         model.test_cfg['average_clips'] = mode_before
         model.train(was_training)

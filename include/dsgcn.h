@@ -651,6 +651,28 @@ int dsgcn_head_target_bwd(const float* dscore, const float* pooled, const float*
 int dsgcn_head_test_fwd(const float* feat, const float* w, const float* b, int N, int clips, int M, int C, int K, int mode,
                         float* clip_score, float* out, void* stream);
 
+/* Feature / score-map extraction at test time (csrc/featext.hip): recognizergcn.py:68-93 under test_cfg['feat_ext'] /
+ * ['score_ext'] — x.mean(axis, keepdim=True) over the axes named in pool_opt, then (score_ext) fc_cls at every remaining
+ * position (einsum('nmctv,oc->nmotv') + bias), then the cast to float16.  ONE launch; the pooled tensor never reaches HBM.
+ *   x (videos*clips*M, C, T, V): the last block's output, clip-major within a video — or its (videos*clips*M, C) plane
+ *   means (dsgcn_fuse_out_pool_fwd) with T = V = 1.
+ *   pool_mask: bit 0 'n' (the clips of ONE video: pooling never crosses videos), bit 1 'm', bit 2 't', bit 3 'v'.
+ *   w == NULL: feature mode, the output channel extent is C (K and b are ignored);  w (K, C): score mode, b (K) or NULL,
+ *   score = sum_c w[k, c] pooled[c] + b[k].
+ *   out32 (float) / out16 (IEEE half) of shape (videos, n', m', C|K, t', v'), a pooled axis having extent 1; either may
+ *   be NULL.  out16 is out32's value rounded to nearest even (overflow to +-inf, subnormals kept).
+ *   Each mean is one fp64 sum over the pooled axes (clip, person, frame, joint nest; whole (T, V) planes: lane-strided
+ *   partial sums + the wave's xor tree) divided once and rounded once to fp32 — equal to the reference's chain of fp32
+ *   means wherever that chain is exact.  The projection: v_mfma_f32_32x32x2_f32 (true fp32, four interleaved accumulators)
+ *   when a video has 32 positions or more, wave dot products with fp64 partial sums below; channels in a fixed order, the
+ *   bias added last.  No atomics: repeated launches are bit-identical.
+ * DSGCN_EINVAL: NULL x, a non-positive size (K only in score mode), both outputs NULL, pool_mask bits outside the four.
+ * DSGCN_EUNSUPPORTED: score mode with C above 512 (the [C][32] pooled tile must fit 64 KB of LDS); more than 2^31 - 1
+ * positions per video, elements per plane or 32-position tiles in the launch; feature mode with more than 65535 channel
+ * slices per tile (32 channels a slice; 4 when whole (T, V) planes are reduced, i.e. C above 262140). */
+int dsgcn_feat_ext_fwd(const float* x, const float* w, const float* b, int videos, int clips, int M, int C, int T, int V,
+                       int K, int pool_mask, float* out32, void* out16, void* stream);
+
 /* Training-mode buffer update of njobs BatchNorm layers in one launch (what F.batch_norm(training=True) does to its
  * buffers, momentum form): running_mean = (1 - m) running_mean + m mean; running_var = (1 - m) running_var + m var *
  * unbias (unbias = count / (count - 1)); num_batches_tracked += 1 (entries may be NULL).  The arrays are HOST arrays of
