@@ -20,7 +20,8 @@ from . import kernels
 from . import pipeline
 from .pipeline import PIPELINES, DATASETS, Compose, PoseDataset, SkeletonStore, SkeletonBatcher, build_dataset
 from .data_parallel import FlatParams, FlatDataParallel, shard_batch
-from .train import FlatSGD, cosine_lr
+from .train import FlatAdam, FlatSGD, build_optimizer, cosine_lr
+from .paramwise import param_rules
 from .checkpoint import load_checkpoint, save_checkpoint, resume, find_resume, fuse_conv_bn
 from .engine import TrainEngine
 from .apis import train_model, EpochRunner, EvalLoop, epoch_indices, evaluate_scores

@@ -29,6 +29,9 @@ micro-iteration and every k-th one an update on the mean of the k gradients (``T
 and the log count micro-iterations as mmcv's ``runner.iter`` does, the last ``max_iters % k`` iterations form a short group
 divided by their own count, and a group that an epoch end cuts short is closed there (checkpoints hold no accumulator).
 
+``optimizer=dict(type='SGD' | 'Adam' | 'AdamW', ..., paramwise_cfg=...)`` is mmcv's ``build_optimizer`` (``train.build_optimizer``,
+``paramwise.py``): per-tensor rates and weight decays, the schedule evaluated once per distinct initial rate.
+
 Not reproduced: TensorBoard logging, multi-optimizer configs.
 """
 import math
@@ -170,16 +173,29 @@ class EpochRunner:
         if self.warmup is not None:
             self.warmup_iters = int(lr_cfg['warmup_iters']) * (self.iters_per_epoch if lr_cfg.get('warmup_by_epoch') else 1)
 
-    def current_lr(self):
-        """The rate of iteration ``self.iter``: the policy's regular rate, scaled by the warm-up rule during the first
+    def current_lr(self, base=None):
+        """The rate of iteration ``self.iter`` for a group whose initial rate is ``base`` (default: the optimizer's
+        ``base_lr``, group 0's — the one mmcv logs): the policy's regular rate, scaled by the warm-up rule during the first
         ``warmup_iters`` iterations (counted from the start of the run: a resumed run continues where it stopped)."""
-        lr = self.regular_lr()
+        lr = self.regular_lr(base)
         if self.warmup is not None and self.iter < self.warmup_iters:
             lr = warmup_lr(lr, self.iter, self.warmup, self.warmup_iters, self.warmup_ratio)
         return lr
 
-    def regular_lr(self):
-        base = self.engine.opt.base_lr
+    def current_lrs(self):
+        """None for an optimizer with one rate; else one rate per group of the optimizer: mmcv's LrUpdaterHook applies
+        ``get_lr(initial_lr)`` and then the warm-up to every param group, which with ``min_lr != 0`` (cosine, or the step
+        policy's floor) is not proportional to the groups' ``lr_mult`` — so the schedule is evaluated per initial rate."""
+        opt = self.engine.opt
+        bases = opt.group_base_lrs if hasattr(type(opt), 'group_base_lrs') else None     # (absent on a stand-in optimizer)
+        if bases is None:
+            return None
+        by_base = {b: self.current_lr(b) for b in set(bases)}
+        return [by_base[b] for b in bases]
+
+    def regular_lr(self, base=None):
+        if base is None:
+            base = self.engine.opt.base_lr
         if self.lr_cfg['policy'] == 'CosineAnnealing':
             return cosine_lr(base, self.iter, self.max_iters, float(self.lr_cfg.get('min_lr', 0) or 0))
         if self.lr_cfg['policy'] in ('step', 'Step'):     # mmcv StepLrUpdaterHook(by_epoch=True): set before each epoch
@@ -196,7 +212,8 @@ class EpochRunner:
             nxt = order[(b + 1) * self.batch_size:(b + 2) * self.batch_size] if b + 1 < self.iters_per_epoch else None
             kp, lb = self.source.batch(idx, nxt)
             lr = self.current_lr()                                    # before_train_iter
-            logs = self.engine.step(kp, lb, lr)                       # run_iter + after_train_iter (OptimizerHook)
+            lrs = self.current_lrs()                                  # (one rate per group under paramwise_cfg / Adam)
+            logs = self.engine.step(kp, lb, lr if lrs is None else lrs)       # run_iter + after_train_iter (OptimizerHook)
             # a replayed hipGraph hands back the SAME static tensors every iteration: keep this iteration's values
             pending.append(({k: v.clone() for k, v in logs.items()}, len(idx)))
             self.iter += 1
@@ -460,7 +477,7 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     """Train ``model`` on ``dataset`` the way the reference's ``train_model`` does for the skeleton configs; returns the
     ``EpochRunner`` (its ``.log`` holds the interval records, ``.engine`` the optimizer state).
 
-    cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer`` (SGD),
+    cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer``,
     ``optimizer_config`` (``grad_clip``; ``type`` + ``cumulative_iters``), ``lr_config`` (policy + warm-up),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
     ``auto_resume``; with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
@@ -470,14 +487,13 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     if isinstance(dataset, list) and len(dataset) == 1:
         dataset = dataset[0]
     opt_cfg = dict(_get(cfg, 'optimizer', None) or dict(type='SGD', lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True))
-    if opt_cfg.pop('type', 'SGD') != 'SGD':
-        raise NotImplementedError('the skeleton configs train with SGD (configs/_init_/lr_schedual.py:11)')
     grad_clip, accumulate = parse_optimizer_config(_get(cfg, 'optimizer_config', None))
     model = model.to(device)
     world = _rank_world()[1]
-    engine = TrainEngine(model, lr=opt_cfg.get('lr', 0.1), momentum=opt_cfg.get('momentum', 0),
-                         weight_decay=opt_cfg.get('weight_decay', 0), nesterov=opt_cfg.get('nesterov', False),
-                         use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip, accumulate=accumulate)
+    # mmcv's build_optimizer(model, cfg.optimizer): SGD | Adam | AdamW with torch's defaults for absent keys, and
+    # paramwise_cfg (train.build_optimizer raises for what is not implemented, naming the key)
+    engine = TrainEngine(model, optimizer=opt_cfg, use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip,
+                         accumulate=accumulate)
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)
     work_dir = _get(cfg, 'work_dir', None)
     runner = EpochRunner(model, engine, source, cfg, work_dir=work_dir, meta=meta, logger=logger)

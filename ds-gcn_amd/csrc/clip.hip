@@ -8,41 +8,14 @@
 //                 coefficient), then runs k_sgd's update (head.hip) on g * coef and writes g * coef back
 // Fixed grids, fixed order, no atomics: the same bits on every run and every box.
 #include "common.h"
+#include "grad_norm.h"
 #include "sgd_update.h"
 
 namespace {
 
-constexpr int GN_NT = 256;
 constexpr int GN_VPT = 8;                          // float4 per thread of a norm slice
 constexpr int GN_SLICE = GN_NT * GN_VPT * 4;       // elements per workgroup: 8192 (32 KB)
 constexpr int SC_VPT = 4;                          // float4 per thread of the update
-
-// INF: max that keeps a NaN (torch's max does);  else: sum
-template <bool INF>
-__device__ __forceinline__ double gn_comb(double a, double b) {
-  if (INF) return (a > b || a != a) ? a : b;
-  return a + b;
-}
-
-template <bool INF>
-__device__ __forceinline__ double gn_term(double a, float x) {
-  const double v = (double)x;
-  if (INF) return gn_comb<true>(a, fabs(v));
-  return fma(v, v, a);                             // v * v is exact in fp64: this is a + v*v rounded once
-}
-
-// all threads get the combination of the 256 values, in the order of a binary LDS tree
-template <bool INF>
-__device__ __forceinline__ double gn_block(double v, double* red, int tid) {
-  red[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = GN_NT / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = gn_comb<INF>(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // thread t of workgroup r takes the float4s t, t + 256, ... of the slice, elements in ascending order
 template <bool INF>
@@ -78,17 +51,9 @@ __global__ __launch_bounds__(GN_NT) void k_sgd_clip(float* __restrict__ p, float
                                                     float mom, float wd, int nesterov, long n4, long n) {
   __shared__ double red[GN_NT];
   const int tid = threadIdx.x;
-  double a = 0.;
   float total;
-  if (inf) {
-    for (long r = tid; r < rows; r += GN_NT) a = gn_comb<true>(a, partial[r]);
-    total = (float)gn_block<true>(a, red, tid);
-  } else {
-    for (long r = tid; r < rows; r += GN_NT) a = gn_comb<false>(a, partial[r]);
-    total = (float)sqrt(gn_block<false>(a, red, tid));
-  }
   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-  const float coef = fminf(1.f, max_norm / (total + 1e-6f));
+  const float coef = gn_clip_coef(partial, rows, inf, max_norm, red, tid, total);
   if (blockIdx.x == 0 && tid == 0) grad_norm[0] = total;
   const float rate = lr[0];
   auto one = [&](float pv, float gv, float& bv) { return sgd_update(pv, gv, bv, buf != nullptr, rate, mom, wd, nesterov); };

@@ -57,6 +57,9 @@ class FlatParams:
                 off += n
         self.numel = total
         self.views = [self.flat_g[off:off + n].view(p.shape) for p, (off, n) in zip(self.params, self.slices)]
+        # called by collect_grads (gather mode) with `p.grad is not None` per tensor, before the grads are re-pointed:
+        # an optimizer that skips parameters without a gradient, as torch does, learns here which ones those are
+        self.grad_observers = []
         self.flat_views = [self.flat_g[off:off + n] for (off, n) in self.slices]
 
     def zero_grad(self):
@@ -78,6 +81,10 @@ class FlatParams:
             raise RuntimeError('FlatParams(gather=True): a gradient still aliases the flat buffer — call zero_grad() '
                                'before every backward (a second backward would accumulate into the views and this '
                                'call would wipe it)')
+        if self.grad_observers:
+            pattern = tuple(p.grad is not None for p in self.params)
+            for observe in self.grad_observers:
+                observe(pattern)
         if self.flat_g.is_cuda:
             # one launch writes the whole buffer: a copy per gradient, zeros where none arrived
             self._pack_cuda([(p.grad, off, n) for p, (off, n) in zip(self.params, self.slices)])
@@ -112,13 +119,16 @@ class FlatParams:
             return dict(host=host, dev=torch.empty_like(host, device=dev), event=None)
 
         if torch.cuda.is_current_stream_capturing():
-            # the slot reserved by an earlier eager call (pinned allocation is not a capturable operation in the
-            # default capture mode); further captures allocate (works under capture_error_mode='thread_local')
-            slot = self.__dict__.pop('_pack_reserved', None) or new_slot()
+            # a slot reserved by an earlier eager call: pinned allocation is not a capturable operation.  Two are kept,
+            # because with accumulate > 1 the micro-iteration's and the stepping iteration's graphs are captured on
+            # consecutive calls, with no eager call between them
+            reserved = self.__dict__.setdefault('_pack_reserved', [])
+            slot = reserved.pop() if reserved else new_slot()
             self.__dict__.setdefault('_pack_graph_slots', []).append(slot)      # alive as long as the graph may replay
             return slot
-        if self.__dict__.get('_pack_reserved') is None:
-            self._pack_reserved = new_slot()
+        reserved = self.__dict__.setdefault('_pack_reserved', [])
+        while len(reserved) < 2:
+            reserved.append(new_slot())
         slots = self.__dict__.setdefault('_pack_slots', [])
         self._pack_next = (getattr(self, '_pack_next', -1) + 1) % self._PACK_SLOTS
         if len(slots) <= self._pack_next:

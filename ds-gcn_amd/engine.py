@@ -20,14 +20,19 @@ import torch.distributed as dist
 
 from . import kernels
 from .data_parallel import FlatDataParallel, FlatParams
-from .train import FlatSGD
+from .train import FlatAdam, FlatSGD, build_optimizer
 
 
 class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
-                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1):
-        """grad_clip: mmcv's ``optimizer_config.grad_clip`` dict (``max_norm``, ``norm_type`` 2 or inf) or None.  The clip
+                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1, optimizer=None):
+        """optimizer: mmcv's ``optimizer`` dict (``type`` 'SGD' | 'Adam' | 'AdamW', ..., ``paramwise_cfg``; see
+        ``train.build_optimizer``) or a ``FlatSGD`` / ``FlatAdam`` built over ``FlatParams(model, gather=True)`` — in place of
+        the keywords lr / momentum / weight_decay / nesterov (and, for a built one, of grad_clip / accumulate, which it
+        carries).  FlatAdam and FlatSGD with per-tensor groups skip the parameters that receive no gradient and learn
+        which ones those are at the first step, which must therefore be eager: ``warmup_eager=0`` raises.
+        grad_clip: mmcv's ``optimizer_config.grad_clip`` dict (``max_norm``, ``norm_type`` 2 or inf) or None.  The clip
         runs with the update, AFTER the all-reduce (the reference's order: backward, DDP average, clip_grads, step): every
         rank holds the same averaged buffer and the norm is reduced in a fixed order, so every rank applies the same
         coefficient without a second collective.  ``step()`` then also returns ``grad_norm`` (before clipping).
@@ -39,10 +44,23 @@ class TrainEngine:
         accumulator — and every k-th one also averages the k gradients, exchanges, clips and updates, at the rate passed
         on THAT call: k micro-batches on one GPU are the reference's k ranks.  ``flush()`` closes a short last group."""
         self.model = model
-        self.flat = FlatParams(model, gather=True)
+        if isinstance(optimizer, (FlatSGD, FlatAdam)):
+            if optimizer.flat.module is not model or not optimizer.flat.gather or not optimizer.capturable:
+                raise ValueError('TrainEngine(optimizer=...): build it with capturable=True over FlatParams(model, gather=True)')
+            self.flat = optimizer.flat
+        else:
+            self.flat = FlatParams(model, gather=True)
         self.dp = FlatDataParallel(self.flat, process_group)
-        self.opt = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                           capturable=True, grad_clip=grad_clip, accumulate=accumulate)
+        if isinstance(optimizer, (FlatSGD, FlatAdam)):
+            self.opt = optimizer
+        elif optimizer is not None:
+            self.opt = build_optimizer(self.flat, optimizer, grad_clip=grad_clip, accumulate=accumulate)
+        else:
+            self.opt = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                               capturable=True, grad_clip=grad_clip, accumulate=accumulate)
+        if getattr(self.opt, 'table', None) is not None and bool(use_graph) and warmup_eager < 1:
+            raise ValueError(f'{type(self.opt).__name__} with per-tensor groups needs warmup_eager >= 1: the first step runs '
+                             'eagerly, the parameters that receive no gradient are marked there')
         self.accumulate = self.opt.accumulate
         self.pending = 0           # gradients in the accumulator: micro-iterations since the last update
         self.use_graph = bool(use_graph) and self.flat.flat_p.is_cuda

@@ -164,6 +164,19 @@ SIGNATURES = {
                             ctypes.c_float, c_int, ctypes.c_longlong, c_st],
     'dsgcn_grad_accum': [c_f, c_f, ctypes.c_longlong, c_st],
     'dsgcn_grad_accum_finish': [c_f, c_f, c_f, ctypes.c_longlong, c_st],
+    'dsgcn_optim_chunks': [ctypes.c_longlong],
+    'dsgcn_optim_table': [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_int, ctypes.c_longlong,
+                          ctypes.c_void_p],                           # HOST pointers
+    'dsgcn_sgd_group_step': [c_f, c_f, c_f, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_float,
+                             c_int, ctypes.c_longlong, c_st],
+    'dsgcn_sgd_group_step_clip': [c_f, c_f, c_f, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                  ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_float, c_int,
+                                  ctypes.c_longlong, c_st],
+    'dsgcn_adam_step': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                        ctypes.c_double, ctypes.c_double, ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_adam_step_clip': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                             ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_double, ctypes.c_double,
+                             ctypes.c_float, c_int, ctypes.c_longlong, c_st],
     'dsgcn_bn_running_multi': [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
                                ctypes.POINTER(ctypes.c_float), c_int, c_st],
 }

@@ -737,6 +737,55 @@ int dsgcn_sgd_step_clip(float* p, float* g, float* buf, const float* lr, const d
 int dsgcn_grad_accum(float* acc, const float* g, long long n, void* stream);
 int dsgcn_grad_accum_finish(float* acc, float* g, const float* factor, long long n, void* stream);
 
+/* Optimizer updates with a rate and a weight decay per parameter tensor (mmcv's build_optimizer with paramwise_cfg) and
+ * torch.optim.Adam / AdamW, over the unpadded flat fp32 buffers of n elements (csrc/optim.hip).  One launch per update
+ * whatever the number of tensors and groups; the *_clip forms follow dsgcn_grad_norm_partials (two launches) and treat
+ * partial / rows / norm_type / max_norm / grad_norm_out exactly as dsgcn_sgd_step_clip does: the norm is global over all
+ * groups, g * coef is written back to every element of g, and coef == 1 gives the bits of the unclipped form.
+ *
+ * The table (int32, device memory, uploaded once):
+ *   ends[ntens]   ascending end offsets of the parameter tensors in the flat buffer, ends[ntens - 1] == n.  Boundaries may
+ *                 fall anywhere (inside a 16-byte vector, on a workgroup's chunk edge; one-element tensors).
+ *   group[ntens]  the tensor's group id in [0, groups), or DSGCN_OPTIM_SKIP: its elements of p and of the optimizer state
+ *                 are left untouched bit for bit (a parameter whose .grad is None: torch skips it).
+ *   first[chunks + 1]  first[c] = the tensor holding element min(c * 4096, n - 1): workgroup c updates the 4096 elements
+ *                 from c * 4096 on and searches the tensors first[c] .. first[c + 1] only.
+ *   lr[groups], wd[groups]  fp64 (the Python floats of torch's param groups); the host rewrites lr per iteration, a
+ *                 captured launch follows.  groups <= 256.
+ * dsgcn_optim_chunks  number of workgroups of an update over n elements (n / 4096 + 1) = number of Adam step counters.
+ * dsgcn_optim_table   HOST pointers, no launch: checks a table (ends strictly ascending from above 0 to n, ids in
+ *                     [-1, groups), every wd finite and >= 0) and fills first[chunks + 1].
+ *
+ * dsgcn_sgd_group_step[_clip]  dsgcn_sgd_step[_clip]'s update with rate (float)lr[group] and decay (float)wd[group] per
+ *                     element: with one group it is bit-identical to them.  buf may be NULL when momentum == 0.
+ * dsgcn_adam_step[_clip]  torch's single-tensor Adam (amsgrad=False, maximize=False), g after the optional clip:
+ *                       decoupled == 0 (Adam):  g += wd p            decoupled != 0 (AdamW):  p *= (float)(1 - lr wd)
+ *                       m = m + (1 - beta1)(g - m);   v = beta2 v + ((1 - beta2) g) g;
+ *                       p -= ((float)(lr / bc1) m) / (sqrt(v) / (float)sqrt(bc2) + eps),   bc_k = 1 - beta_k^t in fp64,
+ *                     every operation rounded on its own.  t = step[c] + 1 in workgroup c, which then stores t to step[c]:
+ *                     step holds `chunks` int32 counters, all equal to the number of updates so far (zero them at
+ *                     construction); the launch advances them itself, so a replayed hipGraph counts on.
+ * DSGCN_EINVAL: a NULL or misaligned pointer (p, g, buf, m, v: 16 bytes; lr, wd, partial: 8; the rest: 4), n <= 0,
+ * ntens <= 0 or > n, groups <= 0, momentum < 0 or momentum != 0 without buf, a beta outside [0, 1), eps < 0, max_norm < 0,
+ * norm_type other than 0 and 2, rows <= 0.  DSGCN_EUNSUPPORTED: groups > 256, n >= 2^31. */
+#define DSGCN_OPTIM_SKIP (-1)
+int dsgcn_optim_chunks(long long n);
+int dsgcn_optim_table(const int* ends, const int* group, int ntens, const double* wd, int groups, long long n, int* first);
+int dsgcn_sgd_group_step(float* p, float* g, float* buf, const int* ends, const int* group, const int* first, int ntens,
+                         const double* lr, const double* wd, int groups, float momentum, int nesterov, long long n,
+                         void* stream);
+int dsgcn_sgd_group_step_clip(float* p, float* g, float* buf, const int* ends, const int* group, const int* first, int ntens,
+                              const double* lr, const double* wd, int groups, const double* partial, int rows,
+                              int norm_type, float max_norm, float* grad_norm_out, float momentum, int nesterov,
+                              long long n, void* stream);
+int dsgcn_adam_step(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group, const int* first,
+                    int ntens, const double* lr, const double* wd, int groups, double beta1, double beta2, float eps,
+                    int decoupled, long long n, void* stream);
+int dsgcn_adam_step_clip(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
+                         const int* first, int ntens, const double* lr, const double* wd, int groups, const double* partial,
+                         int rows, int norm_type, float max_norm, float* grad_norm_out, double beta1, double beta2,
+                         float eps, int decoupled, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
