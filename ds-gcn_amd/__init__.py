@@ -17,6 +17,7 @@ from .tcn_units import dgmstcn, mstcn, msmlp, unitmlp, unit_tcn, MSTCN
 from .backbones import DGSTGCN, STGCN, CTRGCN, AAGCN, DGBlock, STGCNBlock, CTRGCNBlock, AAGCNBlock
 from .recognizers import RecognizerGCN, reduce_log_vars, gather_results
 from . import kernels
+from .kernels import set_matmul_precision, get_matmul_precision, matmul_precision
 from . import pipeline
 from .pipeline import PIPELINES, DATASETS, Compose, PoseDataset, SkeletonStore, SkeletonBatcher, build_dataset
 from .data_parallel import FlatParams, FlatDataParallel, shard_batch

@@ -327,6 +327,7 @@ class EvalLoop:
         self.best_score = self.best_ckpt = None
         self.broadcast_bn_buffer = bool(broadcast_bn_buffer)
         self.engine = engine
+        self.matmul_precision = None      # a level for the eager passes of predict() (train_model sets the run's)
         self.results = []
 
     def restore(self, meta):
@@ -373,6 +374,13 @@ class EvalLoop:
         would split that array on its first axis; not reproduced)."""
         if self.engine is not None and self.engine.model is not model:
             raise ValueError('EvalLoop(engine=...): the engine was built over another model')
+        if self.matmul_precision is not None and self.engine is None:
+            from . import kernels
+            with kernels.matmul_precision(self.matmul_precision):
+                return self._predict(model, rank, world)
+        return self._predict(model, rank, world)
+
+    def _predict(self, model, rank, world):
         n = len(self.source)
         order = epoch_indices(n, 0, 0, rank, world, shuffle=False)
         was_training = model.training
@@ -480,7 +488,8 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer``,
     ``optimizer_config`` (``grad_clip``; ``type`` + ``cumulative_iters``), ``lr_config`` (policy + warm-up),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
-    ``auto_resume``; with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
+    ``auto_resume``, ``matmul_precision`` ('highest' | 'high': the run's training steps and validation passes; absent = the
+    process level, ``kernels.set_matmul_precision``); with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
     overrides ``data.val``: a map-style dataset or a (``SkeletonStore``, ``SkeletonBatcher``) pair built for the val
     pipeline).  ``runner.evaluator.results`` holds the evaluation records.  ``prefetch``: plan the next batch of a resident
     store on a feeder thread while the device runs the current step (same RNG stream either way)."""
@@ -493,7 +502,9 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     # mmcv's build_optimizer(model, cfg.optimizer): SGD | Adam | AdamW with torch's defaults for absent keys, and
     # paramwise_cfg (train.build_optimizer raises for what is not implemented, naming the key)
     engine = TrainEngine(model, optimizer=opt_cfg, use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip,
-                         accumulate=accumulate)
+                         accumulate=accumulate, matmul_precision=_get(cfg, 'matmul_precision', None))
+    if logger is not None:
+        logger.info('matmul precision: %s', engine.matmul_precision)
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)
     work_dir = _get(cfg, 'work_dir', None)
     runner = EpochRunner(model, engine, source, cfg, work_dir=work_dir, meta=meta, logger=logger)
@@ -509,6 +520,7 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
         eval_cfg = dict(_get(cfg, 'evaluation', None) or {})
         runner.evaluator = EvalLoop(val_dataset, batch_size=vloader['videos_per_gpu'],
                                     device=next(model.parameters()).device, **eval_cfg)
+        runner.evaluator.matmul_precision = engine.matmul_precision
     ckpt = find_resume(work_dir, _get(cfg, 'resume_from', None), bool(_get(cfg, 'auto_resume', False))) if work_dir else \
         _get(cfg, 'resume_from', None)
     if ckpt:

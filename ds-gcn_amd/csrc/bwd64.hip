@@ -706,6 +706,13 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64_hosts(int n, int Ci, int C
 
 __attribute__((visibility("hidden"))) int dsgcn_bwd64_tuning(int value) { g_bf_b3 = value; return 0; }
 
+// bf16 products per fp32 product of the one-pass backward of a single-stream conv of this shape: k_bwd64b stays on six
+// terms at every matmul precision level (it runs at the copy rate: nothing to buy); 0 = its fp32 MFMA form
+__attribute__((visibility("hidden"))) int dsgcn_bwd64_terms(int n, int Ci, int Co, int L) {
+  BfPlan p;
+  return (bf_plan(n, Ci, Co, L, &p) && g_bf_b3 && Ci >= 16) ? 6 : 0;
+}
+
 #ifdef DSGCN_LAB
 extern "C" int dsgcn_bwd64_phases(long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bf_stamp), sizeof(long long) * 64);

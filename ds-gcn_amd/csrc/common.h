@@ -16,6 +16,10 @@
     if (e__ != hipSuccess) return (int)e__;       \
   } while (0)
 
+// Matmul precision level (include/dsgcn.h: dsgcn_set_matmul_precision): 0 = highest (six bf16 products per fp32 product),
+// 1 = high (three).  One atomic in version.hip, read by the HOST launch code only — never by a kernel.
+__attribute__((visibility("hidden"))) int dsgcn_precision_level();
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -86,6 +90,12 @@ __device__ __forceinline__ void plane_to_lds(const float* __restrict__ src, floa
 // accumulator), the dropped ones are below 2^-24 |a||b| — the rounding class of the fp32 MFMA it replaces, at 2.7x its
 // rate: six v_mfma_f32_32x32x16_bf16 (32 cycles each) per 16 channels against eight v_mfma_f32_32x32x2_f32 (64 cycles).
 // Non-finite inputs give NaN where fp32 would keep an infinity (inf - inf in the residue).
+//
+// Two-term form (matmul precision 'high', opt-in): only x0 and x1 are formed (each cast is off by at most 2^-8 relative,
+// so |x - x0 - x1| <= 2^-16 |x|) and the three products with i + j <= 1 are kept: a0*b0 + a0*b1 + a1*b0.  The dropped part
+// of a*b is at most 3 * 2^-16 |a||b| (4.6e-5; about 5e-6 of sum |a||b| on random data: between TF32 and fp32) for half the
+// MFMAs, two thirds of the split's VALU work and two thirds of the LDS traffic.  The kernels that offer it are second
+// instantiations (term count 2) of the bodies of the three-term ones.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -105,4 +115,34 @@ __device__ __forceinline__ void b3_split(float a, float b, unsigned& p0, unsigne
   a -= __builtin_bit_cast(float, p1 << 16);
   b -= __builtin_bit_cast(float, p1 & 0xffff0000u);
   p2 = b3_pack(a, b);
+}
+
+// the first two terms only (the two-term form above)
+__device__ __forceinline__ void b2_split(float a, float b, unsigned& p0, unsigned& p1) {
+  p0 = b3_pack(a, b);
+  a -= __builtin_bit_cast(float, p0 << 16);
+  b -= __builtin_bit_cast(float, p0 & 0xffff0000u);
+  p1 = b3_pack(a, b);
+}
+
+// NT = 3: the three terms (p2 written); NT = 2: the first two (p2 untouched)
+template <int NT>
+__device__ __forceinline__ void bn_split(float a, float b, unsigned& p0, unsigned& p1, unsigned& p2) {
+  if constexpr (NT == 3) b3_split(a, b, p0, p1, p2);
+  else b2_split(a, b, p0, p1);
+}
+
+// the products of one 16-deep k-step on the terms' fragments: six (NT = 3: i + j <= 2) or three (NT = 2: i + j <= 1),
+// smallest first
+template <int NT>
+__device__ __forceinline__ f32x16 bn_products(const bf16x8 (&a)[NT], const bf16x8 (&b)[NT], f32x16 c) {
+  if constexpr (NT == 3) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+  }
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+  return c;
 }

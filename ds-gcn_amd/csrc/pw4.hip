@@ -282,19 +282,12 @@ __device__ int g_pwg_stamp_block = 0;            // which workgroup stamps (dsgc
 // activation prefetch distance is one chunk by construction (a second register set would buy nothing).
 constexpr int G3_BBUF = 3 * PG_T * PG_RB;          // one activation buffer: [3 terms][128 position slots][RB]
 
-template <int MODE, int EPI, int MT>
-__global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short* __restrict__ wfr, int RT,
-                                                 P4GuestArg<pwg3_hosts<MODE, EPI, MT>> guest) {
+// The body is templated on the term count NT: 3 = the six products (k_pwg3), 2 = the three products of matmul precision
+// 'high' (k_pwg3h: common.h, two-term form).  NT = 2 reads terms 0 and 1 of the SAME weight image and LDS layout (term 2's
+// plane / rows are simply not touched): two split steps, two LDS rows and two A fragments per value instead of three.
+template <int MODE, int EPI, int MT, int NT>
+__device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short* __restrict__ wfr, int RT, int bid, float* lds) {
   typedef VQ<4>::T vq;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  int bid = blockIdx.x;
-  if constexpr (pwg3_hosts<MODE, EPI, MT>) {       // guest blocks (see P4Guest): the leading workgroups
-    if (bid < guest.nblk) {
-      p4_block<1, 2, 0, 16, EPI>(guest.a, bid, lds);
-      return;
-    }
-    bid -= guest.nblk;
-  }
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -342,12 +335,12 @@ __global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short
   const __amdgpu_buffer_rsrc_t rw = p4_rsrc(wfr, 3 * RT * KS * 1024);
   // (the fragment's KB index is wave-uniform: it rides in the scalar offset, one vector register addresses all of them)
   const int fragA0 = __builtin_amdgcn_readfirstlane(mBase >> 5);
-  u32x4v af0[MT][3], af1[MT][3];                   // k-steps of even / odd index
-  auto issueA = [&](int ks, u32x4v (&af)[MT][3]) {
+  u32x4v af0[MT][NT], af1[MT][NT];                 // k-steps of even / odd index
+  auto issueA = [&](int ks, u32x4v (&af)[MT][NT]) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         af[m][t] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, ((t * RT + fragA0 + m) * KS + ks) * 1024, 0));
   };
   const float lo = a.relu ? 0.f : -__builtin_inff();
@@ -369,15 +362,15 @@ __global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short
       }
     }
   };
-  // position sub-tile q of the (combined) chunk -> its three term rows of buffer `dst`
+  // position sub-tile q of the (combined) chunk -> its NT term rows of buffer `dst`
   auto commit_q = [&](char* dst, int q) {
     char* base = dst + (32 * q + l31) * PG_RB + cg * 8;
     unsigned p0, p1, p2, q0, q1, q2;
-    b3_split(bw[0][q], bw[1][q], p0, p1, p2);
-    b3_split(bw[2][q], bw[3][q], q0, q1, q2);
+    bn_split<NT>(bw[0][q], bw[1][q], p0, p1, p2);
+    bn_split<NT>(bw[2][q], bw[3][q], q0, q1, q2);
     *reinterpret_cast<u32x2v*>(base) = u32x2v{p0, q0};
     *reinterpret_cast<u32x2v*>(base + PG_T * PG_RB) = u32x2v{p1, q1};
-    *reinterpret_cast<u32x2v*>(base + 2 * PG_T * PG_RB) = u32x2v{p2, q2};
+    if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * PG_T * PG_RB) = u32x2v{p2, q2};
   };
 
   // prologue: the first TWO activation chunks are requested before anything else (the second into a register set that is
@@ -438,25 +431,19 @@ __global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short
   const int fragoff = l31 * PG_RB + 16 * half;
   // one k-step of products on buffer `cur` (ksl = 0 / 1: the chunk's first / second 16 channels); `fill(q)` runs after
   // the products of position sub-tile q (the next chunk's split: VALU + LDS stores in the MFMA shadow)
-  auto products = [&](const char* cur, int ksl, u32x4v (&af)[MT][3], auto&& fill) {
+  auto products = [&](const char* cur, int ksl, u32x4v (&af)[MT][NT], auto&& fill) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      bf16x8 bf[3];
+      bf16x8 bf[NT];
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         bf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(cur + fragoff + (t * PG_T + 32 * q) * PG_RB + 32 * ksl));
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        const bf16x8 a0 = __builtin_bit_cast(bf16x8, af[m][0]), a1 = __builtin_bit_cast(bf16x8, af[m][1]),
-                     a2 = __builtin_bit_cast(bf16x8, af[m][2]);
-        f32x16 c = acc[m][q];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bf[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bf[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bf[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[0], c, 0, 0, 0);
-        acc[m][q] = c;
+        bf16x8 am[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) am[t] = __builtin_bit_cast(bf16x8, af[m][t]);
+        acc[m][q] = bn_products<NT>(am, bf, acc[m][q]);
       }
       fill(q);
     }
@@ -506,6 +493,38 @@ __global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short
 #ifdef DSGCN_LAB
   if (blockIdx.x == PWG_STAMP_BLOCK && threadIdx.x == 0) g_pwg_stamp[63] = nst;
 #endif
+}
+
+template <int MODE, int EPI, int MT>
+__global__ __launch_bounds__(256, 2) void k_pwg3(Pw4Args a, const unsigned short* __restrict__ wfr, int RT,
+                                                 P4GuestArg<pwg3_hosts<MODE, EPI, MT>> guest) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int bid = blockIdx.x;
+  if constexpr (pwg3_hosts<MODE, EPI, MT>) {       // guest blocks (see P4Guest): the leading workgroups
+    if (bid < guest.nblk) {
+      p4_block<1, 2, 0, 16, EPI>(guest.a, bid, lds);
+      return;
+    }
+    bid -= guest.nblk;
+  }
+  pwg3_body<MODE, EPI, MT, 3>(a, wfr, RT, bid, lds);
+}
+
+// matmul precision 'high': the same launch on two terms per operand (three products); the guest blocks run their narrow
+// fp32 form unchanged
+template <int MODE, int EPI, int MT>
+__global__ __launch_bounds__(256, 2) void k_pwg3h(Pw4Args a, const unsigned short* __restrict__ wfr, int RT,
+                                                  P4GuestArg<pwg3_hosts<MODE, EPI, MT>> guest) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int bid = blockIdx.x;
+  if constexpr (pwg3_hosts<MODE, EPI, MT>) {
+    if (bid < guest.nblk) {
+      p4_block<1, 2, 0, 16, EPI>(guest.a, bid, lds);
+      return;
+    }
+    bid -= guest.nblk;
+  }
+  pwg3_body<MODE, EPI, MT, 2>(a, wfr, RT, bid, lds);
 }
 
 // The three bf16 terms of W (Co x Ci) as two images, k contiguous and zero-padded to whole tiles:
@@ -704,18 +723,19 @@ bool p4_launch_cfg(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStre
 // the fragment-image form: MT = 2 (256 rows per workgroup) when the conv has more than 128 output rows
 template <int MODE, int EPI, int MT>
 bool pwg3_launch_one(const Pw4Args& a, const dim3 grid, size_t lds, hipStream_t st, const unsigned short* wfr, int RT,
-                     const P4Hosted* h) {
+                     const P4Hosted* h, bool high) {
   constexpr bool HOST = pwg3_hosts<MODE, EPI, MT>;
   const bool hosted = HOST && h;
   const dim3 g(grid.x + (hosted ? (unsigned)h->g.nblk : 0u));
   if (hosted && h->lds > lds) lds = h->lds;
-  hipLaunchKernelGGL((k_pwg3<MODE, EPI, MT>), g, dim3(256), lds, st, a, wfr, RT, p4_guest_arg<HOST>(hosted ? h : nullptr));
+  if (high) hipLaunchKernelGGL((k_pwg3h<MODE, EPI, MT>), g, dim3(256), lds, st, a, wfr, RT, p4_guest_arg<HOST>(hosted ? h : nullptr));
+  else hipLaunchKernelGGL((k_pwg3<MODE, EPI, MT>), g, dim3(256), lds, st, a, wfr, RT, p4_guest_arg<HOST>(hosted ? h : nullptr));
   return hosted;
 }
 
 template <int MT>
 bool pwg3_launch(Pw4Args a, int mode, int epi, const P4Plan& p, const unsigned short* wfr, int Mp, hipStream_t st,
-                 const P4Hosted* h = nullptr) {
+                 const P4Hosted* h = nullptr, bool high = false) {
   constexpr int TA = 128 * MT;
   a.cc = (a.M + TA - 1) / TA;
   const size_t main_b = (size_t)2 * G3_BBUF + (size_t)p.Kpad * 16;
@@ -726,29 +746,33 @@ bool pwg3_launch(Pw4Args a, int mode, int epi, const P4Plan& p, const unsigned s
     const void* fs[5] = {reinterpret_cast<const void*>(&k_pwg3<0, 0, MT>), reinterpret_cast<const void*>(&k_pwg3<1, 0, MT>),
                          reinterpret_cast<const void*>(&k_pwg3<2, 0, MT>), reinterpret_cast<const void*>(&k_pwg3<0, 1, MT>),
                          reinterpret_cast<const void*>(&k_pwg3<2, 1, MT>)};
+    const void* hs[5] = {reinterpret_cast<const void*>(&k_pwg3h<0, 0, MT>), reinterpret_cast<const void*>(&k_pwg3h<1, 0, MT>),
+                         reinterpret_cast<const void*>(&k_pwg3h<2, 0, MT>), reinterpret_cast<const void*>(&k_pwg3h<0, 1, MT>),
+                         reinterpret_cast<const void*>(&k_pwg3h<2, 1, MT>)};
     for (const void* f : fs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    for (const void* f : hs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     raised = true;
   }
   const dim3 grid((unsigned)((p.ngrp + 7) / 8 * 8 * a.cc));
   const int RT = Mp / 32;
   if (epi == 0) {
-    if (mode == 0) return pwg3_launch_one<0, 0, MT>(a, grid, lds, st, wfr, RT, h);
-    if (mode == 1) return pwg3_launch_one<1, 0, MT>(a, grid, lds, st, wfr, RT, h);
-    return pwg3_launch_one<2, 0, MT>(a, grid, lds, st, wfr, RT, h);
+    if (mode == 0) return pwg3_launch_one<0, 0, MT>(a, grid, lds, st, wfr, RT, h, high);
+    if (mode == 1) return pwg3_launch_one<1, 0, MT>(a, grid, lds, st, wfr, RT, h, high);
+    return pwg3_launch_one<2, 0, MT>(a, grid, lds, st, wfr, RT, h, high);
   }
-  if (mode == 0) return pwg3_launch_one<0, 1, MT>(a, grid, lds, st, wfr, RT, h);
-  return pwg3_launch_one<2, 1, MT>(a, grid, lds, st, wfr, RT, h);
+  if (mode == 0) return pwg3_launch_one<0, 1, MT>(a, grid, lds, st, wfr, RT, h, high);
+  return pwg3_launch_one<2, 1, MT>(a, grid, lds, st, wfr, RT, h, high);
 }
 
 template <int PD>
 bool p4_launch_pd(const Pw4Args& a, int mode, int epi, const P4Plan& p, hipStream_t st, const unsigned short* wsp = nullptr,
-                  int Mp = 0, const P4Hosted* h = nullptr, bool* took = nullptr) {
+                  int Mp = 0, const P4Hosted* h = nullptr, bool* took = nullptr, bool high = false) {
   const int key = p.MT * 10 + p.NQ;
   bool t = false;                                  // the launch carried the guest h
   if (took) *took = false;
   if (p.gemm && wsp && g_p4_ws == 2) {
-    if (a.M > 128 && !(g_p4_mt1 & (1 << epi))) t = pwg3_launch<2>(a, mode, epi, p, wsp, Mp, st, h);
-    else t = pwg3_launch<1>(a, mode, epi, p, wsp, Mp, st, h);
+    if (a.M > 128 && !(g_p4_mt1 & (1 << epi))) t = pwg3_launch<2>(a, mode, epi, p, wsp, Mp, st, h, high);
+    else t = pwg3_launch<1>(a, mode, epi, p, wsp, Mp, st, h, high);
     if (took) *took = t;
     return true;
   }
@@ -843,6 +867,15 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_tuning(int key, int value) {
   return 0;
 }
 
+// bf16 products per fp32 product of the forward (epi 0: K = Ci, M = Co) / data gradient (epi 1: K = Co, M = Ci) launch of
+// this shape under the current precision level, the weight image supplied wherever dsgcn_p4_ws_bytes asks for one:
+// 6 / 3 = k_pwg3 / k_pwg3h (k_pwg without the fragment-order image: always 6), 0 = an fp32 MFMA form
+__attribute__((visibility("hidden"))) int dsgcn_p4_terms(int n, int K, int M, int L, int epi) {
+  P4Plan p;
+  if (!p4_plan(n, K, M, L, &p, epi) || !p.gemm) return 0;
+  return (g_p4_ws == 2 && dsgcn_precision_level() == 1) ? 3 : 6;
+}
+
 __attribute__((visibility("hidden"))) int dsgcn_p4_groups(int n, int K, int M, int L, int epi) {
   P4Plan p;
   return p4_plan(n, K, M, L, &p, epi) ? p.ngrp : 0;
@@ -873,8 +906,9 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const fl
   const P4Hosted* h = nullptr;
   if (guest && p4_hosts_guest(p, 0, mode, Co, wsp != nullptr) && p4_guest_plan(*guest, 0, &hg)) h = &hg;
   bool took = false;
-  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 0, p, st, wsp, wd.MpN, h, &took)
-                            : p4_launch_pd<16>(a, mode, 0, p, st, wsp, wd.MpN, h, &took);
+  const bool high = dsgcn_precision_level() == 1;  // (read here, on the host: a captured launch keeps its kernel)
+  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 0, p, st, wsp, wd.MpN, h, &took, high)
+                            : p4_launch_pd<16>(a, mode, 0, p, st, wsp, wd.MpN, h, &took, high);
   if (!ok) return 0;
   DSGCN_LAUNCH_CHECK();
   if (hosted && took) *hosted = 1;
@@ -922,8 +956,9 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const 
   const P4Hosted* h = nullptr;
   if (guest && p4_hosts_guest(p, 1, mode, Ci, wsp != nullptr) && p4_guest_plan(*guest, 1, &hg)) h = &hg;
   bool took = false;
-  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 1, p, st, wsp, wd.MpT, h, &took)
-                            : p4_launch_pd<16>(a, mode, 1, p, st, wsp, wd.MpT, h, &took);
+  const bool high = dsgcn_precision_level() == 1;
+  const bool ok = p.PD == 8 ? p4_launch_pd<8>(a, mode, 1, p, st, wsp, wd.MpT, h, &took, high)
+                            : p4_launch_pd<16>(a, mode, 1, p, st, wsp, wd.MpT, h, &took, high);
   if (!ok) return 0;
   DSGCN_LAUNCH_CHECK();
   if (hosted && took) *hosted = 1;

@@ -1177,6 +1177,9 @@ int g_pw4 = 15;           // bit 0: wide-load forward (pw4.hip), bit 1: wide-loa
 // pw4.hip (internal linkage across the library's objects, not exported)
 __attribute__((visibility("hidden"))) int dsgcn_p4_tuning(int key, int value);
 __attribute__((visibility("hidden"))) int dsgcn_p4_groups(int n, int K, int M, int L, int epi);
+__attribute__((visibility("hidden"))) int dsgcn_p4_terms(int n, int K, int M, int L, int epi);
+__attribute__((visibility("hidden"))) int dsgcn_wg2_terms(int n, int Ci, int Co, int L);
+__attribute__((visibility("hidden"))) int dsgcn_bwd64_terms(int n, int Ci, int Co, int L);
 __attribute__((visibility("hidden"))) int dsgcn_wg2_tuning(int key, int value);
 __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const float* s1, const float* h1,
                                                         const float* x2, const float* s2, const float* h2, int relu,
@@ -1401,6 +1404,20 @@ int dsgcn_pwconv_fwd(const float* x1, const float* s1, const float* h1, const fl
                      void* stream) {
   return dsgcn_pwconv_fwd_ws(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats,
                              nullptr, stream);
+}
+
+// bf16 products per fp32 product of the launch this shape takes under the CURRENT matmul precision level (dir: 0 forward,
+// 1 data gradient, 2 weight gradient): 6 (highest) or 3 (high), 0 = the shape runs an fp32 MFMA form.  Mirrors the
+// dispatch of pw_fwd / pw_dgrad / dsgcn_pwconv_wgrad_jobs and the one-pass backward (dsgcn_pwconv_bwd_rows != 0: six
+// terms at both levels), for a plain conv (no global-joint column) with the weight image passed wherever
+// dsgcn_pwconv_wsplit_bytes asks for one.
+int dsgcn_pwconv_terms(int dir, int n, int Ci, int Co, int T, int V, int stride) {
+  if (dir < 0 || dir > 2 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride != 1) return 0;
+  const int L = T * V;
+  if (dir == 0) return (g_pw4 & 3) == 3 ? dsgcn_p4_terms(n, Ci, Co, L, 0) : 0;
+  if ((g_pw4 & 8) && dsgcn_bwd64_splits(n, Ci, Co, L) > 0) return dsgcn_bwd64_terms(n, Ci, Co, L);
+  if (dir == 1) return (g_pw4 & 3) == 3 ? dsgcn_p4_terms(n, Co, Ci, L, 1) : 0;
+  return (g_pw4 & 4) ? dsgcn_wg2_terms(n, Ci, Co, L) : 0;
 }
 
 // Bytes of the pre-split weight image (three bf16 terms of W and of W^T, zero-padded to whole tiles) that the forward /

@@ -74,9 +74,10 @@ __device__ __forceinline__ float half_sum(float v) {
 // WM: row tiles (of 32 output rows) per workgroup = 4 or 2; the four waves are WM row tiles x 4/WM groups of the position
 // slots, a wave holds 32 rows x 32*WM slots.
 // QS: stride-1 staging with 16-byte loads (launcher: st == 1, up == 1, source planes a multiple of 4 floats long)
-template <int MODE, int EPI, int WM, bool QS = false>
-__global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// NT: bf16 terms per operand — 3 (six products: k_tcg) or 2 (matmul precision 'high', three products: k_tcgh; common.h).
+// NT = 2 reads terms 0 and 1 of the same per-tap weight image and keeps the three-term LDS layout (term 2 untouched).
+template <int MODE, int EPI, int WM, bool QS, int NT>
+__device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
   constexpr int PW = 4 / WM, NQW = WM;             // position groups per workgroup, 32-slot tiles per wave
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -169,12 +170,12 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
               v[e] = ok ? x : 0.f;
             }
             unsigned p0, p1, p2, q0, q1, q2;
-            b3_split(v[0], v[1], p0, p1, p2);
-            b3_split(v[2], v[3], q0, q1, q2);
+            bn_split<NT>(v[0], v[1], p0, p1, p2);
+            bn_split<NT>(v[2], v[3], q0, q1, q2);
             char* base = Bb + sdst[i];
             *reinterpret_cast<u32x2v*>(base) = u32x2v{p0, q0};
             *reinterpret_cast<u32x2v*>(base + NRA * TG_RB) = u32x2v{p1, q1};
-            *reinterpret_cast<u32x2v*>(base + 2 * NRA * TG_RB) = u32x2v{p2, q2};
+            if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * NRA * TG_RB) = u32x2v{p2, q2};
           }
         }
       }
@@ -247,12 +248,12 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
               }
               if (j >= 0 && j < NR) {
                 unsigned p0, p1, p2, q0_, q1, q2;
-                b3_split(v[0], v[1], p0, p1, p2);
-                b3_split(v[2], v[3], q0_, q1, q2);
+                bn_split<NT>(v[0], v[1], p0, p1, p2);
+                bn_split<NT>(v[2], v[3], q0_, q1, q2);
                 char* base = Bb + j * TG_RB + (tid & 7) * 8;
                 *reinterpret_cast<u32x2v*>(base) = u32x2v{p0, q0_};
                 *reinterpret_cast<u32x2v*>(base + NRA * TG_RB) = u32x2v{p1, q1};
-                *reinterpret_cast<u32x2v*>(base + 2 * NRA * TG_RB) = u32x2v{p2, q2};
+                if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * NRA * TG_RB) = u32x2v{p2, q2};
               }
             }
           }
@@ -268,12 +269,12 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
   // one tap of products (0.3-0.6 us) to hide each of them behind.
   const unsigned short* arow = a.wsp + ((size_t)((mBase0 >> 5) + rt) * (a.Kp >> 4)) * 512 + (half * 32 + l31) * 8;
   const size_t tstride = (size_t)a.Mp * a.Kp;      // elements between the (tap, term) planes
-  u32x4v ac[2][3], an[2][3];
-  auto loadA = [&](int tap, int ch0, u32x4v (&af)[2][3]) {
+  u32x4v ac[2][NT], an[2][NT];
+  auto loadA = [&](int tap, int ch0, u32x4v (&af)[2][NT]) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         af[ks][t] = *reinterpret_cast<const u32x4v*>(arow + (size_t)(tap * 3 + t) * tstride + ((ch0 >> 4) + ks) * 512);
   };
   f32x16 acc[NQW];
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
   // products, less than an L2 round trip under load) also the one after it (round 5; the 128-row kernels have no registers
   // left for a third set)
   constexpr bool PF2 = WM == 2;
-  u32x4v an2[PF2 ? 2 : 1][3];
+  u32x4v an2[PF2 ? 2 : 1][NT];
   loadA(0, 0, ac);
   if constexpr (PF2) {
     if (KT > 1) loadA(1, 0, an);
@@ -325,28 +326,22 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
       const char* Bft = Bb + tap * V * TG_RB;
 #pragma unroll
       for (int ks = 0; ks < TG_KC / 16; ++ks) {
-        const bf16x8 a0 = __builtin_bit_cast(bf16x8, ac[ks][0]), a1 = __builtin_bit_cast(bf16x8, ac[ks][1]),
-                     a2 = __builtin_bit_cast(bf16x8, ac[ks][2]);
+        bf16x8 am[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) am[t] = __builtin_bit_cast(bf16x8, ac[ks][t]);
 #pragma unroll
         for (int q = 0; q < NQW; ++q) {
-          bf16x8 bf[3];
+          bf16x8 bf[NT];
 #pragma unroll
-          for (int t = 0; t < 3; ++t)
+          for (int t = 0; t < NT; ++t)
             bf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(Bft + bfo[q] + t * NRA * TG_RB + 32 * ks));
-          f32x16 c = acc[q];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bf[0], c, 0, 0, 0);
-          acc[q] = c;
+          acc[q] = bn_products<NT>(am, bf, acc[q]);
         }
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
+        for (int t = 0; t < NT; ++t) {
           ac[ks][t] = an[ks][t];
           if constexpr (PF2) an[ks][t] = an2[ks][t];
         }
@@ -479,6 +474,19 @@ __global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
   }
 }
 
+template <int MODE, int EPI, int WM, bool QS = false>
+__global__ __launch_bounds__(TG_NT, 2) void k_tcg(TcgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  tcg_body<MODE, EPI, WM, QS, 3>(a, lds);
+}
+
+// matmul precision 'high': two terms per operand, three products
+template <int MODE, int EPI, int WM, bool QS = false>
+__global__ __launch_bounds__(TG_NT, 2) void k_tcgh(TcgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  tcg_body<MODE, EPI, WM, QS, 2>(a, lds);
+}
+
 // The three bf16 terms of W (Co, Ci, KT) per tap, zero-padded to whole tiles, every (tap, term) plane in MFMA-fragment
 // order [row tile of 32][k-step of 16][lane = 32*(k%16 / 8) + row%32][k%8] (a wave's A fragment = one contiguous 1 KB):
 //   N image (forward):        [KT][3][MpN = ceil128(Co) x KpN = ceil32(Ci)]   value W[co][ci][tap]
@@ -566,9 +574,9 @@ __device__ long long g_tcw_stamp[64];
 #endif
 
 // ST: 1 = stride 1 (the x' ring), 2 = stride 2
-template <int KT, int ST>
-__global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// NT: bf16 terms per operand, as for tcg_body (2: k_tcwh)
+template <int KT, int ST, int NT>
+__device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -706,12 +714,12 @@ __global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
         const float v0 = xr[q_ & (TW_RING - 1)], v1 = xr[(q_ + 1) & (TW_RING - 1)], v2 = xr[(q_ + 2) & (TW_RING - 1)],
                     v3 = xr[(q_ + 3) & (TW_RING - 1)];
         unsigned p0_, p1_, p2_, q0_, q1_, q2_;
-        b3_split(v0, v1, p0_, p1_, p2_);
-        b3_split(v2, v3, q0_, q1_, q2_);
+        bn_split<NT>(v0, v1, p0_, p1_, p2_);
+        bn_split<NT>(v2, v3, q0_, q1_, q2_);
         char* base = Bb0 + (tl * 3 * TW_TN + brow) * TG_RB + bpc * 8;
         *reinterpret_cast<u32x2v*>(base) = u32x2v{p0_, q0_};
         *reinterpret_cast<u32x2v*>(base + TW_TN * TG_RB) = u32x2v{p1_, q1_};
-        *reinterpret_cast<u32x2v*>(base + 2 * TW_TN * TG_RB) = u32x2v{p2_, q2_};
+        if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * TW_TN * TG_RB) = u32x2v{p2_, q2_};
       }
     }
   };
@@ -785,11 +793,11 @@ __global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
     dbacc += sv;
     unsigned t0[4], t1[4], t2[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) b3_split(v[2 * j], v[2 * j + 1], t0[j], t1[j], t2[j]);
+    for (int j = 0; j < 4; ++j) bn_split<NT>(v[2 * j], v[2 * j + 1], t0[j], t1[j], t2[j]);
     char* base = Ab + arow * TG_RB + apc * 16;
     *reinterpret_cast<u32x4v*>(base) = u32x4v{t0[0], t0[1], t0[2], t0[3]};
     *reinterpret_cast<u32x4v*>(base + TW_TM * TG_RB) = u32x4v{t1[0], t1[1], t1[2], t1[3]};
-    *reinterpret_cast<u32x4v*>(base + 2 * TW_TM * TG_RB) = u32x4v{t2[0], t2[1], t2[2], t2[3]};
+    if constexpr (NT == 3) *reinterpret_cast<u32x4v*>(base + 2 * TW_TM * TG_RB) = u32x4v{t2[0], t2[1], t2[2], t2[3]};
   };
   auto commitB = [&](int u, int grp, int buf) {
     char* Bb = Bb0 + buf * BSZ;
@@ -813,12 +821,12 @@ __global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
           v[e] = ok ? x : 0.f;                     // zero padding applies to the activated value
         }
         unsigned p0_, p1_, p2_, q0_, q1_, q2_;
-        b3_split(v[0], v[1], p0_, p1_, p2_);
-        b3_split(v[2], v[3], q0_, q1_, q2_);
+        bn_split<NT>(v[0], v[1], p0_, p1_, p2_);
+        bn_split<NT>(v[2], v[3], q0_, q1_, q2_);
         char* base = Bb + (tl * 3 * TW_TN + brow) * TG_RB + bpc * 8;
         *reinterpret_cast<u32x2v*>(base) = u32x2v{p0_, q0_};
         *reinterpret_cast<u32x2v*>(base + TW_TN * TG_RB) = u32x2v{p1_, q1_};
-        *reinterpret_cast<u32x2v*>(base + 2 * TW_TN * TG_RB) = u32x2v{p2_, q2_};
+        if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * TW_TN * TG_RB) = u32x2v{p2_, q2_};
       }
     }
   };
@@ -834,26 +842,19 @@ __global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
     const char* Bf = Bf0 + bbuf * BSZ;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[3];
+      bf16x8 af[NT];
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         af[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(Af + t * TW_TM * TG_RB + 32 * ks));
 #pragma unroll
       for (int tl = 0; tl < TW_G; ++tl) {
         const int tap = grp * TW_G + tl;
         if (tap < KT && owns(tl)) {
-          bf16x8 bf[3];
+          bf16x8 bf[NT];
 #pragma unroll
-          for (int t = 0; t < 3; ++t)
+          for (int t = 0; t < NT; ++t)
             bf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(Bf + ((tl * 3 + t) * TW_TN) * TG_RB + 32 * ks));
-          f32x16 c = acc[tap];
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], c, 0, 0, 0);
-          acc[tap] = c;
+          acc[tap] = bn_products<NT>(af, bf, acc[tap]);
         }
       }
     }
@@ -942,6 +943,19 @@ __global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
   if (cn == 0 && (tide & 3) == 0 && acoe < Co) a.dbp[(size_t)sp * a.pstride + acoe] = dbacc;
 }
 
+template <int KT, int ST>
+__global__ __launch_bounds__(TW_NT, 2) void k_tcw(TcwArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  tcw_body<KT, ST, 3>(a, lds);
+}
+
+// matmul precision 'high': two terms per operand, three products
+template <int KT, int ST>
+__global__ __launch_bounds__(TW_NT, 2) void k_tcwh(TcwArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  tcw_body<KT, ST, 2>(a, lds);
+}
+
 struct TwPlan { int cpl, units, ccM, ccN, splits, nqi; size_t lds; };
 bool tw_plan(int n, int Ci, int Co, int To, int V, int KT, TwPlan* p, int st = 1) {
   const long L = (long)To * V;                     // positions of dz per plane
@@ -1007,8 +1021,9 @@ template <int EPI, int WM, bool QS>
 int tg_launch_qs(const TcgArgs& a, int mode, const TgPlan& p, hipStream_t st) {
   static bool raised = false;
   if (!raised) {
-    const void* fs[3] = {reinterpret_cast<const void*>(&k_tcg<0, EPI, WM, QS>), reinterpret_cast<const void*>(&k_tcg<1, EPI, WM, QS>),
-                         reinterpret_cast<const void*>(&k_tcg<2, EPI, WM, QS>)};
+    const void* fs[6] = {reinterpret_cast<const void*>(&k_tcg<0, EPI, WM, QS>), reinterpret_cast<const void*>(&k_tcg<1, EPI, WM, QS>),
+                         reinterpret_cast<const void*>(&k_tcg<2, EPI, WM, QS>), reinterpret_cast<const void*>(&k_tcgh<0, EPI, WM, QS>),
+                         reinterpret_cast<const void*>(&k_tcgh<1, EPI, WM, QS>), reinterpret_cast<const void*>(&k_tcgh<2, EPI, WM, QS>)};
     for (const void* f : fs) {
       hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       if (e != hipSuccess) return (int)e;
@@ -1016,6 +1031,13 @@ int tg_launch_qs(const TcgArgs& a, int mode, const TgPlan& p, hipStream_t st) {
     raised = true;
   }
   const dim3 grid(p.grid), blk(TG_NT);
+  if (dsgcn_precision_level() == 1) {              // (read here, on the host: a captured launch keeps its kernel)
+    if (mode == 0) hipLaunchKernelGGL((k_tcgh<0, EPI, WM, QS>), grid, blk, p.lds, st, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_tcgh<1, EPI, WM, QS>), grid, blk, p.lds, st, a);
+    else hipLaunchKernelGGL((k_tcgh<2, EPI, WM, QS>), grid, blk, p.lds, st, a);
+    DSGCN_LAUNCH_CHECK();
+    return 0;
+  }
   if (mode == 0) hipLaunchKernelGGL((k_tcg<0, EPI, WM, QS>), grid, blk, p.lds, st, a);
   else if (mode == 1) hipLaunchKernelGGL((k_tcg<1, EPI, WM, QS>), grid, blk, p.lds, st, a);
   else hipLaunchKernelGGL((k_tcg<2, EPI, WM, QS>), grid, blk, p.lds, st, a);
@@ -1050,6 +1072,14 @@ size_t dsgcn_tconv_ws_bytes(int n, int Ci, int Co, int T, int V, int KT, int str
       !tw_plan(n, Ci, Co, To, V, KT, &pw, stride))
     return 0;
   return ts_dims(Ci, Co, KT).bytes;
+}
+
+// bf16 products per fp32 product of the dense temporal conv's launch for this shape (dir: 0 forward, 1 data gradient,
+// 2 weight gradient) under the current matmul precision level: 6 = k_tcg / k_tcw, 3 = k_tcgh / k_tcwh; 0 = the GEMM form
+// does not take the shape.
+int dsgcn_tconv_terms(int dir, int n, int Ci, int Co, int T, int V, int KT, int stride) {
+  if (dir < 0 || dir > 2 || dsgcn_tconv_ws_bytes(n, Ci, Co, T, V, KT, stride) == 0) return 0;
+  return dsgcn_precision_level() == 1 ? 3 : 6;
 }
 
 // The weight images of njobs convs in one launch per DSGCN_TSPLIT_JOBS_MAX records (include/dsgcn_jobs.h).
@@ -1158,13 +1188,29 @@ int dsgcn_tconv_wgrad(const float* x1, const float* s1, const float* h1, const f
   const dim3 grid((unsigned)(p.splits * p.ccM * p.ccN)), blk(TW_NT);
   static bool raised = false;
   if (!raised) {
-    const void* fs[6] = {reinterpret_cast<const void*>(&k_tcw<9, 1>), reinterpret_cast<const void*>(&k_tcw<5, 1>),
-                         reinterpret_cast<const void*>(&k_tcw<3, 1>), reinterpret_cast<const void*>(&k_tcw<9, 2>),
-                         reinterpret_cast<const void*>(&k_tcw<5, 2>), reinterpret_cast<const void*>(&k_tcw<3, 2>)};
+    const void* fs[12] = {reinterpret_cast<const void*>(&k_tcw<9, 1>), reinterpret_cast<const void*>(&k_tcw<5, 1>),
+                          reinterpret_cast<const void*>(&k_tcw<3, 1>), reinterpret_cast<const void*>(&k_tcw<9, 2>),
+                          reinterpret_cast<const void*>(&k_tcw<5, 2>), reinterpret_cast<const void*>(&k_tcw<3, 2>),
+                          reinterpret_cast<const void*>(&k_tcwh<9, 1>), reinterpret_cast<const void*>(&k_tcwh<5, 1>),
+                          reinterpret_cast<const void*>(&k_tcwh<3, 1>), reinterpret_cast<const void*>(&k_tcwh<9, 2>),
+                          reinterpret_cast<const void*>(&k_tcwh<5, 2>), reinterpret_cast<const void*>(&k_tcwh<3, 2>)};
     for (const void* f : fs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     raised = true;
   }
   hipStream_t st = (hipStream_t)stream;
+  if (dsgcn_precision_level() == 1) {              // (read here, on the host: a captured launch keeps its kernel)
+    if (stride == 1) {
+      if (KT == 9) hipLaunchKernelGGL((k_tcwh<9, 1>), grid, blk, p.lds, st, a);
+      else if (KT == 5) hipLaunchKernelGGL((k_tcwh<5, 1>), grid, blk, p.lds, st, a);
+      else hipLaunchKernelGGL((k_tcwh<3, 1>), grid, blk, p.lds, st, a);
+    } else {
+      if (KT == 9) hipLaunchKernelGGL((k_tcwh<9, 2>), grid, blk, p.lds, st, a);
+      else if (KT == 5) hipLaunchKernelGGL((k_tcwh<5, 2>), grid, blk, p.lds, st, a);
+      else hipLaunchKernelGGL((k_tcwh<3, 2>), grid, blk, p.lds, st, a);
+    }
+    DSGCN_LAUNCH_CHECK();
+    return 0;
+  }
   if (stride == 1) {
     if (KT == 9) hipLaunchKernelGGL((k_tcw<9, 1>), grid, blk, p.lds, st, a);
     else if (KT == 5) hipLaunchKernelGGL((k_tcw<5, 1>), grid, blk, p.lds, st, a);

@@ -41,22 +41,35 @@ __device__ __forceinline__ int wg_row32(int r, int half) { return (r & 3) + 8 * 
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// What every weight-gradient kernel does before its body, on the kernel's OWN argument (the job table and the group
+// records are indexed at run time: read straight from the kernel-argument segment here, they never become a private copy):
+// the workgroups past the weight gradient's run the hosted BatchNorm coefficient jobs (the weight gradient is off the
+// critical chain), a grouped launch picks this workgroup's conv.
+#define WG_KERNEL_HEAD(NTHR)                                                                                             \
+  extern __shared__ __attribute__((aligned(16))) float lds[];                                                            \
+  if ((int)blockIdx.x >= a_.main_blocks) {                                                                               \
+    bnj_dispatch(a_.jobs, (int)blockIdx.x - a_.main_blocks,                                                              \
+                 [&](const BnCoefJob& J, int b) { bn_coef_rows_block<NTHR>(J, b, reinterpret_cast<double (*)[8][2]>(lds)); }); \
+    return;                                                                                                              \
+  }                                                                                                                      \
+  Wg2Args a = a_;                                                                                                        \
+  if (a_.ngroup > 1) {                                                                                                   \
+    const Wg2Args::Grp& q = a_.g[blockIdx.y];                                                                            \
+    a.x1 = q.x1; a.s1 = q.s1; a.h1 = q.h1; a.gz = q.gz; a.dwp = q.dwp; a.dbp = q.dbp;                                    \
+  }
+
 // B3: the tiles are staged as the three bf16 terms of every value (common.h: exact split, six bf16 MFMAs per 16 positions
 // in place of eight fp32 ones at twice the cycles each); rows of KC bf16 + 16 B of pad per term (conflict-free 16-byte
 // fragment reads: a lane reads 8 consecutive positions of its channel row).
-template <int TM, int TN, int KC, bool HAS2, bool HASC, bool B3 = false>
-__global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
-  Wg2Args a = a_;
-  if (a_.ngroup > 1) {                             // grouped launch: this workgroup's conv
-    const Wg2Args::Grp& q = a_.g[blockIdx.y];
-    a.x1 = q.x1; a.s1 = q.s1; a.h1 = q.h1; a.gz = q.gz; a.dwp = q.dwp; a.dbp = q.dbp;
-  }
+// NT: bf16 terms staged per value — 3 (six products) or 2 (matmul precision 'high': three products, common.h); NT = 2
+// keeps the three-term LDS layout and leaves term 2's rows untouched.
+template <int TM, int TN, int KC, bool HAS2, bool HASC, bool B3, int NT>
+__device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
   constexpr int LS = KC + 2;
   constexpr int RB = KC * 2 + 16;                 // B3: bytes per row per term
   constexpr int Q = KC / 4;                       // float4 slots per row
   constexpr int JD = TM * Q / WG_NT, JX = TN * Q / WG_NT;
   constexpr int MI = TM / 64, NI = TN / 64;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Ds = lds;                                // [TM][LS] dz_eff
   float* Xs = lds + TM * LS;                      // [TN][LS] virtual input
   constexpr int TF = B3 ? 3 * (TM + TN) * RB / 4 : (TM + TN) * LS;   // floats of tile storage
@@ -64,11 +77,6 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
   char* Xb = Db + 3 * TM * RB;                    // B3: [3][TN][RB] virtual-input terms
   f32x2* Cs = reinterpret_cast<f32x2*>(lds + TF);          // [TM] (A0, B0)
   f32x4* Ps = reinterpret_cast<f32x4*>(lds + TF + 2 * TM);  // [TN] (s1, h1, s2, h2)
-  if ((int)blockIdx.x >= a.main_blocks) {          // hosted BatchNorm coefficient jobs: the weight gradient is off the critical chain
-    bnj_dispatch(a.jobs, (int)blockIdx.x - a.main_blocks,
-                 [&](const BnCoefJob& J, int b) { bn_coef_rows_block<WG_NT>(J, b, reinterpret_cast<double (*)[8][2]>(lds)); });
-    return;
-  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
@@ -160,12 +168,12 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
       dsum[j] += (d.x + d.y) + (d.z + d.w);
       if constexpr (B3) {
         unsigned p0, p1, p2, q0, q1, q2;
-        b3_split(d.x, d.y, p0, p1, p2);
-        b3_split(d.z, d.w, q0, q1, q2);
+        bn_split<NT>(d.x, d.y, p0, p1, p2);
+        bn_split<NT>(d.z, d.w, q0, q1, q2);
         char* dst = Db + row * RB + col * 2;
         *reinterpret_cast<u32x2v*>(dst) = u32x2v{p0, q0};
         *reinterpret_cast<u32x2v*>(dst + TM * RB) = u32x2v{p1, q1};
-        *reinterpret_cast<u32x2v*>(dst + 2 * TM * RB) = u32x2v{p2, q2};
+        if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(dst + 2 * TM * RB) = u32x2v{p2, q2};
       } else {
         f32x2* dst = reinterpret_cast<f32x2*>(Ds + row * LS + col);
         dst[0] = f32x2{d.x, d.y};
@@ -186,12 +194,12 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
       }
       if constexpr (B3) {
         unsigned p0, p1, p2, q0, q1, q2;
-        b3_split(v.x, v.y, p0, p1, p2);
-        b3_split(v.z, v.w, q0, q1, q2);
+        bn_split<NT>(v.x, v.y, p0, p1, p2);
+        bn_split<NT>(v.z, v.w, q0, q1, q2);
         char* dst = Xb + row * RB + col * 2;
         *reinterpret_cast<u32x2v*>(dst) = u32x2v{p0, q0};
         *reinterpret_cast<u32x2v*>(dst + TN * RB) = u32x2v{p1, q1};
-        *reinterpret_cast<u32x2v*>(dst + 2 * TN * RB) = u32x2v{p2, q2};
+        if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(dst + 2 * TN * RB) = u32x2v{p2, q2};
       } else {
         f32x2* dst = reinterpret_cast<f32x2*>(Xs + row * LS + col);
         dst[0] = f32x2{v.x, v.y};
@@ -224,9 +232,9 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
       const char* Bb = Xb + (n0 + l31) * RB + 16 * half;
 #pragma unroll
       for (int ks = 0; ks < KC / 16; ++ks) {
-        bf16x8 af[MI][3], bf[NI][3];
+        bf16x8 af[MI][NT], bf[NI][NT];
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
+        for (int t = 0; t < NT; ++t) {
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi)
             af[mi][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(Ab + (t * TM + 32 * mi) * RB + 32 * ks));
@@ -237,16 +245,7 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            f32x16 c = acc[mi][ni];
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][2], bf[ni][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][1], bf[ni][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[ni][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][1], bf[ni][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[ni][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[ni][0], c, 0, 0, 0);
-            acc[mi][ni] = c;
-          }
+          for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = bn_products<NT>(af[mi], bf[ni], acc[mi][ni]);
       }
     } else {
 #pragma unroll
@@ -295,6 +294,19 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
   }
 }
 
+template <int TM, int TN, int KC, bool HAS2, bool HASC, bool B3 = false>
+__global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
+  WG_KERNEL_HEAD(WG_NT)
+  wg2_body<TM, TN, KC, HAS2, HASC, B3, 3>(a, lds);
+}
+
+// matmul precision 'high': the B3 tile on two terms per value
+template <int TM, int TN, int KC, bool HAS2, bool HASC>
+__global__ __launch_bounds__(WG_NT, 2) void k_wg2h(Wg2Args a_) {
+  WG_KERNEL_HEAD(WG_NT)
+  wg2_body<TM, TN, KC, HAS2, HASC, true, 2>(a, lds);
+}
+
 // ---- wide convs (more than 128 channels on either side): the whole dW tile in one workgroup ("wg3") ------------------
 // k_wg2<128,128,32,B3> at 256 -> 256 runs 2 x 2 output tiles x 128 K-splits: every dz_eff / input value is split into its
 // three bf16 terms TWICE (42 values per MFMA), in lockstep phases (commit, barrier, 48 products, barrier) on one LDS
@@ -305,29 +317,18 @@ __global__ __launch_bounds__(WG_NT, 2) void k_wg2(Wg2Args a_) {
 // register sets.  One workgroup per CU (150 KB of LDS), ~256 K-splits: one round.
 constexpr int W3_NT = 512, W3_KC = 16, W3_RB = 48;
 
-template <int TM, int TN, bool HAS2, bool HASC>
-__global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
-  Wg2Args a = a_;
-  if (a_.ngroup > 1) {                             // grouped launch: this workgroup's conv
-    const Wg2Args::Grp& q = a_.g[blockIdx.y];
-    a.x1 = q.x1; a.s1 = q.s1; a.h1 = q.h1; a.gz = q.gz; a.dwp = q.dwp; a.dbp = q.dbp;
-  }
+template <int TM, int TN, bool HAS2, bool HASC, int NT>
+__device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
   constexpr int JD = TM * 4 / W3_NT, JX = TN * 4 / W3_NT;          // float4 slots per thread and chunk
   constexpr int MI = TM / 128, NI = TN / 64;                       // wave tile: (TM/4) x (TN/2) = MI x NI MFMA tiles
   constexpr int BUF = 3 * (TM + TN) * W3_RB;
   // operand chunks in flight ahead of the one being split: 2 (ping-pong register sets) except where 256 accumulator +
   // fragment registers leave room for one set only (two input streams AND a BatchNorm term on the full tile)
   constexpr int DEPTH = (HAS2 && HASC && TM == 256 && TN == 256) ? 1 : 2;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   char* B0p = reinterpret_cast<char*>(lds);                        // buffer: [3][TM][RB] dz_eff terms, [3][TN][RB] input terms
   char* B1p = B0p + BUF;
   f32x2* Cs = reinterpret_cast<f32x2*>(B1p + BUF);                 // [TM] (A0, B0)
   f32x4* Ps = reinterpret_cast<f32x4*>(Cs + TM);                   // [TN] (s1, h1, s2, h2)
-  if ((int)blockIdx.x >= a.main_blocks) {          // hosted BatchNorm coefficient jobs (see k_wg2)
-    bnj_dispatch(a.jobs, (int)blockIdx.x - a.main_blocks,
-                 [&](const BnCoefJob& J, int b) { bn_coef_rows_block<W3_NT>(J, b, reinterpret_cast<double (*)[8][2]>(lds)); });
-    return;
-  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
@@ -417,8 +418,8 @@ __global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
 #pragma unroll
       for (int e = 1; e < 4; ++e) d[e] = e < nv ? d[e] : 0.f;
       dsum[j] += (d.x + d.y) + (d.z + d.w);
-      b3_split(d.x, d.y, p0, p1, p2);
-      b3_split(d.z, d.w, q0, q1, q2);
+      bn_split<NT>(d.x, d.y, p0, p1, p2);
+      bn_split<NT>(d.z, d.w, q0, q1, q2);
       base = dst + row * W3_RB + col * 2;
       tstride = TM * W3_RB;
     } else {
@@ -433,14 +434,14 @@ __global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
         if constexpr (HAS2) t += fmaf(r.y[j][e], p.z, p.w);
         v[e] = (ok & (e < nv)) ? fmaxf(t, lo) : 0.f;
       }
-      b3_split(v.x, v.y, p0, p1, p2);
-      b3_split(v.z, v.w, q0, q1, q2);
+      bn_split<NT>(v.x, v.y, p0, p1, p2);
+      bn_split<NT>(v.z, v.w, q0, q1, q2);
       base = dst + 3 * TM * W3_RB + row * W3_RB + col * 2;
       tstride = TN * W3_RB;
     }
     *reinterpret_cast<u32x2v*>(base) = u32x2v{p0, q0};
     *reinterpret_cast<u32x2v*>(base + tstride) = u32x2v{p1, q1};
-    *reinterpret_cast<u32x2v*>(base + 2 * tstride) = u32x2v{p2, q2};
+    if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(base + 2 * tstride) = u32x2v{p2, q2};
   };
 
   f32x16 acc[MI][NI];
@@ -469,36 +470,27 @@ __global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
 
   // one chunk: its 16 positions' products on `cur` with chunk ch+1's split (register set r) written to `nxt` in between
   auto step = [&](int ch, const char* cur, char* nxt, Regs& r) {
-    bf16x8 af[MI][3];
+    bf16x8 af[MI][NT];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         af[mi][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(cur + aoff + (t * TM + 32 * mi) * W3_RB));
     // input fragments one position sub-block ahead, in two register sets pinned by scheduling barriers (left alone the
     // compiler hoists all NI x 3 fragment reads to the top: 48 registers it does not have)
-    bf16x8 bfs[2][3];
-    auto loadB = [&](int ni, bf16x8 (&bf)[3]) {
+    bf16x8 bfs[2][NT];
+    auto loadB = [&](int ni, bf16x8 (&bf)[NT]) {
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
+      for (int t = 0; t < NT; ++t)
         bf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4v*>(cur + boff + (t * TN + 32 * ni) * W3_RB));
     };
     loadB(0, bfs[0]);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      bf16x8 (&bf)[3] = bfs[ni & 1];
+      bf16x8 (&bf)[NT] = bfs[ni & 1];
       if (ni + 1 < NI) loadB(ni + 1, bfs[(ni + 1) & 1]);
 #pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        f32x16 c = acc[mi][ni];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][2], bf[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][1], bf[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][1], bf[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[mi][0], bf[0], c, 0, 0, 0);
-        acc[mi][ni] = c;
-      }
+      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = bn_products<NT>(af[mi], bf, acc[mi][ni]);
       // the next chunk's split, a piece per position sub-block of products (VALU + LDS stores in the MFMA shadow)
 #pragma unroll
       for (int pc = ni; pc < JD + JX; pc += NI) commit_piece(ch + 1, r, nxt, pc);
@@ -552,6 +544,19 @@ __global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
       if ((tid & 3) == 0 && co < Co) a.dbp[(size_t)split * a.pstride + co] = s;
     }
   }
+}
+
+template <int TM, int TN, bool HAS2, bool HASC>
+__global__ __launch_bounds__(W3_NT, 2) void k_wg3(Wg2Args a_) {
+  WG_KERNEL_HEAD(W3_NT)
+  wg3_body<TM, TN, HAS2, HASC, 3>(a, lds);
+}
+
+// matmul precision 'high': two terms per value
+template <int TM, int TN, bool HAS2, bool HASC>
+__global__ __launch_bounds__(W3_NT, 2) void k_wg3h(Wg2Args a_) {
+  WG_KERNEL_HEAD(W3_NT)
+  wg3_body<TM, TN, HAS2, HASC, 2>(a, lds);
 }
 
 int g_wg2_target4 = 512, g_wg2_kc128 = 32, g_wg2_target1 = 512, g_wg2_b3 = 1, g_wg3 = 3, g_wg3_target = 256, g_wg3_tm = 128;    // lab knobs (dsgcn_pwconv_tuning keys 7, 8); the values are the product's
@@ -613,14 +618,38 @@ void wg2_launch(const Wg2Args& a, bool has2, bool hasc, dim3 grid, size_t lds, h
   }
 }
 
+// the 128 x 128 B3 tile at matmul precision 'high'
+void wg2h_launch(const Wg2Args& a, bool has2, bool hasc, dim3 grid, size_t lds, hipStream_t st) {
+  if (has2) {
+    if (hasc) hipLaunchKernelGGL((k_wg2h<128, 128, 32, true, true>), grid, dim3(WG_NT), lds, st, a);
+    else hipLaunchKernelGGL((k_wg2h<128, 128, 32, true, false>), grid, dim3(WG_NT), lds, st, a);
+  } else {
+    if (hasc) hipLaunchKernelGGL((k_wg2h<128, 128, 32, false, true>), grid, dim3(WG_NT), lds, st, a);
+    else hipLaunchKernelGGL((k_wg2h<128, 128, 32, false, false>), grid, dim3(WG_NT), lds, st, a);
+  }
+}
+
 template <int TM, int TN>
-void wg3_launch(const Wg2Args& a, bool has2, bool hasc, dim3 grid, size_t lds, hipStream_t st) {
+void wg3_launch(const Wg2Args& a, bool has2, bool hasc, dim3 grid, size_t lds, hipStream_t st, bool high) {
   static bool raised = false;
   if (!raised) {
     const void* fs[4] = {reinterpret_cast<const void*>(&k_wg3<TM, TN, false, false>), reinterpret_cast<const void*>(&k_wg3<TM, TN, false, true>),
                          reinterpret_cast<const void*>(&k_wg3<TM, TN, true, false>), reinterpret_cast<const void*>(&k_wg3<TM, TN, true, true>)};
+    const void* hs[4] = {reinterpret_cast<const void*>(&k_wg3h<TM, TN, false, false>), reinterpret_cast<const void*>(&k_wg3h<TM, TN, false, true>),
+                         reinterpret_cast<const void*>(&k_wg3h<TM, TN, true, false>), reinterpret_cast<const void*>(&k_wg3h<TM, TN, true, true>)};
     for (const void* f : fs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const void* f : hs) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     raised = true;
+  }
+  if (high) {
+    if (has2) {
+      if (hasc) hipLaunchKernelGGL((k_wg3h<TM, TN, true, true>), grid, dim3(W3_NT), lds, st, a);
+      else hipLaunchKernelGGL((k_wg3h<TM, TN, true, false>), grid, dim3(W3_NT), lds, st, a);
+    } else {
+      if (hasc) hipLaunchKernelGGL((k_wg3h<TM, TN, false, true>), grid, dim3(W3_NT), lds, st, a);
+      else hipLaunchKernelGGL((k_wg3h<TM, TN, false, false>), grid, dim3(W3_NT), lds, st, a);
+    }
+    return;
   }
   if (has2) {
     if (hasc) hipLaunchKernelGGL((k_wg3<TM, TN, true, true>), grid, dim3(W3_NT), lds, st, a);
@@ -651,6 +680,14 @@ __attribute__((visibility("hidden"))) int dsgcn_wg2_splits(int n, int Ci, int Co
   return wg2_plan(n, Ci, Co, L, &p) ? p.splits : 0;
 }
 
+// bf16 products per fp32 product of the fast weight gradient of this shape under the current precision level: 6 / 3 = the
+// B3 tile of k_wg2 or k_wg3 (k_wg2h / k_wg3h), 0 = an fp32 MFMA tile or not eligible
+__attribute__((visibility("hidden"))) int dsgcn_wg2_terms(int n, int Ci, int Co, int L) {
+  Wg2Plan p;
+  if (!wg2_plan(n, Ci, Co, L, &p) || !p.b3) return 0;
+  return dsgcn_precision_level() == 1 ? 3 : 6;
+}
+
 // Returns 1 = launched, 0 = not eligible (caller falls back), other = error.
 __attribute__((visibility("hidden"))) int dsgcn_wg2(const float* x1, const float* s1, const float* h1, const float* x2,
                                                      const float* s2, const float* h2, int relu, const float* z,
@@ -677,13 +714,14 @@ __attribute__((visibility("hidden"))) int dsgcn_wg2(const float* x1, const float
   a.main_blocks = tiles > 1 ? (p.splits + 7) / 8 * 8 * tiles : p.splits;
   const dim3 grid((unsigned)(a.main_blocks + bnj_total_blocks(a.jobs)), ngroup > 1 ? (unsigned)ngroup : 1u);
   const bool has2 = x2 != nullptr, hasc = A0 != nullptr;
+  const bool high = dsgcn_precision_level() == 1;  // (read here, on the host: a captured launch keeps its kernel)
   if (p.v3) {
 #ifdef DSGCN_LAB                                   // the full 256 x 256 tile (key 17 = 256) measured slower in the step: lab builds only
-    if (p.TM == 256 && p.TN == 256) wg3_launch<256, 256>(a, has2, hasc, grid, p.lds, st);
+    if (p.TM == 256 && p.TN == 256) wg3_launch<256, 256>(a, has2, hasc, grid, p.lds, st, high);
     else
 #endif
-    if (p.TM == 256) wg3_launch<256, 128>(a, has2, hasc, grid, p.lds, st);
-    else wg3_launch<128, 256>(a, has2, hasc, grid, p.lds, st);
+    if (p.TM == 256) wg3_launch<256, 128>(a, has2, hasc, grid, p.lds, st, high);
+    else wg3_launch<128, 256>(a, has2, hasc, grid, p.lds, st, high);
     DSGCN_LAUNCH_CHECK();
     return 1;
   }
@@ -691,7 +729,8 @@ __attribute__((visibility("hidden"))) int dsgcn_wg2(const float* x1, const float
   if (p.TM == 128 && p.TN == 128 && p.KC == 64) wg2_launch<128, 128, 64>(a, has2, hasc, grid, p.lds, st);
   else
 #endif
-  if (p.b3) wg2_launch<128, 128, 32, true>(a, has2, hasc, grid, p.lds, st);
+  if (p.b3 && high) wg2h_launch(a, has2, hasc, grid, p.lds, st);
+  else if (p.b3) wg2_launch<128, 128, 32, true>(a, has2, hasc, grid, p.lds, st);
   else if (p.TM == 128 && p.TN == 128) wg2_launch<128, 128, 32>(a, has2, hasc, grid, p.lds, st);
   else if (p.TM == 128) wg2_launch<128, 64, 64>(a, has2, hasc, grid, p.lds, st);
   else if (p.TN == 128) wg2_launch<64, 128, 64>(a, has2, hasc, grid, p.lds, st);

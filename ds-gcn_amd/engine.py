@@ -26,7 +26,8 @@ from .train import FlatAdam, FlatSGD, build_optimizer
 class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
-                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1, optimizer=None):
+                 warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1, optimizer=None,
+                 matmul_precision=None):
         """optimizer: mmcv's ``optimizer`` dict (``type`` 'SGD' | 'Adam' | 'AdamW', ..., ``paramwise_cfg``; see
         ``train.build_optimizer``) or a ``FlatSGD`` / ``FlatAdam`` built over ``FlatParams(model, gather=True)`` — in place of
         the keywords lr / momentum / weight_decay / nesterov (and, for a built one, of grad_clip / accumulate, which it
@@ -42,8 +43,13 @@ class TrainEngine:
         accumulate: mmcv's ``GradientCumulativeOptimizerHook.cumulative_iters``.  With k > 1 every ``step()`` is one
         micro-iteration — forward, backward (its own BatchNorm statistics, its own dropout masks), gradient added to the
         accumulator — and every k-th one also averages the k gradients, exchanges, clips and updates, at the rate passed
-        on THAT call: k micro-batches on one GPU are the reference's k ranks.  ``flush()`` closes a short last group."""
+        on THAT call: k micro-batches on one GPU are the reference's k ranks.  ``flush()`` closes a short last group.
+        matmul_precision: 'highest' | 'high' (``kernels.set_matmul_precision``) or None = the process level at this moment.
+        Fixed here: every eager step, capture and replay of this engine runs under it, whatever the process level is set
+        to later and whatever level another engine of the process uses."""
         self.model = model
+        self.matmul_precision = kernels.get_matmul_precision() if matmul_precision is None else matmul_precision
+        kernels.matmul_precision(self.matmul_precision)        # (ValueError for an unknown name)
         if isinstance(optimizer, (FlatSGD, FlatAdam)):
             if optimizer.flat.module is not model or not optimizer.flat.gather or not optimizer.capturable:
                 raise ValueError('TrainEngine(optimizer=...): build it with capturable=True over FlatParams(model, gather=True)')
@@ -136,6 +142,10 @@ class TrainEngine:
     def step(self, keypoint, label, lr=None):
         """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc; grad_norm with grad_clip): no host
         sync here.  With accumulate > 1: one micro-iteration; grad_norm is the one of the last update."""
+        with kernels.matmul_precision(self.matmul_precision):
+            return self._step(keypoint, label, lr)
+
+    def _step(self, keypoint, label, lr):
         if lr is not None:
             self.opt.set_lr(lr)
         key = (tuple(keypoint.shape), tuple(label.shape))

@@ -20,18 +20,21 @@ from .heads import SimpleHead
 
 class InferEngine:
 
-    def __init__(self, model, use_graph=True, warmup_eager=1, strict_graph=False, max_views=None):
+    def __init__(self, model, use_graph=True, warmup_eager=1, strict_graph=False, max_views=None, matmul_precision=None):
         """use_graph: capture one hipGraph per input shape after ``warmup_eager`` eager calls of that shape and replay it
         from then on.  strict_graph: a failed capture raises instead of falling back to eager launches (``capture_error``
         keeps the reason either way; multi-GPU runs: ranks must not silently differ).  max_views: the largest number of
         clips (videos x clips) one forward may hold; a larger batch is cut into chunks of whole videos (a single video is
-        never split), at most two chunk shapes, results concatenated.
+        never split), at most two chunk shapes, results concatenated.  matmul_precision: 'highest' | 'high' or None = the
+        process level at this moment; fixed here for every eager call, capture and replay (see ``TrainEngine``).
 
         The captured graph contains the launches that build the bf16 weight images of the wide convs, so a replay after the
         parameters were changed IN PLACE (an optimizer step, ``load_state_dict``) computes with the new values.  Anything
         that changes tensor addresses or the module tree (``.to()``, ``fuse_conv_bn`` creating a bias, swapping a layer)
         needs ``reset()`` — or build the engine afterwards, as ``test_model`` does."""
         self.model = model
+        self.matmul_precision = kernels.get_matmul_precision() if matmul_precision is None else matmul_precision
+        kernels.matmul_precision(self.matmul_precision)        # (ValueError for an unknown name)
         self._want_graph = bool(use_graph)
         self.warmup_eager = int(warmup_eager)
         self.strict_graph = strict_graph
@@ -128,7 +131,7 @@ class InferEngine:
         if was_training:
             model.eval()
         try:
-            with kernels.private_weight_images(self._images):
+            with kernels.private_weight_images(self._images), kernels.matmul_precision(self.matmul_precision):
                 parts = [self._run(keypoint[a:b]) for a, b in self._chunks(keypoint.shape[0], keypoint.shape[1])]
         finally:
             if was_training:

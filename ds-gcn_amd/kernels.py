@@ -72,6 +72,14 @@ PRESTRIDED = _os.environ.get('DSGCN_PRESTRIDED', '1') != '0'
 # one); '0': the framework's own launches (A/B switch)
 FUSED_ENDS = _os.environ.get('DSGCN_FUSED_ENDS', '1') != '0'
 
+# ---- matmul precision (precision.py) --------------------------------------------------------------------------------
+# DSGCN_MATMUL_PRECISION: 'highest' (default: every fp32 product of a wide conv on six bf16 MFMAs) | 'high' (three) — the
+# level the process starts at; set_matmul_precision / the matmul_precision context manager change it afterwards
+from .precision import (MATMUL_PRECISIONS, get_matmul_precision, matmul_precision, set_matmul_precision,  # noqa: E402,F401
+                        precision_level as _precision_level)
+native.INITIAL_MATMUL_PRECISION = _precision_level(_os.environ.get('DSGCN_MATMUL_PRECISION', 'highest'),
+                                                   'DSGCN_MATMUL_PRECISION')
+
 
 class side_branch:
     """``with side_branch(t): ...`` runs the body on a second HIP stream that first waits for the current one, and

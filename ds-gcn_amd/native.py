@@ -18,6 +18,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), 'include')
 
 _lib = None
 _lab = None
+# matmul precision level the library starts at (kernels.py sets it from DSGCN_MATMUL_PRECISION before the first load)
+INITIAL_MATMUL_PRECISION = 0
 
 c_f = ctypes.c_void_p      # const float* / float*  (device)
 c_i = ctypes.c_void_p      # const int*             (device)
@@ -27,6 +29,10 @@ c_st = ctypes.c_void_p     # hipStream_t
 # name -> argtypes; every entry point returns int (0 ok, >0 hipError_t, <0 argument error)
 SIGNATURES = {
     'dsgcn_version': [],
+    'dsgcn_set_matmul_precision': [c_int],
+    'dsgcn_get_matmul_precision': [],
+    'dsgcn_pwconv_terms': [c_int] * 7,
+    'dsgcn_tconv_terms': [c_int] * 8,
     'dsgcn_aggregate_fwd': [c_f, c_f, c_f, c_int, c_f, c_f, c_int, c_int, c_int, c_int, c_st],
     'dsgcn_aggregate_bwd_partial_rows': [c_int, c_int, c_int],
     'dsgcn_aggregate_bwd': [c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_st],
@@ -348,6 +354,8 @@ def lib():
             fn = getattr(handle, name)      # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
             fn.restype = ctypes.c_size_t if name in SIZE_T_RESULTS else ctypes.c_int
+        if INITIAL_MATMUL_PRECISION:
+            check(handle.dsgcn_set_matmul_precision(INITIAL_MATMUL_PRECISION), 'dsgcn_set_matmul_precision')
         _lib = handle
     return _lib
 

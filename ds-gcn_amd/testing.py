@@ -9,6 +9,7 @@ with the call shape of ``apis.train_model``:
 ``dump_results`` / ``ensemble_results`` end the j / b / jm / bm workflow inside the package: the paper's headline rows are
 sums of four such result files."""
 import json
+import logging
 import os
 import pickle
 
@@ -97,6 +98,7 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
     -> ``dict(results=[...], metrics=OrderedDict | None)``: the scores of every video in dataset order on every rank
     (``(classes,)`` float32 arrays; ``(clips, classes)`` when the model's ``average_clips`` is None, which has no metrics);
     ``metrics`` on rank 0 only.  ``cfg.evaluation.metric_options`` is honoured.  The numpy RNG state is left as found.
+    ``cfg.matmul_precision`` ('highest' | 'high'; absent = the process level) is the level of the pass, logged once.
 
     Under ``test_cfg['feat_ext']`` / ``['score_ext']`` ``results`` holds one float16 array per video — what
     ``forward_test`` returns for that video alone, ``(n', m', C, t', v')`` resp. ``(1, n', m', classes, t', v')`` — and
@@ -130,7 +132,9 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
         model.test_cfg['average_clips'] = average_clips
     try:
         # built AFTER the structural steps above (device move, conv + BatchNorm folding): its graphs hold addresses
-        engine = InferEngine(model, use_graph=use_graph, strict_graph=world > 1)
+        engine = InferEngine(model, use_graph=use_graph, strict_graph=world > 1,
+                             matmul_precision=_get(cfg, 'matmul_precision', None))
+        logging.getLogger('dsgcn_amd').info('test_model: matmul precision: %s', engine.matmul_precision)
         eval_cfg = _get(cfg, 'evaluation', None) or {}
         loop = EvalLoop(dataset, batch_size=test_batch_size(cfg), metrics=list(metrics),
                         metric_options=eval_cfg.get('metric_options'), save_best=None,

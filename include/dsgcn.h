@@ -13,6 +13,10 @@
  *     caller; nothing is allocated or freed; no host/device synchronisation happens inside.
  *   - `stream` is a hipStream_t (NULL = default stream); launches are asynchronous on it; calls on
  *     distinct streams are thread-safe.
+ *   - the matmul precision level (dsgcn_set_matmul_precision) is the one piece of state: PROCESS-WIDE, not per stream
+ *     and not per thread.  It is one atomic integer, read on the host by the call that launches and never by a kernel:
+ *     a launch uses the level at the time of its call, a captured hipGraph keeps the kernels it was captured with, and
+ *     two threads that want different levels must serialise their calls themselves.
  *   - layouts: activations (n, C, T, V) with V fastest ("NCHW"), adjacency (n, C, V, V).
  */
 #ifndef DSGCN_H_
@@ -29,6 +33,26 @@ extern "C" {
 
 /* ABI version (major*100+minor). */
 int dsgcn_version(void);
+
+/* Matmul precision of the kernels that carry an fp32 product on bf16 terms (gfx950 has no TF32 matrix path):
+ *   0 'highest' (default): six v_mfma_f32_32x32x16_bf16 on the exact three-way bf16 split of both operands, fp32-class
+ *                error (the dropped terms are below 2^-24 |a||b|);
+ *   1 'high':    three products on the first two terms of each operand (a0*b0 + a0*b1 + a1*b0), fp32 accumulate: the
+ *                dropped part of a*b is at most 3 * 2^-16 |a||b|.
+ * Honoured by the GEMM-form K-C forward / data gradient on the weight image (k_pwg3h), the wide weight gradients
+ * (k_wg2h, k_wg3h) and the dense temporal conv (k_tcgh, k_tcwh).  Everything else computes the same at both levels: the
+ * fp32 MFMA kernels, the one-pass narrow backward (k_bwd64b) and the GEMM form without a weight image (k_pwg) stay as
+ * they are.  Weight images (dsgcn_pwconv_wsplit, dsgcn_tconv_wsplit) do not depend on the level.
+ * set: 0 or DSGCN_EINVAL (any other level; the level is then unchanged).  get: the current level. */
+int dsgcn_set_matmul_precision(int level);
+int dsgcn_get_matmul_precision(void);
+/* bf16 products per fp32 product of the launch a conv of this shape takes under the CURRENT level: 6 or 3, or 0 when the
+ * shape does not run on bf16 terms at all (fp32 MFMA forms, unsupported shapes).  dir: 0 forward, 1 data gradient,
+ * 2 weight gradient.  dsgcn_pwconv_terms: a plain 1x1 conv (no global-joint column), one input stream on the one-pass
+ * backward shapes, the weight image passed wherever dsgcn_pwconv_wsplit_bytes asks for one.  dsgcn_tconv_terms: the dense
+ * temporal conv of dsgcn_tconv_fwd / _dgrad / _wgrad. */
+int dsgcn_pwconv_terms(int dir, int n, int Ci, int Co, int T, int V, int stride);
+int dsgcn_tconv_terms(int dir, int n, int Ci, int Co, int T, int V, int KT, int stride);
 
 /* K-A gather-aggregate.  Replaces torch.einsum('nkctv,nkcvw->nkctw', pre_x, A)
  * (reference pyskl/models/gcns/utils/gcn.py:2350-2352) fused with the BN+ReLU of `pre`
