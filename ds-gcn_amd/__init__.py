@@ -19,14 +19,15 @@ from .recognizers import RecognizerGCN, reduce_log_vars, gather_results
 from . import kernels
 from .kernels import set_matmul_precision, get_matmul_precision, matmul_precision
 from . import pipeline
-from .pipeline import PIPELINES, DATASETS, Compose, PoseDataset, SkeletonStore, SkeletonBatcher, build_dataset
+from .pipeline import PIPELINES, DATASETS, Compose, PoseDataset, SkeletonStore, SkeletonBatcher, StreamBatcher, build_dataset
 from .data_parallel import FlatParams, FlatDataParallel, shard_batch
 from .train import FlatAdam, FlatSGD, build_optimizer, cosine_lr
 from .paramwise import param_rules
 from .checkpoint import load_checkpoint, save_checkpoint, resume, find_resume, fuse_conv_bn
 from .engine import TrainEngine
 from .apis import train_model, EpochRunner, EvalLoop, epoch_indices, evaluate_scores
-from .infer import InferEngine
-from .testing import test_model, dump_results, load_results, ensemble_results
+from .infer import InferEngine, EnsembleEngine
+from .testing import (test_model, dump_results, load_results, ensemble_results, test_ensemble, parse_stream_weights,
+                      STREAM_WEIGHTS)
 
 __version__ = '0.1.0'

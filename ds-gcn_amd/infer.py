@@ -140,3 +140,182 @@ class InferEngine:
 
     def graphed(self, keypoint):
         return self._key(keypoint) in self._graphs
+
+
+class EnsembleEngine:
+    """The multi-stream test pass (joint + bone + joint motion + bone motion, configs/*/README.md note 2) of S recognizers
+    that belong together, as
+
+        one hipGraph replay per batch shape:  weight images of every model  ->  S x backbone(x_s, pool=True)  ->  head_ensemble
+
+    — the S heads and the weighted sum of their scores are ONE launch (csrc/head_ensemble.hip) whose stream rows and sum
+    have the bits of S ``InferEngine`` passes followed by ``testing.ensemble_results``."""
+
+    MAX_SIDE_STREAMS = 4
+
+    def __init__(self, models, weights, use_graph=True, warmup_eager=1, max_views=None, matmul_precision=None,
+                 concurrent=False):
+        """models: S ``RecognizerGCN``s with a 'GCN' pooling head, the same ``num_classes``, head ``in_channels`` and
+        ``test_cfg['average_clips']`` ('prob' | 'score'), none of them extracting features (ValueError otherwise).
+        weights: S stream weights; they live in a device tensor the head launch reads, so ``set_weights`` is followed by
+        the next replay.  use_graph / warmup_eager / max_views / matmul_precision: as ``InferEngine`` — static buffers
+        inside, copies out, parameters changed in place seen by the next replay, ``reset()`` after a structural change.
+        concurrent: the backbones run as parallel branches on up to four side streams, forked from and joined to the
+        calling stream (in a capture: graph edges); False: back to back on the calling stream."""
+        from .recognizers import RecognizerGCN
+        self.models = list(models)
+        S = len(self.models)
+        if not 1 <= S <= kernels.ENSEMBLE_MAX:
+            raise ValueError(f'EnsembleEngine: {S} models; 1 to {kernels.ENSEMBLE_MAX} streams fit the head launch')
+        weights = [float(w) for w in weights]
+        if len(weights) != S:
+            raise ValueError(f'EnsembleEngine: {S} models, {len(weights)} stream weights')
+        for i, m in enumerate(self.models):
+            head = getattr(m, 'cls_head', None)
+            if not isinstance(m, RecognizerGCN) or not (
+                    isinstance(head, SimpleHead) and type(head).forward is SimpleHead.forward and head.mode == 'GCN'
+                    and head.dropout is None and getattr(m.backbone, 'supports_pool', False)):
+                raise ValueError(f'EnsembleEngine: model {i} is not a RecognizerGCN with a GCNHead over a pooling backbone')
+            if m.extraction() is not None:
+                raise ValueError(f'EnsembleEngine: model {i}: test_cfg feat_ext / score_ext has no weighted sum')
+        h0 = self.models[0].cls_head
+        for i, m in enumerate(self.models):
+            if m.cls_head.num_classes != h0.num_classes or m.cls_head.in_c != h0.in_c:
+                raise ValueError(f'EnsembleEngine: model {i}: head ({m.cls_head.in_c} channels, {m.cls_head.num_classes} '
+                                 f'classes) differs from model 0 ({h0.in_c}, {h0.num_classes})')
+        self._mode()
+        self.matmul_precision = kernels.get_matmul_precision() if matmul_precision is None else matmul_precision
+        kernels.matmul_precision(self.matmul_precision)
+        self._want_graph = bool(use_graph)
+        self.warmup_eager = int(warmup_eager)
+        self.max_views = None if not max_views else int(max_views)
+        self.concurrent = bool(concurrent)
+        self.weights = torch.tensor(weights, dtype=torch.float32, device=next(self.models[0].parameters()).device)
+        self._images = {}
+        self._sides = []
+        self.stream_scores = None
+        self.reset()
+
+    def _mode(self):
+        modes = [m.test_cfg['average_clips'] for m in self.models]
+        if any(md != modes[0] for md in modes) or modes[0] not in ('prob', 'score'):
+            raise ValueError(f"EnsembleEngine: test_cfg['average_clips'] of the models is {modes}: one of 'prob' / 'score' "
+                             'for all (per-clip score lists have no weighted sum)')
+        return modes[0]
+
+    def set_weights(self, weights):
+        """New stream weights, in place: the next call — replayed or not — sums with them."""
+        weights = [float(w) for w in weights]
+        if len(weights) != len(self.models):
+            raise ValueError(f'EnsembleEngine: {len(self.models)} models, {len(weights)} stream weights')
+        self.weights.copy_(torch.tensor(weights, dtype=torch.float32))
+
+    def reset(self):
+        """Forget every captured graph, static buffer and weight image (after a structural change of a model)."""
+        self._graphs = {}          # (shape, dtype, average_clips) -> (graph, static inputs, static sum, static stream scores)
+        self._seen = {}
+        self._images.clear()
+        self.use_graph = self._want_graph
+        self.capture_error = None
+        self.replays = self.eager_calls = 0
+
+    # ---- pieces --------------------------------------------------------------------------------------------
+    def _backbones(self, xs):
+        flat = [x.float().flatten(0, 1) for x in xs]
+        if not self.concurrent or len(flat) == 1:
+            return [m.backbone(x, pool=True) for m, x in zip(self.models, flat)]
+        dev = flat[0].device
+        main = torch.cuda.current_stream(dev)
+        while len(self._sides) < min(len(flat), self.MAX_SIDE_STREAMS):
+            self._sides.append(torch.cuda.Stream(device=dev))
+        feats = []
+        for s, (m, x) in enumerate(zip(self.models, flat)):
+            side = self._sides[s % len(self._sides)]
+            if s < len(self._sides):
+                side.wait_stream(main)                    # fork (a fifth model queues behind the first on its stream)
+            with torch.cuda.stream(side):
+                feats.append(m.backbone(x, pool=True))
+        for side in self._sides[:len(flat)]:
+            main.wait_stream(side)                        # join
+        for f in feats:
+            f.record_stream(main)
+        return feats
+
+    def _forward(self, xs):
+        N, clips, M = xs[0].shape[:3]
+        feats = self._backbones(xs)
+        heads = [(m.cls_head.fc_cls.weight, m.cls_head.fc_cls.bias) for m in self.models]
+        return kernels.head_ensemble([f.reshape(N * clips * M, -1) for f in feats], heads, self.weights, N, clips, M,
+                                     self._mode(), want_streams=True)
+
+    def _capture(self, xs):
+        sx = [x.clone() for x in xs]
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode='thread_local'):
+            out, so = self._forward(sx)
+        torch.cuda.synchronize()
+        return g, sx, out, so
+
+    def _key(self, xs):
+        return tuple(xs[0].shape), xs[0].dtype, self._mode()
+
+    def _run(self, xs):
+        key = self._key(xs)
+        if self.use_graph and key not in self._graphs and self._seen.get(key, 0) >= self.warmup_eager:
+            try:
+                self._graphs[key] = self._capture(xs)
+            except Exception as exc:       # noqa: BLE001 — kept in capture_error; eager launches from here on
+                self.capture_error = f'{type(exc).__name__}: {exc}'
+                self.use_graph = False
+        if self.use_graph and key in self._graphs:
+            g, sx, out, so = self._graphs[key]
+            for d, x in zip(sx, xs):
+                d.copy_(x)
+            g.replay()
+            self.replays += 1
+            return out.clone(), so.clone()     # the static buffers are rewritten by the next replay
+        res = self._forward(xs)
+        self._seen[key] = self._seen.get(key, 0) + 1
+        self.eager_calls += 1
+        return res
+
+    def _chunks(self, N, clips):
+        if self.max_views is None or N * clips <= self.max_views:
+            return [(0, N)]
+        per = max(1, self.max_views // clips)
+        return [(a, min(a + per, N)) for a in range(0, N, per)]
+
+    # ---- the call ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def __call__(self, keypoints):
+        """keypoints: S tensors (N, clips, M, T, V, C) on the device, one per model, of one shape -> DEVICE tensor
+        (N, classes), the weighted sum; ``stream_scores`` (S, N, classes) holds the models' own scores of this call.  No
+        host synchronisation."""
+        xs = list(keypoints)
+        if len(xs) != len(self.models):
+            raise ValueError(f'EnsembleEngine: {len(self.models)} models, {len(xs)} inputs')
+        for x in xs:
+            if x.dim() != 6:
+                raise ValueError(f'EnsembleEngine expects (N, clips, M, T, V, C) per stream, got {tuple(x.shape)}')
+            if not x.is_cuda:
+                raise RuntimeError('EnsembleEngine runs on the GPU only (there is no CPU path): move the batch to the device')
+            if x.shape != xs[0].shape or x.dtype != xs[0].dtype:
+                raise ValueError(f'EnsembleEngine: the streams differ in shape: {[tuple(t.shape) for t in xs]}')
+        was_training = [m.training for m in self.models]
+        for m in self.models:
+            m.eval()
+        try:
+            with kernels.private_weight_images(self._images), kernels.matmul_precision(self.matmul_precision):
+                parts = [self._run([x[a:b] for x in xs]) for a, b in self._chunks(xs[0].shape[0], xs[0].shape[1])]
+        finally:
+            for m, t in zip(self.models, was_training):
+                m.train(t)
+        if len(parts) == 1:
+            out, self.stream_scores = parts[0]
+        else:
+            out, self.stream_scores = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts], 1)
+        return out
+
+    def graphed(self, keypoints):
+        return self._key(list(keypoints)) in self._graphs

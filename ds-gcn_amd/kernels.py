@@ -3118,8 +3118,8 @@ from .kernels_flags import dynadj_flags  # noqa: E402,F401
 from .kernels_plain import dynadj_plain  # noqa: E402,F401
 
 # the ops of the test pass (csrc/head_test.hip's front, the engine-owned weight-image table) live in a module of their own
-from .kernels_infer import (feat_ext, feat_ext_shape, head_test, head_test_fits, parse_pool_opt,  # noqa: E402,F401
-                            private_weight_images)
+from .kernels_infer import (ENSEMBLE_MAX, feat_ext, feat_ext_shape, head_ensemble, head_ensemble_fits,  # noqa: E402,F401
+                            head_test, head_test_fits, parse_pool_opt, private_weight_images)
 
 # the head with class weights / soft labels / multi-label BCE (csrc/head_target.hip) likewise
 from .kernels_head import head_target  # noqa: E402,F401

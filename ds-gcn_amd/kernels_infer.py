@@ -1,4 +1,5 @@
-"""The ops of the test pass: the front of the one-launch test-time head (csrc/head_test.hip, ``dsgcn_head_test_fwd``), the
+"""The ops of the test pass: the front of the one-launch test-time head (csrc/head_test.hip, ``dsgcn_head_test_fwd``), of
+the multi-stream head (csrc/head_ensemble.hip, ``dsgcn_head_ensemble_fwd``), the
 feature / score-map extraction (csrc/featext.hip, ``dsgcn_feat_ext_fwd``) and the switch that gives an
 ``infer.InferEngine`` a weight-image table of its own.  ``dsgcn_amd.kernels`` re-exports them.
 Checked against fp64 by tests/test_infer_gpu.py and tests/test_feat_ext_gpu.py."""
@@ -39,6 +40,62 @@ def head_test(feat, weight, bias, videos, clips, persons, average_clips='prob', 
                                           None if mode == 2 else _K._ptr(out), _K._stream())
     native.check(rc, 'dsgcn_head_test_fwd')
     return (out, cs) if want_clip_scores else out
+
+
+ENSEMBLE_MAX = 8          # dsgcn_head_ensemble_fwd: streams per launch
+
+
+def head_ensemble_fits(clips, C, K):
+    """dsgcn_head_ensemble_fwd passes the streams through the same LDS one after another: ``head_test_fits``' limit,
+    whatever the number of streams."""
+    return head_test_fits(clips, C, K)
+
+
+def head_ensemble(feats, weights_and_biases, stream_weights, videos, clips, persons, average_clips='prob',
+                  want_streams=False):
+    """The test-time heads of S models and their weighted sum in ONE launch (csrc/head_ensemble.hip).
+    feats: S tensors (videos*clips*persons, C) of plane means;  weights_and_biases: S pairs (weight (K, C), bias (K) |
+    None), one C and one K for all;  stream_weights: (S,) float32 DEVICE tensor (read by the launch: a captured graph
+    follows its contents).  -> (videos, K): ((0 + w_0 p_0) + w_1 p_1) + ... in fp32, p_s being ``head_test``'s result for
+    stream s bit for bit — ``ensemble_results`` of the S result sets.  ``want_streams``: -> (sum, (S, videos, K) p_s).
+    ``average_clips`` 'prob' | 'score'; the per-clip mode (None) has no weighted sum: ValueError.  No gradient."""
+    import ctypes
+    if average_clips not in ('prob', 'score'):
+        raise ValueError(f'head_ensemble: average_clips={average_clips!r}: "prob" or "score" (a weighted sum of per-clip '
+                         'score lists is not defined)')
+    S = len(feats)
+    if not 1 <= S <= ENSEMBLE_MAX:
+        raise ValueError(f'head_ensemble: {S} streams; 1 to {ENSEMBLE_MAX} fit one launch')
+    if len(weights_and_biases) != S or stream_weights.numel() != S:
+        raise ValueError(f'head_ensemble: {S} feature tensors, {len(weights_and_biases)} heads, '
+                         f'{stream_weights.numel()} stream weights')
+    N, Q, M = int(videos), int(clips), int(persons)
+    keep, fp, wp, bp = [], [], [], []
+    C = K = None
+    for f, (w, b) in zip(feats, weights_and_biases):
+        _K._require_cuda(f, w, b)
+        f, w, b = _K._f32c(f.detach()), _K._f32c(w.detach()), _K._f32c(None if b is None else b.detach())
+        if C is None:
+            C, K = f.shape[1], w.shape[0]
+        if tuple(f.shape) != (N * Q * M, C) or tuple(w.shape) != (K, C) or (b is not None and tuple(b.shape) != (K,)):
+            raise ValueError(f'head_ensemble: feat {tuple(f.shape)}, weight {tuple(w.shape)}, {N} videos x {Q} clips x '
+                             f'{M} persons, {C} channels and {K} classes do not fit together')
+        keep += [f, w, b]
+        fp.append(_K._ptr(f)); wp.append(_K._ptr(w)); bp.append(_K._ptr(b))
+    _K._require_cuda(stream_weights)
+    if stream_weights.dtype != torch.float32 or not stream_weights.is_contiguous():
+        raise ValueError('head_ensemble: stream_weights is a contiguous float32 tensor on the device')
+    if not head_ensemble_fits(Q, C, K):
+        raise native.DsgcnError(f'dsgcn_head_ensemble_fwd: {Q} clips x ({C} channels + {K} classes) floats exceed the 60 KB '
+                                'of LDS a video may take')
+    out = torch.empty((N, K), device=stream_weights.device, dtype=torch.float32)
+    so = torch.empty((S, N, K), device=stream_weights.device, dtype=torch.float32) if want_streams else None
+    table = ctypes.c_void_p * S
+    rc = native.lib().dsgcn_head_ensemble_fwd(table(*fp), table(*wp), table(*bp), _K._ptr(stream_weights), S, N, Q, M, C, K,
+                                              HEAD_TEST_MODES[average_clips], _K._ptr(so), _K._ptr(out), _K._stream())
+    native.check(rc, 'dsgcn_head_ensemble_fwd')
+    del keep
+    return (out, so) if want_streams else out
 
 
 POOL_BITS = dict(n=1, m=2, t=4, v=8)      # dsgcn_feat_ext_fwd's pool_mask

@@ -128,6 +128,7 @@ SIGNATURES = {
     'dsgcn_gate_fwd': [c_f, c_f, c_int, c_f, c_f] + [c_int] * 5 + [c_st],
     'dsgcn_gate_bwd': [c_f, c_f, c_int, c_f, c_f, c_int, c_f, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_skeleton_prep': [ctypes.c_void_p] * 11 + [c_int] * 10 + [c_st],
+    'dsgcn_skeleton_prep_streams': [ctypes.c_void_p] * 10 + [ctypes.POINTER(ctypes.c_void_p)] + [c_int] * 10 + [c_st],
     'dsgcn_dynadj_partial_stride': [c_int, c_int, c_int],
     'dsgcn_dynadj_fwd': [c_f] * 6 + [c_i, c_i, c_f] + [c_int] * 6 + [c_st],
     'dsgcn_dynadj_bwd': [c_f] * 5 + [c_i, c_i] + [c_f] * 4 + [c_int] * 7 + [c_st],
@@ -160,6 +161,7 @@ SIGNATURES = {
     'dsgcn_head_target_fwd': [c_f] * 4 + [ctypes.c_void_p] + [c_int] * 5 + [ctypes.c_float] + [c_f] * 7 + [c_st],
     'dsgcn_head_target_bwd': [c_f] * 5 + [c_int] * 4 + [ctypes.c_float] + [c_f] * 3 + [c_st],
     'dsgcn_head_test_fwd': [c_f, c_f, c_f] + [c_int] * 6 + [c_f, c_f, c_st],
+    'dsgcn_head_ensemble_fwd': [ctypes.POINTER(ctypes.c_void_p)] * 3 + [c_f] + [c_int] * 7 + [c_f, c_f, c_st],   # HOST tables
     'dsgcn_feat_ext_fwd': [c_f, c_f, c_f] + [c_int] * 8 + [c_f, ctypes.c_void_p, c_st],
     'dsgcn_data_bn_fwd': [c_f] * 10 + [c_int] * 7 + [ctypes.c_float, ctypes.c_float, c_st],
     'dsgcn_data_bn_bwd': [c_f] * 6 + [c_int] * 6 + [c_st],

@@ -910,6 +910,11 @@ class SkeletonBatcher:
 
     def run(self, store, plan):
         """-> (keypoint (N, clips, num_person, clip_len, V, C_out) float32 on the store's device, label (N, 1) int64)."""
+        return self._launch(store, plan, split=False)
+
+    def _launch(self, store, plan, split):
+        """split=False: ``dsgcn_skeleton_prep``, the features side by side in the channels of one tensor.  split=True:
+        ``dsgcn_skeleton_prep_streams``, one (.., C) tensor per feature (-> list, label)."""
         from . import native
         if store.data is None:
             raise RuntimeError('SkeletonStore(plan_only=True) holds no device buffer: nothing to run the kernel on')
@@ -918,33 +923,134 @@ class SkeletonBatcher:
         feats = self.feat.feats
         code = {'j': 0, 'b': 1, 'jm': 2, 'bm': 3}
         C = store.C
-        out = torch.empty((N, self.sample.num_clips, self.num_person, self.sample.clip_len, store.V, C * len(feats)),
-                          device=dev, dtype=torch.float32)
-        parent = torch.from_numpy(bone_parent_table(self.feat.dataset, store.V)).to(dev)
+        lead = (N, self.sample.num_clips, self.num_person, self.sample.clip_len, store.V)
+        if split:
+            outs = [torch.empty(lead + (C,), device=dev, dtype=torch.float32) for _ in feats]
+        else:
+            out = torch.empty(lead + (C * len(feats),), device=dev, dtype=torch.float32)
+        if split:
+            # the decisions go up from pinned staging memory: a copy from pageable memory makes the host wait for everything
+            # queued on the stream — behind a whole ensemble replay that wait would keep the next replay from being prepared
+            # while this one runs (profiles/ensemble/README.md).  The parent table is constant: uploaded once.
+            def up(a):
+                return torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)
+            key = (self.feat.dataset, store.V, dev)
+            if getattr(self, '_parent', (None,))[0] != key:
+                self._parent = (key, torch.from_numpy(bone_parent_table(self.feat.dataset, store.V)).to(dev))
+            parent = self._parent[1]
+        else:
+            def up(a):
+                return torch.from_numpy(a).to(dev, non_blocking=True)
+            parent = torch.from_numpy(bone_parent_table(self.feat.dataset, store.V)).to(dev)
         scored = int(C == 3 and self.feat.dataset in ('openpose', 'coco'))
         # one small H2D copy of the packed decisions (a few hundred bytes per clip)
         ints = np.concatenate([plan['M'], plan['T'], plan['flags'], plan['f0'].reshape(-1), plan['f1'].reshape(-1)]).astype(np.int32)
         flts = np.concatenate([plan['center'].reshape(-1), plan['matrix'].reshape(-1)]).astype(np.float32)
-        d_int = torch.from_numpy(ints).to(dev, non_blocking=True)
-        d_flt = torch.from_numpy(flts).to(dev, non_blocking=True)
-        d_off = torch.from_numpy(plan['offset']).to(dev, non_blocking=True)
+        d_int, d_flt, d_off = up(ints), up(flts), up(plan['offset'])
         fcodes = (code[f] for f in feats)
         fmask = 0
         for i, c in enumerate(fcodes):
             fmask |= c << (2 * i)
         st = torch.cuda.current_stream().cuda_stream
         ip = d_int.data_ptr()
-        rc = native.lib().dsgcn_skeleton_prep(
+        if split:
+            import ctypes
+            entry, name = native.lib().dsgcn_skeleton_prep_streams, 'dsgcn_skeleton_prep_streams'
+            dest = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])     # copied into the kernel arguments
+        else:
+            entry, name, dest = native.lib().dsgcn_skeleton_prep, 'dsgcn_skeleton_prep', out.data_ptr()
+        rc = entry(
             store.data.data_ptr(), d_off.data_ptr(), ip, ip + 4 * N, ip + 8 * N, ip + 12 * N, ip + 12 * N + 4 * N * F,
-            d_flt.data_ptr(), d_flt.data_ptr() + 12 * N, parent.data_ptr(), out.data_ptr(), N, self.sample.num_clips,
+            d_flt.data_ptr(), d_flt.data_ptr() + 12 * N, parent.data_ptr(), dest, N, self.sample.num_clips,
             self.num_person, self.sample.clip_len, store.V, C, len(feats), fmask, scored,
             1 if self.person_mode == 'loop' else 0, st)
-        native.check(rc, 'dsgcn_skeleton_prep')
-        label = torch.from_numpy(plan['label']).to(dev, non_blocking=True).view(N, 1)
-        return out, label
+        native.check(rc, name)
+        label = up(plan['label']).view(N, 1)
+        return (outs if split else out), label
 
     def __call__(self, store, indices):
         return self.run(store, self.plan(store, indices))
+
+
+class StreamBatcher:
+    """S single-feature test (or val) pipelines of the multi-stream workflow (joint, bone, joint motion, bone motion:
+    configs/*/README.md note 2) behind ONE plan and ONE launch per batch.
+
+    The pipelines must be equal once ``GenSkeFeat.feats`` is set aside — the test-mode sampler re-seeds numpy for every
+    clip (sampling.py:103), so equal pipelines pick equal frames and one plan feeds every stream exactly — and each names
+    exactly one feature (channel-concatenated inputs stay with ``SkeletonBatcher``).  ``plan`` is the single-stream
+    plan: the same numpy RNG draws, once per clip.  ``run`` -> (S tensors (N, clips, num_person, clip_len, V, C), label);
+    S = 1 launches what ``SkeletonBatcher`` launches."""
+    MAX_STREAMS = 4               # dsgcn_skeleton_prep_streams: the features of one launch
+
+    def __init__(self, pipelines):
+        pipelines = [list(p) for p in pipelines]
+        if not 1 <= len(pipelines) <= self.MAX_STREAMS:
+            raise ValueError(f'StreamBatcher: {len(pipelines)} pipelines; 1 to {self.MAX_STREAMS} streams share a launch')
+        self.feats = []
+        for i, pipe in enumerate(pipelines):
+            gen = [t for t in pipe if t['type'] == 'GenSkeFeat']
+            if len(gen) != 1:
+                raise ValueError(f'StreamBatcher: pipeline {i} has {len(gen)} GenSkeFeat transforms, one is needed')
+            feats = list(gen[0].get('feats', ['j']))
+            if len(feats) != 1:
+                raise ValueError(f'StreamBatcher: pipeline {i}: GenSkeFeat.feats: {feats} names {len(feats)} features; a '
+                                 'stream has exactly one (channel-concatenated inputs: SkeletonBatcher)')
+            self.feats.append(feats[0])
+            self._same(pipelines[0], pipe, i)
+        merged = [dict(t, feats=list(self.feats)) if t['type'] == 'GenSkeFeat' else dict(t) for t in pipelines[0]]
+        self.batcher = SkeletonBatcher(merged)
+        self.sample, self.num_person, self.person_mode = self.batcher.sample, self.batcher.num_person, self.batcher.person_mode
+
+    @staticmethod
+    def _same(first, other, i):
+        """ValueError naming the first transform and key in which pipeline ``i`` departs from pipeline 0."""
+        absent = '<absent>'
+        for a, b in zip(first, other):
+            if a['type'] != b['type']:
+                raise ValueError(f'StreamBatcher: pipeline {i}: transform {b["type"]} where pipeline 0 has {a["type"]}')
+            for key in list(a) + [k for k in b if k not in a]:
+                if a['type'] == 'GenSkeFeat' and key == 'feats':
+                    continue
+                va, vb = a.get(key, absent), b.get(key, absent)
+                same = (va is absent) == (vb is absent) and (va is absent or _cfg_equal(va, vb))
+                if not same:
+                    raise ValueError(f'StreamBatcher: pipeline {i} differs from pipeline 0: {a["type"]}.{key}: {va} != {vb}')
+        if len(first) != len(other):
+            longer, which = (first, 0) if len(first) > len(other) else (other, i)
+            extra = longer[min(len(first), len(other))]['type']
+            raise ValueError(f'StreamBatcher: pipeline {i} differs from pipeline 0: transform {extra} only in pipeline {which}')
+
+    def __len__(self):
+        return len(self.feats)
+
+    def prepare(self, store, indices=None):
+        return self.batcher.prepare(store, indices)
+
+    def plan(self, store, indices):
+        return self.batcher.plan(store, indices)
+
+    def run(self, store, plan):
+        if len(self.feats) == 1:
+            out, label = self.batcher.run(store, plan)
+            return [out], label
+        return self.batcher._launch(store, plan, split=True)
+
+    def __call__(self, store, indices):
+        return self.run(store, self.plan(store, indices))
+
+
+def _cfg_equal(a, b):
+    """Config values as the transforms see them: a list and a tuple of equal items are the same argument."""
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        return len(a) == len(b) and all(_cfg_equal(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict) and isinstance(b, dict):
+        return set(a) == set(b) and all(_cfg_equal(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return np.array_equal(a, b)
+    if isinstance(a, bool) or isinstance(b, bool):
+        return type(a) is type(b) and a == b
+    return a == b
 
 
 def build_dataset(cfg):

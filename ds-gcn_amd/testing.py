@@ -7,7 +7,8 @@ with the call shape of ``apis.train_model``:
     gather_results -> rank 0 writes ``out`` and evaluates the metrics
 
 ``dump_results`` / ``ensemble_results`` end the j / b / jm / bm workflow inside the package: the paper's headline rows are
-sums of four such result files."""
+sums of four such result files.  ``test_ensemble`` is that workflow as ONE pass: one plan and one input launch per batch
+for all streams, one ``EnsembleEngine`` replay, the stream files and the weighted sum out of the same read-back."""
 import json
 import logging
 import os
@@ -17,7 +18,7 @@ import numpy as np
 
 from .apis import EvalLoop, _get, _rank_world, evaluate_scores
 from .checkpoint import fuse_conv_bn, load_checkpoint
-from .infer import InferEngine
+from .infer import EnsembleEngine, InferEngine
 from .recognizers import gather_results
 
 
@@ -158,3 +159,145 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
 
 
 test_model.__test__ = False
+
+
+STREAM_WEIGHTS = {'two': (1, 1), 'four': (2, 2, 1, 1)}       # the two- and four-stream rows (configs/*/README.md note 2)
+
+
+def parse_stream_weights(weights, streams=None):
+    """'2:2:1:1' | a key of ``STREAM_WEIGHTS`` | a sequence -> tuple of floats; ``streams``: the length it must have."""
+    if isinstance(weights, str):
+        if weights in STREAM_WEIGHTS:
+            vals = STREAM_WEIGHTS[weights]
+        else:
+            try:
+                vals = [float(p) for p in weights.split(':')]
+            except ValueError:
+                raise ValueError(f'stream weights {weights!r}: numbers joined by ":" (e.g. "2:2:1:1") or one of '
+                                 f'{sorted(STREAM_WEIGHTS)}') from None
+    else:
+        vals = list(weights)
+    vals = tuple(float(v) for v in vals)
+    if streams is not None and len(vals) != streams:
+        raise ValueError(f'stream weights {weights!r}: {len(vals)} weights for {streams} streams')
+    return vals
+
+
+def _stream_dataset(cfgs, streams, device):
+    """(SkeletonStore, StreamBatcher) from ``data.test`` of one config per stream: the pipelines may differ in the
+    feature alone, the annotations not at all."""
+    from .pipeline import SkeletonStore, StreamBatcher, build_dataset
+    if len(cfgs) != streams:
+        raise ValueError(f'test_ensemble(dataset=None): {streams} models need {streams} configs, got {len(cfgs)}')
+    tests = [dict((_get(c, 'data', None) or {})['test']) for c in cfgs]
+    batcher = StreamBatcher([t['pipeline'] for t in tests])
+    for i, t in enumerate(tests):
+        for key in sorted((set(t) | set(tests[0])) - {'pipeline'}):
+            if t.get(key) != tests[0].get(key):
+                raise ValueError(f'test_ensemble: data.test of config {i} differs from config 0: {key}: '
+                                 f'{tests[0].get(key)} != {t.get(key)}')
+    first = dict(tests[0], test_mode=True)
+    ds = build_dataset(first)
+    dec = batcher.batcher.decompress
+    opt = None if dec is None else dict(squeeze=dec.squeeze, max_person=dec.max_person)
+    return SkeletonStore(ds.video_infos, device=device, decompress=opt), batcher
+
+
+def test_ensemble(models, dataset, cfg, checkpoints=None, fuse=False, weights='2:2:1:1', out=None, stream_out=None,
+                  metrics=('top_k_accuracy', 'mean_class_accuracy'), average_clips=None, device='cuda', use_graph=True,
+                  concurrent=False):
+    """Score ``dataset`` with the S models of a multi-stream ensemble (joint, bone, joint motion, bone motion) in ONE pass:
+    what S ``test_model`` runs, S result files and ``ensemble_results`` give, bit for bit.
+
+    models: S recognizers (``EnsembleEngine``'s conditions).  dataset: a (``SkeletonStore``, ``StreamBatcher``) pair;
+    ``None``: built from ``data.test`` of ``cfg``, then a list of S configs that differ in ``GenSkeFeat.feats`` alone.
+    cfg: one config, or a list whose first entry gives the batch size (``test_batch_size``), ``evaluation.metric_options``
+    and ``matmul_precision``.  checkpoints: S files (``None`` entries: the model as it is); ``None``: with S configs
+    ``<work_dir>/latest.pth`` of each where it exists.  weights: a sequence or 'a:b:c:d' (``parse_stream_weights``).
+    average_clips: 'prob' / 'score' for this pass, ``None`` = the models' (which must agree).  out / stream_out (S paths):
+    rank 0 writes the summed and the per-stream results through ``dump_results`` — each stream file is what
+    ``test_model`` writes for that model.  concurrent: ``EnsembleEngine(concurrent=...)``.
+
+    -> ``dict(results, metrics, stream_results=[S lists], stream_metrics=[S dicts])``, every list in dataset order on
+    every rank, the metrics on rank 0 only.  The numpy RNG state is left as found."""
+    from .apis import _BatchSource, epoch_indices
+    import torch
+    rank, world = _rank_world()
+    models = list(models)
+    S = len(models)
+    cfgs = list(cfg) if isinstance(cfg, (list, tuple)) else [cfg]
+    cfg0 = cfgs[0]
+    vals = parse_stream_weights(weights, S)
+    if stream_out is not None and len(stream_out) != S:
+        raise ValueError(f'test_ensemble: {S} models, {len(stream_out)} stream_out paths')
+    if checkpoints is not None and len(checkpoints) != S:
+        raise ValueError(f'test_ensemble: {S} models, {len(checkpoints)} checkpoints')
+    if average_clips not in (None, 'prob', 'score'):
+        raise ValueError(f'average_clips={average_clips!r}: "prob", "score" or None (keep the models\' test_cfg)')
+    if dataset is None:
+        dataset = _stream_dataset(cfgs, S, device)
+    if not (isinstance(dataset, (tuple, list)) and len(dataset) == 2 and hasattr(dataset[1], 'plan')
+            and len(dataset[1]) == S):
+        raise ValueError(f'test_ensemble: dataset is a (SkeletonStore, StreamBatcher) pair with {S} streams')
+    if checkpoints is None:
+        checkpoints = [None] * S
+        if len(cfgs) == S:
+            for i, c in enumerate(cfgs):
+                work_dir = _get(c, 'work_dir', None)
+                if work_dir and os.path.exists(os.path.join(work_dir, 'latest.pth')):
+                    checkpoints[i] = os.path.join(work_dir, 'latest.pth')
+    was_training, modes_before = [m.training for m in models], [m.test_cfg['average_clips'] for m in models]
+    for i, ckpt in enumerate(checkpoints):
+        if ckpt is not None:
+            load_checkpoint(models[i], ckpt, map_location='cpu')
+        models[i] = models[i].to(device)
+        models[i].eval()
+        if fuse:
+            fuse_conv_bn(models[i])
+        if average_clips is not None:
+            models[i].test_cfg['average_clips'] = average_clips
+    try:
+        # built AFTER the structural steps above (device move, conv + BatchNorm folding): its graphs hold addresses
+        engine = EnsembleEngine(models, vals, use_graph=use_graph, matmul_precision=_get(cfg0, 'matmul_precision', None),
+                                concurrent=concurrent)
+        logging.getLogger('dsgcn_amd').info('test_ensemble: %d streams, weights %s, matmul precision: %s', S, vals,
+                                            engine.matmul_precision)
+        source = _BatchSource(dataset, next(models[0].parameters()).device)
+        n, batch = len(source), test_batch_size(cfg0)
+        order = epoch_indices(n, 0, 0, rank, world, shuffle=False)
+        sums, streams = [], []
+        rng = np.random.get_state()           # the test-mode sampler seeds numpy per clip: put the stream back afterwards
+        try:
+            for b in range(0, len(order), batch):
+                kps, _ = source.batch(order[b:b + batch])
+                sums.append(engine(kps))
+                streams.append(engine.stream_scores)
+        finally:
+            np.random.set_state(rng)
+        if world > 1 and engine.capture_error is not None:
+            raise RuntimeError(f'test_ensemble: the capture failed on rank {rank}: {engine.capture_error}')
+        packed = torch.cat([torch.cat(sums)[None], torch.cat(streams, 1)]).cpu().numpy()      # the pass's one read-back
+    finally:
+        for m, t, md in zip(models, was_training, modes_before):
+            m.test_cfg['average_clips'] = md
+            m.train(t)
+    results = gather_results(list(packed[0]), n)
+    stream_results = [gather_results(list(packed[1 + s]), n) for s in range(S)]
+    vals_sum, stream_vals = None, [None] * S
+    if rank == 0:
+        if out is not None:
+            dump_results(results, out)
+        for s in range(S if stream_out is not None else 0):
+            dump_results(stream_results[s], stream_out[s])
+        eval_cfg = _get(cfg0, 'evaluation', None) or {}
+        labels = [int(v) for v in dataset[0].labels]
+        vals_sum = evaluate_scores(np.stack(results), labels, list(metrics), eval_cfg.get('metric_options'))
+        stream_vals = [evaluate_scores(np.stack(r), labels, list(metrics), eval_cfg.get('metric_options'))
+                       for r in stream_results]
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    return dict(results=results, metrics=vals_sum, stream_results=stream_results, stream_metrics=stream_vals)
+
+
+test_ensemble.__test__ = False

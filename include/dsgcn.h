@@ -619,6 +619,17 @@ int dsgcn_skeleton_prep(const float* raw, const long* offset, const int* M, cons
                         float* out, int N, int clips, int Mout, int clip_len, int V, int C, int nfeat, int fmask,
                         int scored, int loop, void* stream);
 
+/* dsgcn_skeleton_prep for several single-feature models at once (the joint / bone / joint-motion / bone-motion streams of
+ * one test pass): the arguments and rules of dsgcn_skeleton_prep, except that the nfeat features (1..4, fmask as above) go
+ * to nfeat SEPARATE tensors out[s] (N, clips, Mout, clip_len, V, C) — out is a HOST array of nfeat device pointers, copied
+ * into the kernel arguments.  One thread per output position reads its raw joints and decisions once and writes every
+ * stream; out[s] has the bits dsgcn_skeleton_prep writes for nfeat = 1 with feature s alone.
+ * DSGCN_EINVAL: as dsgcn_skeleton_prep, a NULL out or out[s], nfeat outside 1..4. */
+int dsgcn_skeleton_prep_streams(const float* raw, const long* offset, const int* M, const int* T, const int* flags,
+                                const int* f0, const int* f1, const float* center, const float* matrix,
+                                const int* parent, float* const* out, int N, int clips, int Mout, int clip_len, int V,
+                                int C, int nfeat, int fmask, int scored, int loop, void* stream);
+
 /* Classification head of the training step (csrc/head.hip).  Replaces, for the 'GCN' pooling mode, the person mean +
  * nn.Linear of SimpleHead.forward (pyskl/models/heads/simple_head.py:88-98 after the plane mean), BaseHead.loss
  * (heads/base.py:50-84: top-1 / top-5 accuracy, computed there on the host with numpy, + the loss) and CrossEntropyLoss
@@ -674,6 +685,22 @@ int dsgcn_head_target_bwd(const float* dscore, const float* pooled, const float*
  * 23 clips; every N and M are taken).  C % 4 == 0 with a 16-byte aligned w reads the weights 16 bytes at a time. */
 int dsgcn_head_test_fwd(const float* feat, const float* w, const float* b, int N, int clips, int M, int C, int K, int mode,
                         float* clip_score, float* out, void* stream);
+
+/* The test-time heads of S models (1..8) and their weighted sum (csrc/head_ensemble.hip): what S launches of
+ * dsgcn_head_test_fwd in mode 0 / 1, S result files and a host-side weighted sum give.  ONE launch, one workgroup per
+ * video; the streams pass through the same LDS one after another.
+ *   feat, w, b: HOST arrays of S device pointers (copied into the kernel arguments): feat[s] (N*clips*M, C), w[s] (K, C),
+ *   b[s] (K); b or any b[s] may be NULL.  One C and one K for all streams.   weight (S): DEVICE array, read by the launch
+ *   (a replayed hipGraph follows a changed weight vector).
+ *   stream_out (S, N, K) or NULL: row (s, n) = dsgcn_head_test_fwd's out row n for stream s, bit for bit;
+ *   out (N, K) = ((0 + weight[0] p_0) + weight[1] p_1) + ..., fp32, each product and each sum rounded on its own.
+ *   A non-finite feature of video n in stream s reaches row n of out and row (s, n) of stream_out, nothing else.
+ *   No atomics: repeated launches are bit-identical.
+ * DSGCN_EINVAL: NULL feat / w / weight / out or feat[s] / w[s], S outside 1..8, a non-positive size, mode outside 0..1
+ * (the per-clip mode has no weighted sum).  DSGCN_EUNSUPPORTED: dsgcn_head_test_fwd's LDS limit, whatever S is. */
+int dsgcn_head_ensemble_fwd(const float* const* feat, const float* const* w, const float* const* b, const float* weight,
+                            int S, int N, int clips, int M, int C, int K, int mode, float* stream_out, float* out,
+                            void* stream);
 
 /* Feature / score-map extraction at test time (csrc/featext.hip): recognizergcn.py:68-93 under test_cfg['feat_ext'] /
  * ['score_ext'] — x.mean(axis, keepdim=True) over the axes named in pool_opt, then (score_ext) fc_cls at every remaining
