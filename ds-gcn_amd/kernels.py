@@ -289,6 +289,12 @@ _wsplit_state = dict(epoch=0, batched=-1, jobs={}, in_step=False)
 def _wsplit_image(w2, Ci, Co, nbytes):
     st = _wsplit_state
     jobs = st['jobs']
+    # what the cache keeps is DETACHED (the rule of _StepBuilt below): w2 is a view made inside an autograd forward, and a
+    # view keeps its base — for a weight that is COMPUTED from parameters (msmlp's block-diagonal channel mix) the base
+    # carries last step's graph down to its AccumulateGrad nodes and the (default) stream they were made on, and a capture
+    # of the next step dies in hipStreamEndCapture on the cross-stream dependency autograd inserts.  detach() shares
+    # storage and version counter.
+    w2 = w2.detach()
     key = (w2.data_ptr(), Ci, Co, nbytes, w2.device.index)
     job = jobs.get(key)
     capturing = w2.is_cuda and torch.cuda.is_current_stream_capturing()
