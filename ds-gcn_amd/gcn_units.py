@@ -844,27 +844,35 @@ class unit_ctrgcn(nn.Module):
 
 class CTRHGC(nn.Module):
     """One subset of the heterogeneous CTR unit (reference: gcn.py:668-771).  Owns the parameters; the arithmetic of the K
-    subsets runs batched in ``unit_ctrhgcn.forward_deferred``.  Supported flag set = what the shipped CTR-GCN config
-    reaches (configs/ctrgcn/CTRGCN_model.py through unit_ctrhgcn's per-subset overrides): no node attention, optional
-    edge attention (reduced channels), optional ``ada`` Gram term; target_specific / full_channels / add_type raise."""
+    subsets runs batched in ``unit_ctrhgcn.forward_deferred``.  Every semantic switch acts only under ``semantic_index``:
+    optional edge attention (``edge_att_conv`` to E x the reduced channels, or with ``full_channels`` to E x the output
+    channels; ``add_type`` adds conv4 of the plain difference), optional ``target_specific`` (``nodeconv`` to P x the output
+    channels, each joint keeps the block of its type, added to conv3), optional ``ada`` Gram term.  Node attention under
+    ``semantic_index`` raises: unit_ctrhgcn's per-subset overrides never reach it (gcn.py:807-836)."""
 
     def __init__(self, in_channels, out_channels, rel_reduction=8, node_attention=True, edge_attention=False,
                  target_specific=False, full_channels=False, add_type=False, ada=False, num_types=5, edge_num=15,
                  semantic_index=False):
         super().__init__()
-        if (node_attention and semantic_index) or target_specific or full_channels or add_type:
-            raise NotImplementedError('CTRHGC: node attention / target_specific / full_channels / add_type have no HIP path')
+        if node_attention and semantic_index:
+            raise NotImplementedError('CTRHGC: node attention has no HIP path')
         self.in_channels, self.out_channels = in_channels, out_channels
         self.node_attention, self.edge_attention = node_attention, edge_attention
+        self.target_specific, self.full_channels, self.add_type = target_specific, full_channels, add_type
         self.num_types, self.edge_num, self.ada, self.semantic_index = num_types, edge_num, ada, semantic_index
         if ada:
             self.beta = nn.Parameter(torch.zeros(1))
         self.rel_channels = 8 if in_channels <= 16 else in_channels // rel_reduction
+        # creation order = the reference constructor's (RNG use, state_dict key order): conv1, conv2, [edge_att_conv],
+        # conv4, [nodeconv], conv3
         self.conv1 = nn.Conv2d(in_channels, self.rel_channels, kernel_size=1)
         self.conv2 = nn.Conv2d(in_channels, self.rel_channels, kernel_size=1)
         if edge_attention and semantic_index:
-            self.edge_att_conv = nn.Conv2d(self.rel_channels, edge_num * self.rel_channels, 1)
+            self.edge_att_conv = nn.Conv2d(self.rel_channels, edge_num * (out_channels if full_channels else
+                                                                          self.rel_channels), 1)
         self.conv4 = nn.Conv2d(self.rel_channels, out_channels, kernel_size=1)
+        if target_specific and semantic_index:
+            self.nodeconv = nn.Conv2d(in_channels, num_types * out_channels, kernel_size=1)
         self.conv3 = nn.Conv2d(in_channels, out_channels, 1)
         self.tanh = nn.Tanh()
         _kaiming_conv_init(self)
@@ -874,7 +882,10 @@ class unit_ctrhgcn(nn.Module):
     """Heterogeneous CTR-GCN spatial unit (reference: gcn.py:773-880): like ``unit_ctrgcn`` with a learnable scale per
     subset, an edge-typed attention conv on the first subset (each joint pair keeps the variant of its edge class) and
     the Gram term ``beta_k * x1_k^T x2_k`` (``ada``).  Quirk kept: the constructor's per-subset overrides leave node
-    attention off everywhere and edge attention on for subset 0 only (gcn.py:801-842)."""
+    attention off everywhere and edge attention on for subset 0 only (gcn.py:801-842).  The switches outside the shipped
+    config, all under ``semantic_index`` only: ``target_specific`` — conv3 + the node-typed select of ``nodeconv`` of the
+    three subsets as ONE node-typed conv (``kernels.typed_conv``) with the weights ``W3_k + Wn_k[p]``; ``full_channels`` /
+    ``add_type`` — subset 0's refinement (``kernels.ctr_topology``, edge_mode)."""
 
     def __init__(self, in_channels, out_channels, A, edge_type, node_type, semantic_index=False, rel_reduction=8,
                  node_attention=False, edge_attention=False, target_specific=False, full_channels=False, add_type=False,
@@ -884,6 +895,15 @@ class unit_ctrhgcn(nn.Module):
         self.num_subset = A.shape[0]
         self.register_buffer('edge_type_idx', torch.as_tensor(edge_type).to(torch.int32).reshape(-1).contiguous(),
                              persistent=False)
+        self.target_specific = bool(target_specific and semantic_index)
+        self.num_types = num_types
+        self._plans = {}                 # name of the non-persistent plan buffer -> kernels.TypedPlan (its CPU form)
+        if self.target_specific:
+            self.register_buffer('node_type_idx', torch.as_tensor(node_type).to(torch.int32).reshape(-1).contiguous(),
+                                 persistent=False)
+            self._add_plan('node_plan', self.node_type_idx, num_types)
+        if semantic_index and edge_attention and full_channels:
+            self._add_plan('edge_plan', self.edge_type_idx, edge_num)
         self.convs = nn.ModuleList()
         for i in range(self.num_subset):
             if i == 0:
@@ -914,6 +934,15 @@ class unit_ctrhgcn(nn.Module):
         return [[c.conv1.weight for c in cs] + [c.conv2.weight for c in cs], [c.conv1.bias for c in cs] + [c.conv2.bias for c in cs],
                 [c.conv3.weight for c in cs], [c.conv3.bias for c in cs]]
 
+    def _add_plan(self, name, table, P):
+        """The sorted-by-type tile plan of a type table (kernels.typed_plan) as a non-persistent buffer, like the table."""
+        plan = kernels.typed_plan(table, P)
+        self.register_buffer(name, plan.tensor, persistent=False)
+        self._plans[name] = plan
+
+    def _plan(self, name):
+        return self._plans[name].on(getattr(self, name))
+
     def forward_deferred(self, x, xbar=None, x_res=None):
         ops = kernels.ops()
         x_res = x if x_res is None else x_res
@@ -922,15 +951,30 @@ class unit_ctrhgcn(nn.Module):
         cs = self.convs
         edge = {k: (c.edge_att_conv.weight.flatten(1), c.edge_att_conv.bias, self.edge_type_idx)
                 for k, c in enumerate(cs) if hasattr(c, 'edge_att_conv')}
+        # the edge subsets outside the shipped flags (full_channels / add_type): none -> the call below is today's
+        mode = {k: (bool(cs[k].full_channels), bool(cs[k].add_type), cs[k].edge_num,
+                    self._plan('edge_plan') if cs[k].full_channels else None)
+                for k in edge if cs[k].full_channels or cs[k].add_type}
         beta = torch.cat([c.beta for c in cs]) if all(c.ada for c in cs) else None
         cat = kernels.cat_rows
         ahat = ops.ctr_topology(
             xbar, cat([c.conv1.weight.flatten(1) for c in cs]), cat([c.conv1.bias for c in cs]),
             cat([c.conv2.weight.flatten(1) for c in cs]), cat([c.conv2.bias for c in cs]),
-            [c.conv4.weight.flatten(1) for c in cs], [c.conv4.bias for c in cs], self.alpha, self.A, beta, edge)
+            [c.conv4.weight.flatten(1) for c in cs], [c.conv4.bias for c in cs], self.alpha, self.A, beta, edge,
+            **(dict(edge_mode=mode) if mode else {}))
         w3 = cat([c.conv3.weight.flatten(1) for c in cs])
         b3 = cat([c.conv3.bias for c in cs])
-        x3 = ops.pwconv(x, None, None, None, False, w3, b3, 1, False)[0]
+        if self.target_specific:
+            # x3_k + select(nodeconv_k(x)) of the stacked subsets = ONE node-typed conv with the weights W3_k + Wn_k[p]
+            # (nodeconv row p*Co + o): a KB-sized elementwise op on the parameters (cf. unit_gcn.effective_A); autograd
+            # hands the typed gradient back to conv3 and nodeconv.  Written as (n, K*Co, T, V): what aggregate_sum reads.
+            P, Co, Ci = self.num_types, self.out_c, self.in_c
+            wn = torch.cat([c.nodeconv.weight.view(P, Co, Ci) for c in cs], 1)
+            bn_ = torch.cat([c.nodeconv.bias.view(P, Co) for c in cs], 1)
+            x3 = ops.typed_conv(x, w3.unsqueeze(0) + wn, b3.unsqueeze(0) + bn_, self.node_type_idx, P,
+                                self._plan('node_plan'))
+        else:
+            x3 = ops.pwconv(x, None, None, None, False, w3, b3, 1, False)[0]
         y, ay = op_bn(self.bn, lambda g, b, eps, want: ops.aggregate_sum(x3, ahat, self.num_subset, g, b, eps, want),
                       lambda y: y.shape[0] * y.shape[2] * y.shape[3])
         if self.down is None:

@@ -2691,7 +2691,7 @@ class _EdgeSelect(torch.autograd.Function):
         return din, None, None
 
 
-def ctr_topology(xbar, w1, b1, w2, b2, w4, b4, alpha, A, beta=None, edge=None, subset_major=False):
+def ctr_topology(xbar, w1, b1, w2, b2, w4, b4, alpha, A, beta=None, edge=None, subset_major=False, edge_mode=None):
     """CTR-GCN refined topology.  xbar (n,Ci,V) = mean_T x; w1,w2 (K*R,Ci) / b1,b2 (K*R): conv1/conv2 of the K
     subsets stacked (their mean over T commutes with the 1x1 conv); w4[k] (Co,R), b4[k] (Co); A (K,V,V).
     alpha (1): classic unit_ctrgcn;  alpha (K) [+ beta (K)]: unit_ctrhgcn — per-subset scale and the Gram term
@@ -2699,7 +2699,12 @@ def ctr_topology(xbar, w1, b1, w2, b2, w4, b4, alpha, A, beta=None, edge=None, s
     first passes the edge-typed attention conv + select (gcn.py:737-745).
     -> Ahat (n, K*Co, V, V) = alpha_k * conv4_k(sel_k(tanh(x1_k[u] - x2_k[v]))) + A[k] (+ beta_k G_k).
     subset_major: the caller also takes Ahat as (K, n, Co, V, V) (``aggregate_sum`` does, by strides); the classic unit
-    then comes through the one-conv form below and in that layout."""
+    then comes through the one-conv form below and in that layout.
+    edge_mode = {k: (full_channels, add_type, E, plan)} for edge subsets outside the shipped flags (gcn.py:746-749; absent
+    or (False, False, ..): the path above, untouched).  full_channels: w_edge is (E*Co, R) and the refinement is ONE
+    edge-typed conv R -> Co (``typed_conv`` with the table's ``TypedPlan``), no conv4 behind it; with add_type its
+    weights are We[e] + W4, be[e] + b4.  add_type alone: conv4(sel) + conv4(d) as one conv4 launch over sel + d (the
+    conv's second operand) with the bias counted twice."""
     n, Ci, V = xbar.shape
     K = A.shape[0]
     R = w1.shape[0] // K
@@ -2723,9 +2728,23 @@ def ctr_topology(xbar, w1, b1, w2, b2, w4, b4, alpha, A, beta=None, edge=None, s
     S = []
     for k in range(K):
         dk = d[k]
+        full, add = (edge_mode[k][0], edge_mode[k][1]) if edge_mode and edge and k in edge and k in edge_mode else (False, False)
+        if full:
+            we, be, et = edge[k]
+            E, plan = edge_mode[k][2], edge_mode[k][3]
+            Co = w4[k].shape[0]
+            wt, bt = we.view(E, Co, R), be.view(E, Co)
+            if add:                               # KB-sized elementwise ops on the parameters
+                wt, bt = wt + w4[k].unsqueeze(0), bt + b4[k].unsqueeze(0)
+            S.append(ops().typed_conv(dk, wt, bt, et, E, plan))
+            continue
         if edge and k in edge:
             we, be, et = edge[k]
-            dk = _EdgeSelect.apply(pwconv(dk, None, None, None, False, we, be, 1, False)[0], et, R)
+            sel = _EdgeSelect.apply(pwconv(dk, None, None, None, False, we, be, 1, False)[0], et, R)
+            if add:
+                S.append(pwconv(sel, None, dk, None, False, w4[k], 2.0 * b4[k], 1, False)[0])
+                continue
+            dk = sel
         S.append(pwconv(dk, None, None, None, False, w4[k], b4[k], 1, False)[0])
     G = None
     if beta is not None:      # Gram of the mean-pooled projections per subset (gcn.py:826-835): kernels.gram with one-frame planes
@@ -3129,3 +3148,6 @@ from .kernels_infer import (ENSEMBLE_MAX, feat_ext, feat_ext_shape, head_ensembl
 
 # the head with class weights / soft labels / multi-label BCE (csrc/head_target.hip) likewise
 from .kernels_head import head_target  # noqa: E402,F401
+
+# the position-typed 1x1 conv of CTRHGC's target_specific / full_channels arms (csrc/typedconv.hip) likewise
+from .kernels_typedconv import TypedPlan, typed_conv, typed_plan  # noqa: E402,F401

@@ -112,6 +112,10 @@ SIGNATURES = {
     'dsgcn_edge_select_fwd': [c_f, c_i, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_edge_select_bwd': [c_f, c_i, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_plane_stats': [c_f, c_f, ctypes.c_long, c_int, c_st],
+    'dsgcn_typedconv_fwd': [c_f, c_f, c_f, c_i, c_int, c_f] + [c_int] * 7 + [c_st],
+    'dsgcn_typedconv_dgrad': [c_f, c_f, c_i, c_int, c_f] + [c_int] * 7 + [c_st],
+    'dsgcn_typedconv_wgrad_rows': [c_int] * 4,
+    'dsgcn_typedconv_wgrad': [c_f, c_f, c_i, c_int, c_f] + [c_int] * 7 + [c_st],
     'dsgcn_add3': [c_f, c_f, c_f, c_f, ctypes.c_long, c_st],
     'dsgcn_pack': [c_f, c_f, c_f, c_int, c_f, c_st],
     'dsgcn_pack_fill': [c_f, c_f, c_f, c_int, c_f, c_st],

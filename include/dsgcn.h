@@ -489,6 +489,34 @@ int dsgcn_edge_select_fwd(const float* in, const int* edge_type, float* out, int
 int dsgcn_edge_select_bwd(const float* dout, const int* edge_type, float* din, int n, int R, int E, int V, void* stream);
 int dsgcn_plane_stats(const float* x, float* partial, long planes, int L, void* stream);
 
+/* Position-typed 1x1 conv (csrc/typedconv.hip): CTRHGC's target_specific and full_channels arms (gcn.py:737-766) without
+ * the P x / E x wide intermediate.
+ *   y[n, o, pos] = sum_c w[type(pos)][o][c] * x[n, c, pos] + b[type(pos)][o],   type(pos) = table[pos % L]
+ * x (n, Ci, TV), w (P, Co, Ci), b (P, Co) or NULL, y (n, Co, TV); fp32 in, out and accumulate (v_mfma_f32_32x32x2_f32) at
+ * every matmul precision level; all operands at any 4-byte-aligned address.
+ * plan (int32, device; built once on the host from the table): the positions of one chunk (`chunk` = a whole number of
+ * periods L) sorted by type —
+ *   plan[0 .. 16]                        first tile of type p (entry P .. 16: the tile count)
+ *   plan[17 .. 17 + ntiles)              type of each 32-column tile
+ *   plan[17 + ntiles .. 17 + 33 ntiles)  the chunk positions type by type, ascending inside a type, each type's run padded
+ *                                        with -1 to whole tiles; every position 0 .. chunk-1 appears exactly once
+ * fwd / dgrad write y / dx completely.  dgrad: dx[n, c, pos] = sum_o w[type(pos)][o][c] dy[n, o, pos].
+ * wgrad: part (rows, P*Co*Ci + P*Co), rows = dsgcn_typedconv_wgrad_rows(n, Ci, Co, P): row r holds the sums over its share
+ *   of the samples of dW[p][o][c] = sum_{pos of type p} dy[n, o, pos] x[n, c, pos] and, behind them, db[p][o]; every
+ *   element of every row is written (a type no position carries: exact zeros).  The caller adds the rows in order
+ *   (dsgcn_colsum): no float atomics anywhere, the same bits every run.
+ * DSGCN_EINVAL: NULL x / w / y / plan, a size <= 0, chunk not a multiple of L.  DSGCN_EUNSUPPORTED: P > 16, L > 1024,
+ * chunk > 2048, more tiles than chunk / 32 + P, a tensor of 2^31 elements or more. */
+#define DSGCN_TYPED_MAX_TYPES 16
+#define DSGCN_TYPED_MAX_PERIOD 1024
+int dsgcn_typedconv_fwd(const float* x, const float* w, const float* b, const int* plan, int ntiles, float* y, int n,
+                        int Ci, int Co, int TV, int L, int chunk, int P, void* stream);
+int dsgcn_typedconv_dgrad(const float* dy, const float* w, const int* plan, int ntiles, float* dx, int n, int Ci, int Co,
+                          int TV, int L, int chunk, int P, void* stream);
+int dsgcn_typedconv_wgrad_rows(int n, int Ci, int Co, int P);
+int dsgcn_typedconv_wgrad(const float* x, const float* dy, const int* plan, int ntiles, float* part, int n, int Ci, int Co,
+                          int TV, int L, int chunk, int P, void* stream);
+
 /* out = a + b (+ c), n elements (c may be NULL; 16-B aligned buffers): the gradients of one block input from its
  * consumers (pre conv, residual operand of the temporal unit, block residual: dgstgcn.py:63-65) summed in one pass —
  * replaces autograd's pairwise accumulation. */
