@@ -302,7 +302,7 @@ int dsgcn_tanhdiff_aug_fwd(const float* proj, const float* A, float* d, int n, i
   return 0;
 }
 
-// dd: K gradients (n, R + 2, V, V) (NULL = zero); dproj as dsgcn_tanhdiff_bwd; dAp (n, K, V, V) = the A-channel rows.
+// dd: K gradients (n, R + 2, V, V) (NULL = zero); dproj as dsgcn_tanhdiff_bwd_k; dAp (n, K, V, V) = the A-channel rows.
 int dsgcn_tanhdiff_aug_bwd(const float* d, const float* const* dd, float* dproj, float* dAp, int n, int K, int R, int V,
                            void* stream) {
   if (!d || !dd || !dproj || !dAp || n <= 0 || K <= 0 || K > CTR_MAXK || R <= 0 || V <= 0 || V > 32) return DSGCN_EINVAL;
@@ -340,19 +340,6 @@ int dsgcn_ctr_wprep_multi(const dsgcn_ctr_prep_job* jobs, int njobs, void* strea
   return 0;
 }
 
-// w / b: K device pointers (Co, R) / (Co) or NULL; wout (K, Co, R + 2); sh (K, 2, R + 2) = per subset [scale; shift].
-int dsgcn_ctr_wprep(const float* const* w, const float* const* b, const float* alpha, float* wout, float* sh, int K,
-                    int Co, int R, void* stream) {
-  if (!w || !b || K <= 0 || K > CTR_MAXK) return DSGCN_EINVAL;
-  dsgcn_ctr_prep_job j = {};
-  for (int k = 0; k < K; ++k) {
-    j.w[k] = w[k];
-    j.b[k] = b[k];
-  }
-  j.alpha = alpha, j.wout = wout, j.sh = sh, j.K = K, j.Co = Co, j.R = R;
-  return dsgcn_ctr_wprep_multi(&j, 1, stream);
-}
-
 // The finishing launches of njobs units as one (records: include/dsgcn_jobs.h).
 int dsgcn_ctr_wfin_multi(const dsgcn_ctr_fin_job* jobs, int njobs, void* stream) {
   if (!jobs || njobs <= 0) return DSGCN_EINVAL;
@@ -376,32 +363,6 @@ int dsgcn_ctr_wfin_multi(const dsgcn_ctr_fin_job* jobs, int njobs, void* stream)
                        (hipStream_t)stream, t);
     DSGCN_LAUNCH_CHECK();
   }
-  return 0;
-}
-
-// dwp: K gradients of W'_k (Co, R + 2) or NULL; ds: K gradients of the input scales (R + 2 elements, ds_stride floats
-// apart: 3 when they are read straight out of the K-C backward's summed (channel, 3) rows) or NULL;
-// out: K buffers (Co*R + Co) = [dW_k | db_k]; dalpha (1).
-int dsgcn_ctr_wfin(const float* const* dwp, const float* const* ds, int ds_stride, float* const* out, float* dalpha, int K,
-                   int Co, int R, void* stream) {
-  if (!dwp || !ds || !out || K <= 0 || K > CTR_MAXK) return DSGCN_EINVAL;
-  dsgcn_ctr_fin_job j = {};
-  for (int k = 0; k < K; ++k) {
-    j.dwp[k] = dwp[k];
-    j.ds[k] = ds[k];
-    j.out[k] = out[k];
-  }
-  j.dalpha = dalpha, j.K = K, j.Co = Co, j.R = R, j.ds_stride = ds_stride;
-  return dsgcn_ctr_wfin_multi(&j, 1, stream);
-}
-
-int dsgcn_tanhdiff_bwd(const float* d, const float* dd, float* dproj, int n, int K, int R, int V, void* stream) {
-  if (!d || !dd || !dproj || n <= 0 || K <= 0 || K > CTR_MAXK || R <= 0 || V <= 0 || V > 32) return DSGCN_EINVAL;
-  CtrPtrs p = {};
-  for (int k = 0; k < K; ++k) p.s[k] = dd + (size_t)k * n * R * V * V;
-  hipLaunchKernelGGL(k_tanhdiff_bwd, dim3((unsigned)((long)K * n * R)), dim3(64), (size_t)V * V * sizeof(float),
-                     (hipStream_t)stream, d, p, dproj, n, K, R, V, R, (float*)nullptr);
-  DSGCN_LAUNCH_CHECK();
   return 0;
 }
 

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64) void k_fuse_out_bwd(const float* __restrict__ x
 
 // 16-byte form of k_fuse_out_bwd for planes of T*V % 4 == 0: every stream moves as float4, the loads of an iteration
 // are all issued before its arithmetic, absent streams are compile-time (no predicated loads: those become branches and
-// serial waits).  NG = number of full-size gradient streams (1..3); S3 = the even-frame third stream of fuse_out_fwd2.
+// serial waits).  NG = number of full-size gradient streams (1..3); S3 = the even-frame third stream (out_s2 of the forward).
 template <int NG, bool S3, bool X2>
 __global__ __launch_bounds__(64) void k_fuse_out_bwd4(const float* __restrict__ x1, const float* __restrict__ s1,
                                                       const float* __restrict__ h1, const float* __restrict__ x2,
@@ -331,29 +331,11 @@ int dsgcn_fuse_out_fwd(const float* x1, const float* s1, const float* h1, const 
   return dsgcn_fuse_out_fwd_drop(x1, s1, h1, x2, s2, h2, relu, out, nullptr, xbar, nullptr, n, C, T, V, xbar_ld, nullptr, stream);
 }
 
-// out_s2 (NULL or (n, C, ceil(T/2), V)): the even frames of `out` as a second, contiguous output — the operand of a
-// stride-2 block's 1x1 residual conv (reference: unit_tcn(kernel_size=1, stride=2) of the block residual, dgstgcn.py:35-40)
-int dsgcn_fuse_out_fwd2(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                        const float* h2, int relu, float* out, float* out_s2, float* xbar, int n, int C, int T, int V,
-                        int xbar_ld, void* stream) {
-  if (!out) return DSGCN_EINVAL;
-  return dsgcn_fuse_out_fwd_drop(x1, s1, h1, x2, s2, h2, relu, out, out_s2, xbar, nullptr, n, C, T, V, xbar_ld, nullptr, stream);
-}
-
-// The LAST block's output is only ever averaged over its (T, V) planes by the head (simple_head.py:88-93): pmean (n, C) =
-// plane means of the block output, which is never written (one 82 MB write, its read by the pooling launch, and in the
-// backward the broadcast of the pooled gradient and its read are gone).
-int dsgcn_fuse_out_pool_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                            const float* h2, int relu, float* pmean, int n, int C, int T, int V, void* stream) {
-  if (!pmean) return DSGCN_EINVAL;
-  return dsgcn_fuse_out_fwd_drop(x1, s1, h1, x2, s2, h2, relu, nullptr, nullptr, nullptr, pmean, n, C, T, V, V, nullptr, stream);
-}
-
 // Backward of dsgcn_fuse_out_fwd_drop (the same dropout record: the masks are regenerated).  part: (n*C, 4) per-plane
 // [sum dv1*x1, sum dv, sum dv*x2, sum dv1]; dout or dxbar may be NULL (treated as zero).  dout2 / dout3 (NULL or like dout):
 // the gradients of the other consumers of `out` (the next block reads its input three times) — summed while loading,
 // (dout + dout2) + dout3.  stride3 = 2: dout3 is the gradient of the even-frame output, (n, C, ceil(T/2), V);
-// stride3 = 3: dout is (n*C), the gradient of the plane means (dsgcn_fuse_out_pool_fwd), dout2 / dout3 / dxbar NULL.
+// stride3 = 3: dout is (n*C), the gradient of the plane means (pmean of the forward), dout2 / dout3 / dxbar NULL.
 int dsgcn_fuse_out_bwd_drop(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                             const float* h2, int relu, const float* dout, const float* dout2, const float* dout3,
                             int stride3, const float* dxbar, float* dx1, float* dx2, float* part, int n, int C, int T, int V,
@@ -408,33 +390,6 @@ int dsgcn_fuse_out_bwd_drop(const float* x1, const float* s1, const float* h1, c
   return 0;
 }
 
-// dpmean (n, C): gradient of the plane means; dx1 / dx2 / part as in dsgcn_fuse_out_bwd.
-int dsgcn_fuse_out_pool_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                            const float* h2, int relu, const float* dpmean, float* dx1, float* dx2, float* part, int n,
-                            int C, int T, int V, void* stream) {
-  if (!dpmean) return DSGCN_EINVAL;
-  return dsgcn_fuse_out_bwd_drop(x1, s1, h1, x2, s2, h2, relu, dpmean, nullptr, nullptr, 3, nullptr, dx1, dx2, part, n, C, T, V,
-                                 V, nullptr, stream);
-}
-
-int dsgcn_fuse_out_bwd3(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                        const float* h2, int relu, const float* dout, const float* dout2, const float* dout3,
-                        const float* dxbar, float* dx1, float* dx2, float* part, int n, int C, int T, int V, int xbar_ld,
-                        void* stream) {
-  return dsgcn_fuse_out_bwd_drop(x1, s1, h1, x2, s2, h2, relu, dout, dout2, dout3, 1, dxbar, dx1, dx2, part, n, C, T, V,
-                                 xbar_ld, nullptr, stream);
-}
-
-// stride3 = 2: dout3 is the gradient of dsgcn_fuse_out_fwd2's even-frame output, (n, C, ceil(T/2), V)
-int dsgcn_fuse_out_bwd3s(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                         const float* h2, int relu, const float* dout, const float* dout2, const float* dout3, int stride3,
-                         const float* dxbar, float* dx1, float* dx2, float* part, int n, int C, int T, int V, int xbar_ld,
-                         void* stream) {
-  if (stride3 != 1 && stride3 != 2) return DSGCN_EINVAL;
-  return dsgcn_fuse_out_bwd_drop(x1, s1, h1, x2, s2, h2, relu, dout, dout2, dout3, stride3, dxbar, dx1, dx2, part, n, C, T, V,
-                                 xbar_ld, nullptr, stream);
-}
-
 // mask (numel) = the multipliers dsgcn_fuse_out_fwd_drop applies to the first term of a tensor of numel elements under
 // record d: 1/(1-p) or 0 (tests and debugging: the product never materialises it)
 int dsgcn_dropout_mask(float* mask, long numel, const dsgcn_dropout* d, void* stream) {
@@ -457,8 +412,8 @@ int dsgcn_fuse_out_tuning(int key, int value) {      // key 0: 16-byte backward 
 int dsgcn_fuse_out_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                        const float* h2, int relu, const float* dout, const float* dxbar, float* dx1, float* dx2,
                        float* part, int n, int C, int T, int V, int xbar_ld, void* stream) {
-  return dsgcn_fuse_out_bwd3(x1, s1, h1, x2, s2, h2, relu, dout, nullptr, nullptr, dxbar, dx1, dx2, part, n, C, T, V,
-                             xbar_ld, stream);
+  return dsgcn_fuse_out_bwd_drop(x1, s1, h1, x2, s2, h2, relu, dout, nullptr, nullptr, 1, dxbar, dx1, dx2, part, n, C, T, V,
+                                 xbar_ld, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1891,12 +1891,4 @@ int dsgcn_tms_split_wgrad_jobs(const float* z, const float* zaug, const float* s
   return 0;
 }
 
-int dsgcn_tms_split_wgrad(const float* z, const float* zaug, const float* scale, const float* shift, int n_act,
-                          const float* ge, const float* doaug, int n, int C, int T, int V, int stride, int nbr,
-                          const int* type, const int* c0, const int* bc, const int* dil, float* const* dwp, float* const* dbp,
-                          int splits, int pstride, void* stream) {
-  return dsgcn_tms_split_wgrad_jobs(z, zaug, scale, shift, n_act, ge, doaug, n, C, T, V, stride, nbr, type, c0, bc, dil, dwp,
-                                    dbp, splits, pstride, nullptr, 0, stream);
-}
-
 }  // extern "C"

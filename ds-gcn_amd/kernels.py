@@ -593,9 +593,10 @@ def _launch_fin(jobs):
         native.check(lib.dsgcn_bn_finalize_multi(arr, len(chunk), _stream()), 'dsgcn_bn_finalize_multi')
 
 
-def bn_finalize(partial, rows, Co, count, gamma, beta, eps, mean, var, scale, shift, n_affine):
-    """partial rows -> (mean, var, scale, shift): queued inside a bn_batch() region, launched otherwise."""
-    if _fin_queue is not None:
+def bn_finalize(partial, rows, Co, count, gamma, beta, eps, mean, var, scale, shift, n_affine, queue=True):
+    """partial rows -> (mean, var, scale, shift): queued inside a bn_batch() region (unless queue=False), launched
+    otherwise."""
+    if queue and _fin_queue is not None:
         _fin_queue.append(_fin_job(partial, rows, Co, count, gamma, beta, eps, mean, var, scale, shift, n_affine))
         return
     rc = native.lib().dsgcn_bn_finalize(_ptr(partial), rows, Co, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
@@ -683,30 +684,23 @@ def _flush_coef_wait():
         _launch_coef(jobs)
 
 
-def _bn_feed(bn, part, k, i_ds, i_dh):
-    """consumer side, in backward: partial rows part (R, C, k) -> the producer's coefficients (one launch; for a BatchNorm
-    marked ``host`` the job waits for K-B's backward launch, or for the producer's own backward, whichever comes first)."""
-    _bn_feed_multi([(bn, part, k, i_ds, i_dh)])
-
-
 def _job_array(jobs):
     """-> (ctypes array | None, count) for the `jobs, njobs` arguments of a hosting entry point"""
     return ((native.BnCoefJob * len(jobs))(*jobs) if jobs else None), len(jobs)
 
 
 def _bn_feed_multi(feeds, launch=True):
-    """several consumers' rows in one launch (the two BatchNorms of a two-stream operand: `post` + `down`, ...).
+    """consumer side, in backward: feeds = (bn, part, k, i_ds, i_dh) per BatchNorm — partial rows part (R, C, k) -> the
+    producer's coefficients, several consumers' rows in one launch (the two BatchNorms of a two-stream operand: `post` +
+    `down`, ...); for a BatchNorm marked ``host`` the job waits for K-B's backward launch, or for the producer's own
+    backward, whichever comes first.
     launch=False: -> the jobs, for a caller whose NEXT launch hosts them (a weight gradient: nothing on the critical chain
     waits for it, and the rows come from the data gradient before it) — [] when batching is off (launched here then)."""
     if not BN_BATCH:
-        for bn, part, k, i_ds, i_dh in feeds:
-            C = bn.C
-            R = part.numel() // (C * k)
-            acc = bn.coef is not None
-            if not acc:
-                bn.coef = torch.empty((4, C), device=part.device, dtype=torch.float32)
-            rc = native.lib().dsgcn_bn_coef_rows(_ptr(part), R, C, k, i_ds, i_dh, _ptr(bn.mean), _ptr(bn.var), _ptr(bn.gamma),
-                                                 bn.eps, bn.count, bn.n_affine, _ptr(bn.coef), int(acc), _stream())
+        for feed in feeds:
+            j = _coef_job(*feed)
+            rc = native.lib().dsgcn_bn_coef_rows(j.part, j.R, j.C, j.k, j.i_ds, j.i_dh, j.mean, j.var, j.gamma, j.eps, j.count,
+                                                 j.c_affine, j.coef, j.accumulate, _stream())
             native.check(rc, 'dsgcn_bn_coef_rows')
         return []
     now = []
@@ -744,6 +738,77 @@ def _bn_coef(bn, gscale, gshift, mean, var, gamma, eps, count, C, n_affine):
     return coef[0], coef[1], coef[2], coef[3]
 
 
+# ---- the host-side tails the autograd Functions below share --------------------------------------------------------------
+
+def _finalize_stats(ctx, partial, rows, C, count, gamma, beta, eps, n_affine, queue=False):
+    """producer side, in forward: partial rows -> (mean, var, scale, shift), the rows of one (4, C) block; mean / var are
+    marked non-differentiable.  queue: the finalize may wait in a bn_batch() region (the K-C conv only: every other
+    producer's (scale, shift) is read by its unit's next launch)."""
+    stats = torch.empty((4, C), device=partial.device, dtype=torch.float32)
+    mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
+    bn_finalize(partial, rows, C, count, gamma, beta, eps, mean, var, scale, shift, n_affine, queue)
+    ctx.mark_non_differentiable(mean, var)
+    return mean, var, scale, shift
+
+
+def _trim_affine_grads(dgamma, dbeta, gamma, has_beta, n_affine=None):
+    """(dgamma, dbeta) of _bn_coef -> the gradients the BatchNorm's parameters take: None for an absent parameter, the
+    first n_affine channels otherwise (None: all)."""
+    if dgamma is None:
+        return None, None
+    if n_affine is not None:
+        dgamma, dbeta = dgamma[:n_affine], dbeta[:n_affine]
+    return (dgamma if gamma is not None else None), (dbeta if has_beta else None)
+
+
+def _affine_feeds(part, k, streams):
+    """consumer side, in backward.  part (R, C, k): the partial rows of d scale / d shift a kernel wrote for the affine
+    streams of its virtual input; streams: (scale, bn, i_ds, i_dh) per stream — scale None: absent, bn its BNCtx or None,
+    i_ds / i_dh the columns of part that hold its sums.  -> the _bn_feed_multi feeds when EVERY present affine carries a
+    BNCtx, else None (all or nothing: one column sum then serves all of them)."""
+    live = [(bn, part, k, i_ds, i_dh) for scale, bn, i_ds, i_dh in streams if scale is not None]
+    return live if part is not None and live and all(f[0] is not None for f in live) else None
+
+
+def _affine_pick(red, streams):
+    """-> (ds, dh) per stream, flattened, out of the summed columns red (k, C) (None, None for an absent stream)"""
+    return [g for scale, _, i_ds, i_dh in streams for g in ((red[i_ds], red[i_dh]) if scale is not None else (None, None))]
+
+
+def _affine_tail(part, k, streams, launch=True):
+    """The input-affine tail of a backward -> ((ds, dh) per stream flattened, jobs): the producers' coefficients fed
+    directly (gradients None; jobs: what _bn_feed_multi(launch=False) leaves for the caller's next launch to host), or
+    one column sum of part for all streams."""
+    feeds = _affine_feeds(part, k, streams)
+    if feeds is not None:
+        return [None] * (2 * len(streams)), _bn_feed_multi(feeds, launch)
+    if part is None or all(s[0] is None for s in streams):
+        return [None] * (2 * len(streams)), []
+    return _affine_pick(colsum(part, split_last=True), streams), []
+
+
+def _branch_partials(types, cins, couts, KT, rows, device, has_b):
+    """The weight / bias gradient partials of a unit's conv windows (type 0) in ONE buffer (rows, pstride), a row holding
+    window after window [dW (cout, cin, KT) | db (cout)].  rows: the row count, or a function of pstride giving it.
+    -> (part, dwp, dbp, pstride, split): dwp / dbp = the per-window pointers into row 0 (NULL for the other window types),
+    split(red) -> (dws, dbs), the slices of the summed row (db None where the window has no bias)."""
+    wins, off = [], 0
+    for t, ci, co in zip(types, cins, couts):
+        wins.append((t == 0, off, co * ci * KT, co, ci))
+        if t == 0:
+            off += co * ci * KT + co
+    part = torch.empty((rows(off) if callable(rows) else rows, off), device=device, dtype=torch.float32)
+    base = part.data_ptr()
+    dwp = (_ct.c_void_p * len(wins))(*[base + 4 * o if conv else None for conv, o, _, _, _ in wins])
+    dbp = (_ct.c_void_p * len(wins))(*[base + 4 * (o + nw) if conv else None for conv, o, nw, _, _ in wins])
+
+    def split(red):
+        dws = [red[o:o + nw].view(co, ci, KT, 1) if conv else None for conv, o, nw, co, ci in wins]
+        dbs = [red[o + nw:o + nw + co] if (conv and hb) else None for (conv, o, nw, co, _), hb in zip(wins, has_b)]
+        return dws, dbs
+    return part, dwp, dbp, off, split
+
+
 # ---------------------------------------------------------------------------------------------
 # K-A  gather-aggregate
 # ---------------------------------------------------------------------------------------------
@@ -777,12 +842,7 @@ class _Aggregate(torch.autograd.Function):
         rc = native.lib().dsgcn_aggregate_bwd(_ptr(zp), _ptr(scale), _ptr(shift), ctx.relu, _ptr(ahat), _ptr(dy),
                                               _ptr(dzp), _ptr(dahat), _ptr(partial), n, KC, T, V, _stream())
         native.check(rc, 'dsgcn_aggregate_bwd')
-        dscale = dshift = None
-        if scale is not None and ctx.bn is not None:
-            _bn_feed(ctx.bn, partial, 2, 0, 1)
-        elif scale is not None:
-            red = colsum(partial, split_last=True)
-            dscale, dshift = red[0], red[1]
+        (dscale, dshift), _ = _affine_tail(partial, 2, [(scale, ctx.bn, 0, 1)])
         return dzp, dscale, dshift, None, dahat
 
 
@@ -1138,10 +1198,8 @@ class _PwConv(torch.autograd.Function):
         scale = shift = mean = var = None
         count = float(n * Tout * (V + (1 if aug else 0)))
         if want_bn:
-            stats = torch.empty((4, Co), device=dev, dtype=torch.float32)
-            mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
-            bn_finalize(partial, partial.shape[0], Co, count, gamma, beta, eps, mean, var, scale, shift, n_affine)
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale, shift = _finalize_stats(ctx, partial, partial.shape[0], Co, count, gamma, beta, eps, n_affine,
+                                                      queue=True)
         ctx.set_materialize_grads(False)      # no zero tensors for the unused / non-differentiable outputs (mean, var)
         ctx.save_for_backward(x1, s1, h1, x2, s2, h2, w2, z, zaug, gamma, mean, var, ws)
         ctx.cfg = (int(relu), stride, int(aug), float(eps), int(n_affine), bool(want_bn), count, tuple(weight.shape),
@@ -1250,19 +1308,17 @@ class _PwConv(torch.autograd.Function):
         wpart = torch.empty((splits, pstride), device=dev, dtype=torch.float32)
         sink = ctx.sink is not None and bool(ctx.sink)
         # the input BatchNorms' coefficient jobs (rows: the data gradient above) ride in the weight gradient's launch
-        hosted, fed = [], False
-        if (ipart is not None and not (sink and _deferred is not None) and (s1 is None or ctx.bn1 is not None) and
-                (s2 is None or ctx.bn2 is not None)):
-            hosted = _bn_feed_multi(([(ctx.bn1, ipart, 3, 0, 1)] if s1 is not None else []) +
-                                    ([(ctx.bn2, ipart, 3, 2, 1)] if s2 is not None else []), launch=False)
-            fed = True
+        feeds = None
+        if not (sink and _deferred is not None):
+            feeds = _affine_feeds(ipart, 3, [(s1, ctx.bn1, 0, 1), (s2, ctx.bn2, 2, 1)])
+        hosted = _bn_feed_multi(feeds, launch=False) if feeds is not None else []
         rc = lib.dsgcn_pwconv_wgrad_jobs(_ptr(x1), _ptr(s1), _ptr(h1), _ptr(x2), _ptr(s2), _ptr(h2), relu, _ptr(z),
                                          _ptr(zaug), _ptr(gz), _ptr(gzaug), _ptr(A0), _ptr(B0), wpart.data_ptr(),
                                          wpart.data_ptr() + 4 * Co * Ci, pstride, n, Ci, Co, T, V, stride, aug,
                                          *_job_array(hosted), st)
         native.check(rc, 'dsgcn_pwconv_wgrad_jobs')
         return _PwConv._finish(wpart, ipart, dx1, dx2, s1, s2, Co, Ci, wshape, has_bias, dgamma, dbeta, gamma, has_beta,
-                               n_affine, ctx.defer_ok, ctx.bn1, ctx.bn2, sink, fed)
+                               n_affine, ctx.defer_ok, ctx.bn1, ctx.bn2, sink, feeds is not None)
 
     @staticmethod
     def _finish(wpart, ipart, dx1, dx2, s1, s2, Co, Ci, wshape, has_bias, dgamma, dbeta, gamma, has_beta, n_affine,
@@ -1278,12 +1334,12 @@ class _PwConv(torch.autograd.Function):
                 ds1, dh1 = red[:, 0], red[:, 1]
             return (dx1, ds1, dh1, dx2, None, None, None, wsum[:Co * Ci].view(wshape), None, None, None, None, None, None,
                     None, None, None, None, None)
-        fed = ipart is not None and (s1 is None or bn1 is not None) and (s2 is None or bn2 is not None)
-        if fed and already_fed:
-            ipart = None
-        elif fed:
+        streams = [(s1, bn1, 0, 1), (s2, bn2, 2, 1)]
+        feeds = _affine_feeds(ipart, 3, streams)
+        if feeds is not None:
             # every affine of the virtual input belongs to a deferred BatchNorm that takes its coefficients directly
-            _bn_feed_multi(([(bn1, ipart, 3, 0, 1)] if s1 is not None else []) + ([(bn2, ipart, 3, 2, 1)] if s2 is not None else []))
+            if not already_fed:
+                _bn_feed_multi(feeds)
             ipart = None
         if ipart is not None and (_deferred is None or not defer_ok):
             wsum, red = colsum_pair(wpart, ipart, split_last_b=True)
@@ -1295,15 +1351,8 @@ class _PwConv(torch.autograd.Function):
             wsum = param_colsum(wpart, defer_ok)
         dw = wsum[:Co * Ci].view(wshape)
         db = wsum[Co * Ci:] if has_bias else None
-        ds1 = dh1 = ds2 = dh2 = None
-        if ipart is not None:
-            if s1 is not None:
-                ds1, dh1 = red[0], red[1]
-            if s2 is not None:
-                ds2, dh2 = red[2], red[1]
-        if dgamma is not None:
-            dgamma = dgamma[:n_affine] if gamma is not None else None
-            dbeta = dbeta[:n_affine] if has_beta else None
+        ds1, dh1, ds2, dh2 = _affine_pick(red, streams) if ipart is not None else [None] * 4
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta, n_affine)
         return (dx1, ds1, dh1, dx2, ds2, dh2, None, dw, db, None, None, dgamma, dbeta, None, None, None, None, None, None)
 
 
@@ -1477,11 +1526,8 @@ class _BranchAct(torch.autograd.Function):
         rc = native.lib().dsgcn_branch_act_bwd(_ptr(z), _ptr(zaug), _ptr(scale), _ptr(shift), ctx.n_act, _ptr(dh),
                                                _ptr(dz), _ptr(dzaug), _ptr(part), n, C, T, V, _stream())
         native.check(rc, 'dsgcn_branch_act_bwd')
-        if ctx.bn is not None:
-            _bn_feed(ctx.bn, part, 2, 0, 1)
-            return dz, dzaug, None, None, None
-        red = colsum(part, split_last=True)
-        return dz, dzaug, red[0], red[1], None
+        (dscale, dshift), _ = _affine_tail(part, 2, [(scale, ctx.bn, 0, 1)])
+        return dz, dzaug, dscale, dshift, None
 
 
 class _TmsCombine(torch.autograd.Function):
@@ -1503,12 +1549,7 @@ class _TmsCombine(torch.autograd.Function):
         scale = shift = mean = var = None
         count = float(n * T * V)
         if want_bn:
-            stats = torch.empty((4, C), device=dev, dtype=torch.float32)
-            mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
-            rc = lib.dsgcn_bn_finalize(_ptr(partial), n, C, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                       _ptr(var), _ptr(scale), _ptr(shift), C, _stream())
-            native.check(rc, 'dsgcn_bn_finalize')
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale, shift = _finalize_stats(ctx, partial, n, C, count, gamma, beta, eps, C)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(o, coeff, gamma, mean, var)
         ctx.cfg = (float(eps), bool(want_bn), count, beta is not None)
@@ -1533,9 +1574,7 @@ class _TmsCombine(torch.autograd.Function):
                                        T, V, _stream())
         native.check(rc, 'dsgcn_tms_combine_bwd')
         dcoeff = param_colsum(pcoef, ctx.defer_ok)
-        if dgamma is not None:
-            dgamma = dgamma if gamma is not None else None
-            dbeta = dbeta if has_beta else None
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta)
         return do, dcoeff, dgamma, dbeta, None, None, None
 
 
@@ -1590,38 +1629,24 @@ class _TapBranches(torch.autograd.Function):
         Tout = go.shape[2]
         if 0 not in types:                 # pooling / pass-through windows only: nothing to learn
             return (dh, None, None, None, None, None, None, None, None, None, *([None] * (2 * nbr)))
-        offs, off = [], 0
-        for t, ci, co in zip(types, cins, couts):
-            offs.append(off)
-            if t == 0:
-                off += co * ci * KT + co
-        pstride = max(off, 1)
-        # k-splits: enough blocks to fill the chip, but keep the partial buffer (splits x pstride floats) around 8 MB
-        wmax = max([max(ci, co) for t, ci, co in zip(types, cins, couts) if t == 0] or [0])
-        pref = lib.dsgcn_tapconv_wgrad_splits(n, Cin, Cout, T, V1, stride, KT, nbr, tabs[0], tabs[3], tabs[4], tabs[5])
-        if pref > 0:        # wide-load kernel (csrc/tapconv.hip k_tapw): one partial row per workgroup
-            splits = pref
-        elif wmax <= 32:    # narrow windows: every wave is its own split (csrc/tapconv.hip k_tapconv_wgrad_narrow)
-            splits = max(64, min(1024, (1 << 21) // pstride)) // 4 * 4
-            splits = max(4, min(splits, (n * Tout) // 4 * 4))
-        else:
+        def splits_for(pstride):
+            # k-splits: enough blocks to fill the chip, but keep the partial buffer (splits x pstride floats) around 8 MB
+            wmax = max(max(ci, co) for t, ci, co in zip(types, cins, couts) if t == 0)
+            pref = lib.dsgcn_tapconv_wgrad_splits(n, Cin, Cout, T, V1, stride, KT, nbr, tabs[0], tabs[3], tabs[4], tabs[5])
+            if pref > 0:        # wide-load kernel (csrc/tapconv.hip k_tapw): one partial row per workgroup
+                return pref
+            if wmax <= 32:      # narrow windows: every wave is its own split (csrc/tapconv.hip k_tapconv_wgrad_narrow)
+                splits = max(64, min(1024, (1 << 21) // pstride)) // 4 * 4
+                return max(4, min(splits, (n * Tout) // 4 * 4))
             # wide windows: ~512 workgroups over (64x64 tiles) x (K-splits), partial buffer capped at 64 MB
             tiles = sum(((ci + 63) // 64) * ((co + 63) // 64) for t, ci, co in zip(types, cins, couts) if t == 0)
             splits = max(16, min(256, 512 // max(tiles, 1), (1 << 24) // pstride))
-            splits = max(1, min(splits, n * ((Tout + 1) // 2)))
-        part = torch.empty((splits, pstride), device=h.device, dtype=torch.float32)
-        base = part.data_ptr()
-        dwp = (_ct.c_void_p * nbr)(*[base + 4 * o if t == 0 else None for t, o in zip(types, offs)])
-        dbp = (_ct.c_void_p * nbr)(*[base + 4 * (o + co * ci * KT) if t == 0 else None
-                                     for t, o, ci, co in zip(types, offs, cins, couts)])
-        rc = lib.dsgcn_tapconv_wgrad(_ptr(h), _ptr(go), n, Cin, Cout, T, V1, stride, KT, nbr, *tabs, dwp, dbp, splits,
+            return max(1, min(splits, n * ((Tout + 1) // 2)))
+        part, dwp, dbp, pstride, split = _branch_partials(types, cins, couts, KT, splits_for, h.device, has_b)
+        rc = lib.dsgcn_tapconv_wgrad(_ptr(h), _ptr(go), n, Cin, Cout, T, V1, stride, KT, nbr, *tabs, dwp, dbp, part.shape[0],
                                      pstride, _stream())
         native.check(rc, 'dsgcn_tapconv_wgrad')
-        red = param_colsum(part, ctx.defer_ok)
-        dws = [red[o:o + co * ci * KT].view(co, ci, KT, 1) if t == 0 else None
-               for t, o, ci, co in zip(types, offs, cins, couts)]
-        dbs = [red[o + co * ci * KT:o + co * ci * KT + co] if (t == 0 and hb) else None
-               for t, o, ci, co, hb in zip(types, offs, cins, couts, has_b)]
+        dws, dbs = split(param_colsum(part, ctx.defer_ok))
         return (dh, None, None, None, None, None, None, None, None, None, *dws, *dbs)
 
 
@@ -1682,12 +1707,7 @@ class _TemporalFused(torch.autograd.Function):
         scale1 = shift1 = mean = var = None
         count = float(n * Tout * V)
         if want_bn:
-            st = torch.empty((4, C), device=dev, dtype=torch.float32)
-            mean, var, scale1, shift1 = st[0], st[1], st[2], st[3]
-            rc = lib.dsgcn_bn_finalize(_ptr(stats), rows, C, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                       _ptr(var), _ptr(scale1), _ptr(shift1), C, _stream())
-            native.check(rc, 'dsgcn_bn_finalize')
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale1, shift1 = _finalize_stats(ctx, stats, rows, C, count, gamma, beta, eps, C)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z, zaug, scale, shift, coeff, f, oaug, gamma, mean, var, *[w for w in ws if w is not None])
         ctx.cfg = (int(n_act), int(stride), int(KT), tuple(types), tuple(c0s), tuple(bcs), tuple(dils), float(eps),
@@ -1723,38 +1743,17 @@ class _TemporalFused(torch.autograd.Function):
                                  _ptr(A0), _ptr(B0), _ptr(oaug), _ptr(dz), _ptr(dzaug), _ptr(paff), _ptr(pcoeff), n, C, T,
                                  V, stride, KT, nbr, *tabs, _ptr_array(ws), st)
         native.check(rc, 'dsgcn_tms_dgrad')
-        dscale = dshift = dcoeff = None
-        if scale is not None and ctx.bn_in is not None:
-            _bn_feed(ctx.bn_in, paff, 2, 0, 1)
-        elif scale is not None:
-            red = colsum(paff, split_last=True)
-            dscale, dshift = red[0], red[1]
-        if aug:
-            dcoeff = param_colsum(pcoeff, ctx.defer_ok)
+        (dscale, dshift), _ = _affine_tail(paff, 2, [(scale, ctx.bn_in, 0, 1)])
+        dcoeff = param_colsum(pcoeff, ctx.defer_ok) if aug else None
         dws, dbs = [None] * nbr, [None] * nbr
         if 0 in types:
-            offs, off = [], 0
-            for t, bc in zip(types, bcs):
-                offs.append(off)
-                if t == 0:
-                    off += bc * bc * KT + bc
-            pstride = off
             rows2 = lib.dsgcn_tms_rows(2, n, C, T, V, stride, KT, nbr, tabs[0], tabs[2], tabs[3], int(aug))
-            part = torch.empty((rows2, pstride), device=dev, dtype=torch.float32)
-            base = part.data_ptr()
-            dwp = (_ct.c_void_p * nbr)(*[base + 4 * o if t == 0 else None for t, o in zip(types, offs)])
-            dbp = (_ct.c_void_p * nbr)(*[base + 4 * (o + bc * bc * KT) if t == 0 else None
-                                         for t, o, bc in zip(types, offs, bcs)])
+            part, dwp, dbp, pstride, split = _branch_partials(types, bcs, bcs, KT, rows2, dev, has_b)
             rc = lib.dsgcn_tms_wgrad(_ptr(z), _ptr(zaug), _ptr(scale), _ptr(shift), n_act, _ptr(coeff), _ptr(gf), _ptr(f),
                                      _ptr(A0), _ptr(B0), n, C, T, V, stride, KT, nbr, *tabs, dwp, dbp, pstride, st)
             native.check(rc, 'dsgcn_tms_wgrad')
-            red = param_colsum(part, ctx.defer_ok)
-            dws = [red[o:o + bc * bc * KT].view(bc, bc, KT, 1) if t == 0 else None for t, o, bc in zip(types, offs, bcs)]
-            dbs = [red[o + bc * bc * KT:o + bc * bc * KT + bc] if (t == 0 and hb) else None
-                   for t, o, bc, hb in zip(types, offs, bcs, has_b)]
-        if dgamma is not None:
-            dgamma = dgamma if gamma is not None else None
-            dbeta = dbeta if has_beta else None
+            dws, dbs = split(param_colsum(part, ctx.defer_ok))
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta)
         return (dz, dzaug, dscale, dshift, dcoeff, dgamma, dbeta, None, None, None, None, None, None, None, None, None,
                 None, *dws, *dbs)
 
@@ -1793,12 +1792,7 @@ class _TemporalSplit(torch.autograd.Function):
         scale1 = shift1 = mean = var = None
         count = float(n * To * V)
         if want_bn:
-            st = torch.empty((4, C), device=dev, dtype=torch.float32)
-            mean, var, scale1, shift1 = st[0], st[1], st[2], st[3]
-            rc = lib.dsgcn_bn_finalize(_ptr(stats), rows, C, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                       _ptr(var), _ptr(scale1), _ptr(shift1), C, _stream())
-            native.check(rc, 'dsgcn_bn_finalize')
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale1, shift1 = _finalize_stats(ctx, stats, rows, C, count, gamma, beta, eps, C)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(z, zaug, scale, shift, coeff, f, oaug, gamma, mean, var, *[w for w in ws if w is not None])
         ctx.cfg = (int(n_act), int(stride), tuple(types), tuple(c0s), tuple(bcs), tuple(dils), float(eps), bool(want_bn),
@@ -1840,36 +1834,15 @@ class _TemporalSplit(torch.autograd.Function):
         rc = lib.dsgcn_tms_split_dgrad(_ptr(z), _ptr(zaug), _ptr(scale), _ptr(shift), n_act, _ptr(ge), _ptr(doaug), _ptr(dz),
                                        _ptr(dzaug), _ptr(part), n, C, T, V, stride, nbr, *tabs, _ptr_array(ws), st)
         native.check(rc, 'dsgcn_tms_split_dgrad')
-        dscale = dshift = None
-        hosted = []
-        if ctx.bn_in is not None:
-            # the branch BatchNorm's coefficient job rides in the weight gradient's launch below (nothing waits for that one)
-            hosted = _bn_feed_multi([(ctx.bn_in, part, 2, 0, 1)], launch=False)
-        elif scale is not None:
-            red = colsum(part, split_last=True)
-            dscale, dshift = red[0], red[1]
-        offs, off = [], 0
-        for t, bc in zip(types, bcs):
-            offs.append(off)
-            if t == 0:
-                off += bc * bc * 3 + bc
-        pstride = off
+        # the branch BatchNorm's coefficient job rides in the weight gradient's launch below (nothing waits for that one)
+        (dscale, dshift), hosted = _affine_tail(part, 2, [(scale, ctx.bn_in, 0, 1)], launch=False)
         splits = lib.dsgcn_tms_split_rows(2, n, C, T, V, stride, 3, nbr, *tabs)
-        wpart = torch.empty((splits, pstride), device=dev, dtype=torch.float32)
-        base = wpart.data_ptr()
-        dwp = (_ct.c_void_p * nbr)(*[base + 4 * o if t == 0 else None for t, o in zip(types, offs)])
-        dbp = (_ct.c_void_p * nbr)(*[base + 4 * (o + bc * bc * 3) if t == 0 else None
-                                     for t, o, bc in zip(types, offs, bcs)])
+        wpart, dwp, dbp, pstride, split = _branch_partials(types, bcs, bcs, 3, splits, dev, has_b)
         rc = lib.dsgcn_tms_split_wgrad_jobs(_ptr(z), _ptr(zaug), _ptr(scale), _ptr(shift), n_act, _ptr(ge), _ptr(doaug), n, C,
                                             T, V, stride, nbr, *tabs, dwp, dbp, splits, pstride, *_job_array(hosted), st)
         native.check(rc, 'dsgcn_tms_split_wgrad_jobs')
-        red = param_colsum(wpart, ctx.defer_ok)
-        dws = [red[o:o + bc * bc * 3].view(bc, bc, 3, 1) if t == 0 else None for t, o, bc in zip(types, offs, bcs)]
-        dbs = [red[o + bc * bc * 3:o + bc * bc * 3 + bc] if (t == 0 and hb) else None
-               for t, o, bc, hb in zip(types, offs, bcs, has_b)]
-        if dgamma is not None:
-            dgamma = dgamma if gamma is not None else None
-            dbeta = dbeta if has_beta else None
+        dws, dbs = split(param_colsum(wpart, ctx.defer_ok))
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta)
         return (dz, dzaug, dscale, dshift, dcoeff, dgamma, dbeta, None, None, None, None, None, None, None, None, None,
                 *dws, *dbs)
 
@@ -1957,13 +1930,8 @@ class _PlaneStats(torch.autograd.Function):
         lib = native.lib()
         partial = torch.empty((n, C, 2), device=dev, dtype=torch.float32)
         native.check(lib.dsgcn_plane_stats(_ptr(o), _ptr(partial), n * C, T * V, _stream()), 'dsgcn_plane_stats')
-        stats = torch.empty((4, C), device=dev, dtype=torch.float32)
-        mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
         count = float(n * T * V)
-        rc = lib.dsgcn_bn_finalize(_ptr(partial), n, C, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                   _ptr(var), _ptr(scale), _ptr(shift), C, _stream())
-        native.check(rc, 'dsgcn_bn_finalize')
-        ctx.mark_non_differentiable(mean, var)
+        mean, var, scale, shift = _finalize_stats(ctx, partial, n, C, count, gamma, beta, eps, C)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(o, gamma, mean, var)
         ctx.cfg = (float(eps), count, beta is not None)
@@ -2141,12 +2109,7 @@ class _TConvGemm(torch.autograd.Function):
         scale = shift = mean = var = None
         count = float(n * To * V)
         if want_bn:
-            stats = torch.empty((4, Co), device=dev, dtype=torch.float32)
-            mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
-            rc = lib.dsgcn_bn_finalize(_ptr(partial), rows, Co, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                       _ptr(var), _ptr(scale), _ptr(shift), Co, _stream())
-            native.check(rc, 'dsgcn_bn_finalize')
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale, shift = _finalize_stats(ctx, partial, rows, Co, count, gamma, beta, eps, Co)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x1, s1, h1, x2, s2, h2, z, gamma, mean, var, ws)
         ctx.cfg = (int(relu), float(eps), bool(want_bn), count, tuple(w.shape), bias is not None, beta is not None,
@@ -2188,19 +2151,8 @@ class _TConvGemm(torch.autograd.Function):
         red = param_colsum(part, ctx.defer_ok)
         dw = red[:Co * Ci * KT].view(wshape)
         db = red[Co * Ci * KT:] if has_bias else None
-        ds1 = dh1 = ds2 = dh2 = None
-        if ipart is not None and (s1 is None or ctx.bn1 is not None) and (s2 is None or ctx.bn2 is not None):
-            _bn_feed_multi(([(ctx.bn1, ipart, 3, 0, 1)] if s1 is not None else []) +
-                           ([(ctx.bn2, ipart, 3, 2, 1)] if s2 is not None else []))
-        elif ipart is not None:
-            isum = colsum(ipart, split_last=True)
-            if s1 is not None:
-                ds1, dh1 = isum[0], isum[1]
-            if s2 is not None:
-                ds2, dh2 = isum[2], isum[1]
-        if dgamma is not None:
-            dgamma = dgamma if gamma is not None else None
-            dbeta = dbeta if has_beta else None
+        (ds1, dh1, ds2, dh2), _ = _affine_tail(ipart, 3, [(s1, ctx.bn1, 0, 1), (s2, ctx.bn2, 2, 1)])
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta)
         return dx1, ds1, dh1, dx2, ds2, dh2, None, dw, db, dgamma, dbeta, None, None, None, None
 
 
@@ -2272,12 +2224,7 @@ class _AggSum(torch.autograd.Function):
         scale = shift = mean = var = None
         count = float(n * T * V)
         if want_bn:
-            stats = torch.empty((4, Co), device=dev, dtype=torch.float32)
-            mean, var, scale, shift = stats[0], stats[1], stats[2], stats[3]
-            rc = lib.dsgcn_bn_finalize(_ptr(partial), prow, Co, count, _ptr(gamma), _ptr(beta), float(eps), _ptr(mean),
-                                       _ptr(var), _ptr(scale), _ptr(shift), Co, _stream())
-            native.check(rc, 'dsgcn_bn_finalize')
-            ctx.mark_non_differentiable(mean, var)
+            mean, var, scale, shift = _finalize_stats(ctx, partial, prow, Co, count, gamma, beta, eps, Co)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(p, adj, y, gamma, mean, var)
         ctx.cfg = (K, float(eps), bool(want_bn), count, beta is not None, shared, astr, bool(per_sample))
@@ -2317,9 +2264,7 @@ class _AggSum(torch.autograd.Function):
             dadj = param_colsum(dpiece, ctx.defer_ok)
         else:
             dadj = colsum(dpiece) if per_sample else dpiece
-        if dgamma is not None:
-            dgamma = dgamma if gamma is not None else None
-            dbeta = dbeta if has_beta else None
+        dgamma, dbeta = _trim_affine_grads(dgamma, dbeta, gamma, has_beta)
         return dp, dadj, None, dgamma, dbeta, None, None, None, None
 
 
@@ -2908,16 +2853,7 @@ class _FuseOut(torch.autograd.Function):
                                                   _ptr(dx1), _ptr(dx2), _ptr(part), n, C, T, V, ctx.xbar_ld or V,
                                                   _ct.byref(ctx.drop[0]) if ctx.drop else None, _stream())
         native.check(rc, 'dsgcn_fuse_out_bwd_drop')
-        ds1 = dh1 = ds2 = dh2 = None
-        if need_part and (s1 is None or ctx.bn1 is not None) and (s2 is None or ctx.bn2 is not None):
-            _bn_feed_multi(([(ctx.bn1, part, 4, 0, 3)] if s1 is not None else []) +
-                           ([(ctx.bn2, part, 4, 2, 1)] if s2 is not None else []))
-        elif need_part:
-            red = colsum(part, split_last=True)
-            if s1 is not None:
-                ds1, dh1 = red[0], red[3]
-            if s2 is not None:
-                ds2, dh2 = red[2], red[1]
+        (ds1, dh1, ds2, dh2), _ = _affine_tail(part, 4, [(s1, ctx.bn1, 0, 3), (s2, ctx.bn2, 2, 1)])
         return dx1, ds1, dh1, dx2, ds2, dh2, None, None, None, None
 
 
@@ -2956,16 +2892,7 @@ class _FuseOutPool(torch.autograd.Function):
                                                   _ptr(dpm), None, None, 3, None, _ptr(dx1), _ptr(dx2), _ptr(part), n, C, T, V,
                                                   V, _ct.byref(ctx.drop[0]) if ctx.drop else None, _stream())
         native.check(rc, 'dsgcn_fuse_out_bwd_drop')
-        ds1 = dh1 = ds2 = dh2 = None
-        if need_part and (s1 is None or ctx.bn1 is not None) and (s2 is None or ctx.bn2 is not None):
-            _bn_feed_multi(([(ctx.bn1, part, 4, 0, 3)] if s1 is not None else []) +
-                           ([(ctx.bn2, part, 4, 2, 1)] if s2 is not None else []))
-        elif need_part:
-            red = colsum(part, split_last=True)
-            if s1 is not None:
-                ds1, dh1 = red[0], red[3]
-            if s2 is not None:
-                ds2, dh2 = red[2], red[1]
+        (ds1, dh1, ds2, dh2), _ = _affine_tail(part, 4, [(s1, ctx.bn1, 0, 3), (s2, ctx.bn2, 2, 1)])
         return dx1, ds1, dh1, dx2, ds2, dh2, None, None
 
 

@@ -93,20 +93,16 @@ SIGNATURES = {
     'dsgcn_tms_split_fwd': [c_f] * 4 + [c_int] + [c_f] * 4 + [c_int] * 6 + [c_i] * 4 + [ctypes.c_void_p, ctypes.c_void_p, c_st],
     'dsgcn_tms_split_prep': [c_f] * 9 + [c_int] * 4 + [c_st],
     'dsgcn_tms_split_dgrad': [c_f] * 4 + [c_int] + [c_f] * 5 + [c_int] * 6 + [c_i] * 4 + [ctypes.c_void_p, c_st],
-    'dsgcn_tms_split_wgrad': [c_f] * 4 + [c_int] + [c_f] * 2 + [c_int] * 6 + [c_i] * 4 + [ctypes.c_void_p, ctypes.c_void_p, c_int, c_int, c_st],
     'dsgcn_aggsum_partial_rows': [c_int, c_int, c_int],
     'dsgcn_aggsum_bwd_piece_rows': [c_int] * 5,
     'dsgcn_aggsum_fwd': [c_f, c_f] + [ctypes.c_long] * 3 + [c_f, c_f] + [c_int] * 5 + [c_st],
     'dsgcn_aggsum_bwd': [c_f, c_f] + [ctypes.c_long] * 3 + [c_f] * 6 + [ctypes.c_long] * 3 + [c_int] * 5 + [c_st],
     'dsgcn_tanhdiff_fwd': [c_f, c_f] + [c_int] * 4 + [c_st],
-    'dsgcn_tanhdiff_bwd': [c_f, c_f, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_tanhdiff_bwd_k': [c_f, ctypes.c_void_p, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_tanhdiff_aug_fwd': [c_f, c_f, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_tanhdiff_aug_bwd': [c_f, ctypes.c_void_p, c_f, c_f] + [c_int] * 4 + [c_st],
-    'dsgcn_ctr_wprep': [ctypes.c_void_p, ctypes.c_void_p, c_f, c_f, c_f] + [c_int] * 3 + [c_st],
     'dsgcn_ctr_wprep_multi': [ctypes.c_void_p, c_int, c_st],
     'dsgcn_ctr_wfin_multi': [ctypes.c_void_p, c_int, c_st],
-    'dsgcn_ctr_wfin': [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_f] + [c_int] * 3 + [c_st],
     'dsgcn_ctr_affine_fwd': [ctypes.c_void_p, c_f, c_int, c_f, c_f, c_f, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_ctr_affine_bwd': [ctypes.c_void_p, c_f, c_int, c_f, ctypes.c_void_p, c_f] + [c_int] * 4 + [c_st],
     'dsgcn_edge_select_fwd': [c_f, c_i, c_f] + [c_int] * 4 + [c_st],
@@ -122,11 +118,6 @@ SIGNATURES = {
     'dsgcn_colsum_multi_host': [ctypes.c_void_p, c_int, c_st],
     'dsgcn_fuse_out_fwd': [c_f] * 6 + [c_int] + [c_f] * 2 + [c_int] * 5 + [c_st],
     'dsgcn_fuse_out_bwd': [c_f] * 6 + [c_int] + [c_f] * 5 + [c_int] * 5 + [c_st],
-    'dsgcn_fuse_out_bwd3': [c_f] * 6 + [c_int] + [c_f] * 7 + [c_int] * 5 + [c_st],
-    'dsgcn_fuse_out_fwd2': [c_f] * 6 + [c_int] + [c_f] * 3 + [c_int] * 5 + [c_st],
-    'dsgcn_fuse_out_bwd3s': [c_f] * 6 + [c_int] + [c_f] * 3 + [c_int] + [c_f] * 4 + [c_int] * 5 + [c_st],
-    'dsgcn_fuse_out_pool_fwd': [c_f] * 6 + [c_int] + [c_f] + [c_int] * 4 + [c_st],
-    'dsgcn_fuse_out_pool_bwd': [c_f] * 6 + [c_int] + [c_f] * 4 + [c_int] * 4 + [c_st],
     'dsgcn_dwcausal_fwd': [c_f, c_f, c_f, c_i, c_f] + [c_int] * 6 + [c_st],
     'dsgcn_dwcausal_bwd': [c_f, c_f, c_i, c_f, c_f, c_f] + [c_int] * 6 + [c_st],
     'dsgcn_gate_fwd': [c_f, c_f, c_int, c_f, c_f] + [c_int] * 5 + [c_st],

@@ -168,39 +168,20 @@ int dsgcn_fuse_out_fwd(const float* x1, const float* s1, const float* h1, const 
 int dsgcn_fuse_out_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                        const float* h2, int relu, const float* dout, const float* dxbar, float* dx1, float* dx2,
                        float* part, int n, int C, int T, int V, int xbar_ld, void* stream);
-/* the same with up to three gradients of `out`, (dout + dout2) + dout3 formed while loading: the next block reads its
- * input three times (dgstgcn.py:63-65: gcn(x), the unit's residual operand, the block residual) and autograd would
- * otherwise materialise the sum first (dsgcn_add3).  dout2 / dout3 may be NULL. */
-int dsgcn_fuse_out_bwd3(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                        const float* h2, int relu, const float* dout, const float* dout2, const float* dout3,
-                        const float* dxbar, float* dx1, float* dx2, float* part, int n, int C, int T, int V, int xbar_ld,
-                        void* stream);
-/* The even frames as a second output / as the shape of the third gradient stream: a stride-2 block's 1x1 residual conv
- * (reference: the block residual unit_tcn(kernel_size=1, stride=2), dgstgcn.py:35-40 + tcn.py:21-28) reads out[:, :, ::2];
- * dsgcn_fuse_out_fwd2 writes that tensor, out_s2 (n, C, ceil(T/2), V) or NULL, beside `out`, and dsgcn_fuse_out_bwd3s with
- * stride3 = 2 takes dout3 in that shape (added on the even frames) — no strided-copy launch, no zero-filled scatter. */
-int dsgcn_fuse_out_fwd2(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                        const float* h2, int relu, float* out, float* out_s2, float* xbar, int n, int C, int T, int V,
-                        int xbar_ld, void* stream);
-int dsgcn_fuse_out_bwd3s(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                         const float* h2, int relu, const float* dout, const float* dout2, const float* dout3, int stride3,
-                         const float* dxbar, float* dx1, float* dx2, float* part, int n, int C, int T, int V, int xbar_ld,
-                         void* stream);
-
-/* The last block's output as its (T, V) plane means only (what the head's pooling reads, simple_head.py:88-93): pmean
- * (n, C) = mean_tv relu?(x1*s1+h1 (+ x2*s2+h2 | + x2)) — the activation itself is never written.  Backward: dpmean
- * (n, C), dx1 / dx2 / part as dsgcn_fuse_out_bwd. */
-int dsgcn_fuse_out_pool_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                            const float* h2, int relu, float* pmean, int n, int C, int T, int V, void* stream);
-int dsgcn_fuse_out_pool_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                            const float* h2, int relu, const float* dpmean, float* dx1, float* dx2, float* part, int n,
-                            int C, int T, int V, void* stream);
-/* The block output with DROPOUT on its first term (the temporal unit's output: nn.Dropout behind its BatchNorm, tcn.py:30,33;
- * MSTCN msg3d_utils.py:141-146), masks from a counter-based generator (dsgcn_jobs.h: dsgcn_dropout) — no mask tensor, the
- * backward regenerates it:  out = relu?( D * relu2?(x1*s1+h1) + (x2*s2+h2 | x2) ), D = keep/(1-p).  One entry point per
- * direction covers every output form: out / out_s2 / xbar / pmean may be NULL (pmean (n*C): the plane means of
- * dsgcn_fuse_out_pool_fwd); backward stride3 = 1 | 2 as dsgcn_fuse_out_bwd3s, 3 = dout is the (n*C) gradient of the plane
- * means.  d NULL or p = 0: exactly the plain calls.  dsgcn_dropout_mask writes the multipliers a tensor of numel elements
+/* The block output in every form, with optional DROPOUT on its first term (the temporal unit's output: nn.Dropout behind its
+ * BatchNorm, tcn.py:30,33; MSTCN msg3d_utils.py:141-146), masks from a counter-based generator (dsgcn_jobs.h:
+ * dsgcn_dropout) — no mask tensor, the backward regenerates it:
+ *   out = relu?( D * relu2?(x1*s1+h1) + (x2*s2+h2 | x2) ), D = keep/(1-p);  d NULL or p = 0: exactly the plain calls above.
+ * Any of out / out_s2 / xbar / pmean may be NULL:
+ *   out_s2 (n, C, ceil(T/2), V): the even frames of `out` as a second output — what a stride-2 block's 1x1 residual conv
+ *     reads (the block residual unit_tcn(kernel_size=1, stride=2), dgstgcn.py:35-40 + tcn.py:21-28: out[:, :, ::2]);
+ *   pmean (n*C): the (T, V) plane means of the block output, all the head's pooling reads of the LAST block
+ *     (simple_head.py:88-93) — with out NULL the activation itself is never written.
+ * Backward: up to three gradients of `out`, (dout + dout2) + dout3 formed while loading — the next block reads its input
+ * three times (dgstgcn.py:63-65: gcn(x), the unit's residual operand, the block residual) and autograd would otherwise
+ * materialise the sum first (dsgcn_add3); dout2 / dout3 may be NULL.  stride3 = 1: dout3 like dout; 2: dout3 has the shape
+ * of out_s2 and is added on the even frames (no strided-copy launch, no zero-filled scatter); 3: dout is the (n*C) gradient
+ * of the plane means, dout2 / dout3 / dxbar NULL.  dsgcn_dropout_mask writes the multipliers a tensor of numel elements
  * gets under d (tests only: the product never materialises them). */
 int dsgcn_fuse_out_fwd_drop(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                             const float* h2, int relu, float* out, float* out_s2, float* xbar, float* pmean, int n, int C,
@@ -441,14 +422,13 @@ int dsgcn_aggsum_bwd(const float* p, const float* ahat, long a_ns, long a_ks, lo
 
 /* ---- CTR-GCN channel-wise topology (gcn.py:634-666), the parts that are not 1x1 convs ----
  * tanhdiff  : proj (n, 2*K*R, V) rows [k*R+r] = conv1_k(xbar), [K*R+k*R+r] = conv2_k(xbar)
- *             -> d (K, n, R, V, V) = tanh(x1[u] - x2[v])  (gcn.py:653-655); bwd: dproj from dd.
+ *             -> d (K, n, R, V, V) = tanh(x1[u] - x2[v])  (gcn.py:653-655); bwd_k: dproj from the gradient as K separate
+ *             tensors (n, R, V, V) (host array of K device pointers, NULL = zero).
  * ctr_affine: ahat (n, K*Co, V, V) = alpha[0] * s[k] (n,Co,V,V) + A (K,V,V)  (gcn.py:657); s / ds are host arrays
  *             of K <= 4 device pointers.  bwd: ds[k] = alpha*dahat; prow (4*n, K*V*V + K): per (sample, channel
  *             slice) [sum_c dahat | sum dahat*s] (sum over the rows = [dA | per-subset dalpha]).
  * plane_stats: partial (planes, 2) = per-plane [sum, sum of squares] of x (planes, L). */
 int dsgcn_tanhdiff_fwd(const float* proj, float* d, int n, int K, int R, int V, void* stream);
-int dsgcn_tanhdiff_bwd(const float* d, const float* dd, float* dproj, int n, int K, int R, int V, void* stream);
-/* the same with the gradient as K separate tensors (n, R, V, V) (host array of K device pointers, NULL = zero) */
 int dsgcn_tanhdiff_bwd_k(const float* d, const float* const* dd, float* dproj, int n, int K, int R, int V, void* stream);
 /* Classic CTR-GCN refinement as ONE conv per subset (round 5).  Ahat_k = alpha * conv4_k(d_k) + A[k] (ctrgcn's unit:
  * pyskl/models/gcns/utils/gcn.py unit_ctrgcn, `x1 = conv4(tanh(x1 - x2)) * alpha + A[i]`) equals a 1x1 conv over R + 2
@@ -457,23 +437,17 @@ int dsgcn_tanhdiff_bwd_k(const float* d, const float* const* dd, float* dproj, i
  * gradients of alpha (from the input-scale sums), A (the A channel's data gradient), W and b (columns of the weight
  * gradient) fall out of the conv's own backward.
  *   dsgcn_tanhdiff_aug_fwd: d (K, n, R + 2, V, V) = [tanh(x1 - x2) | A[k] | 1].
- *   dsgcn_tanhdiff_aug_bwd: dd = K gradients (n, R + 2, V, V) (host array, NULL = zero) -> dproj as dsgcn_tanhdiff_bwd and
+ *   dsgcn_tanhdiff_aug_bwd: dd = K gradients (n, R + 2, V, V) (host array, NULL = zero) -> dproj as dsgcn_tanhdiff_bwd_k and
  *     dAp (n, K, V, V) = the A-channel rows (their column sum over n is dA).
- *   dsgcn_ctr_wprep: w / b = K device pointers (Co, R) / (Co) (b[k] may be NULL) -> wout (K, Co, R + 2), sh (K, 2, R + 2) =
- *     per subset [input scale; input shift = 0].
- *   dsgcn_ctr_wfin: dwp = K gradients of wout[k] (NULL = zero), ds = K gradients of the input scales (NULL = zero; their
- *     R + 2 elements ds_stride floats apart) ->
- *     out[k] (Co*R + Co) = [dW_k | db_k], dalpha (1).
- *   dsgcn_ctr_wprep_multi / dsgcn_ctr_wfin_multi: the same for njobs units in one launch per 16 records (dsgcn_jobs.h) —
- *     both depend on parameters / finished parameter-gradient sums only, so a training step runs them once for the
- *     whole model. */
+ *   dsgcn_ctr_wprep_multi, per record (dsgcn_jobs.h): w / b = K device pointers (Co, R) / (Co) (b[k] may be NULL) -> wout
+ *     (K, Co, R + 2), sh (K, 2, R + 2) = per subset [input scale; input shift = 0].
+ *   dsgcn_ctr_wfin_multi, per record: dwp = K gradients of wout[k] (NULL = zero), ds = K gradients of the input scales
+ *     (NULL = zero; their R + 2 elements ds_stride floats apart) -> out[k] (Co*R + Co) = [dW_k | db_k], dalpha (1).
+ *   Both take njobs units in one launch per 16 records — they depend on parameters / finished parameter-gradient sums
+ *     only, so a training step runs them once for the whole model. */
 int dsgcn_tanhdiff_aug_fwd(const float* proj, const float* A, float* d, int n, int K, int R, int V, void* stream);
 int dsgcn_tanhdiff_aug_bwd(const float* d, const float* const* dd, float* dproj, float* dAp, int n, int K, int R, int V,
                            void* stream);
-int dsgcn_ctr_wprep(const float* const* w, const float* const* b, const float* alpha, float* wout, float* sh, int K,
-                    int Co, int R, void* stream);
-int dsgcn_ctr_wfin(const float* const* dwp, const float* const* ds, int ds_stride, float* const* out, float* dalpha, int K,
-                   int Co, int R, void* stream);
 int dsgcn_ctr_wprep_multi(const dsgcn_ctr_prep_job* jobs, int njobs, void* stream);
 int dsgcn_ctr_wfin_multi(const dsgcn_ctr_fin_job* jobs, int njobs, void* stream);
 int dsgcn_ctr_affine_fwd(const float* const* s, const float* alpha, int alpha_stride, const float* A, const float* beta,
@@ -589,7 +563,9 @@ int dsgcn_tms_wgrad(const float* z, const float* zaug, const float* scale, const
  *          pcoef (n*C, V) = sum_t ge[t,v]*oaug[t] (dsgcn_colsum finishes d coeff).
  *   dgrad: dz (n,C,T,V), dzaug (n,C,T), part (rows(1), C, 2) = [sum dpre*x, sum dpre] over z AND zaug (the sums
  *          dsgcn_bn_coef_rows takes).  One launch.
- *   wgrad: window i writes split s < rows(2) of its weight / bias partials at dwp[i] + s*pstride / dbp[i] + s*pstride. */
+ *   wgrad_jobs: window i writes split s < rows(2) of its weight / bias partials at dwp[i] + s*pstride / dbp[i] + s*pstride;
+ *          the launch carries BatchNorm coefficient jobs (njobs <= DSGCN_BN_JOBS_MAX, host records; 0: none) as extra
+ *          workgroups: the branch BatchNorm's rows come from dsgcn_tms_split_dgrad, nothing waits for the weight gradient. */
 int dsgcn_tms_split_rows(int which, int n, int C, int T, int V, int stride, int KT, int nbr, const int* type,
                          const int* c0, const int* bc, const int* dil);
 int dsgcn_tms_split_fwd(const float* z, const float* zaug, const float* scale, const float* shift, int n_act,
@@ -603,12 +579,6 @@ int dsgcn_tms_split_dgrad(const float* z, const float* zaug, const float* scale,
                           const float* ge, const float* doaug, float* dz, float* dzaug, float* part, int n, int C, int T,
                           int V, int stride, int nbr, const int* type, const int* c0, const int* bc, const int* dil,
                           const float* const* w, void* stream);
-int dsgcn_tms_split_wgrad(const float* z, const float* zaug, const float* scale, const float* shift, int n_act,
-                          const float* ge, const float* doaug, int n, int C, int T, int V, int stride, int nbr,
-                          const int* type, const int* c0, const int* bc, const int* dil, float* const* dwp, float* const* dbp,
-                          int splits, int pstride, void* stream);
-/* The weight gradient carrying BatchNorm coefficient jobs (njobs <= DSGCN_BN_JOBS_MAX, host records) as extra workgroups:
- * the branch BatchNorm's rows come from dsgcn_tms_split_dgrad, nothing waits for the weight gradient. */
 int dsgcn_tms_split_wgrad_jobs(const float* z, const float* zaug, const float* scale, const float* shift, int n_act,
                                const float* ge, const float* doaug, int n, int C, int T, int V, int stride, int nbr,
                                const int* type, const int* c0, const int* bc, const int* dil, float* const* dwp,
@@ -734,7 +704,7 @@ int dsgcn_head_ensemble_fwd(const float* const* feat, const float* const* w, con
  * ['score_ext'] — x.mean(axis, keepdim=True) over the axes named in pool_opt, then (score_ext) fc_cls at every remaining
  * position (einsum('nmctv,oc->nmotv') + bias), then the cast to float16.  ONE launch; the pooled tensor never reaches HBM.
  *   x (videos*clips*M, C, T, V): the last block's output, clip-major within a video — or its (videos*clips*M, C) plane
- *   means (dsgcn_fuse_out_pool_fwd) with T = V = 1.
+ *   means (pmean of dsgcn_fuse_out_fwd_drop) with T = V = 1.
  *   pool_mask: bit 0 'n' (the clips of ONE video: pooling never crosses videos), bit 1 'm', bit 2 't', bit 3 'v'.
  *   w == NULL: feature mode, the output channel extent is C (K and b are ignored);  w (K, C): score mode, b (K) or NULL,
  *   score = sum_c w[k, c] pooled[c] + b[k].

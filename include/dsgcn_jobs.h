@@ -39,7 +39,7 @@ typedef struct {
   float p;
 } dsgcn_dropout;
 
-/* The parameter-only launches of the CTR-GCN units (dsgcn_ctr_wprep / dsgcn_ctr_wfin, dsgcn.h) as records, so that all
+/* The parameter-only launches of the CTR-GCN units (k_ctr_wprep / k_ctr_wfin, csrc/ctr.hip) as records, so that all
  * units of a model share one launch at the head of the step (dsgcn_ctr_wprep_multi) and one at the end of the backward
  * (dsgcn_ctr_wfin_multi).  Fields as the arguments of the single-unit entry points; K <= 4. */
 #define DSGCN_CTR_JOBS_MAX 16

@@ -34,7 +34,8 @@ def test_library_builds_and_exports_header_symbols():
 
 
 def test_python_binding_covers_header():
-    assert set(declared_symbols()) <= set(native.SIGNATURES), set(declared_symbols()) - set(native.SIGNATURES)
+    # an equality: a binding row without a declaration is a removed (or never declared) entry point still spoken of
+    assert set(declared_symbols()) == set(native.SIGNATURES), set(declared_symbols()) ^ set(native.SIGNATURES)
 
 
 def test_argument_rejection_without_gpu():

@@ -9,28 +9,32 @@ import bench
 from dsgcn_amd import native
 
 lib = native.lib()
-POS = {'dsgcn_pwconv_fwd': 12, 'dsgcn_pwconv_dgrad': 17, 'dsgcn_pwconv_wgrad': 16, 'dsgcn_pwconv_bwd': 18}
+# entry point the package calls -> (report row, position of n): the size arguments sit where the plain forms have them
+POS = {'dsgcn_pwconv_fwd_ws': ('fwd', 12), 'dsgcn_pwconv_fwd_ws_guest': ('fwd', 12),
+       'dsgcn_pwconv_dgrad_ws': ('dgrad', 17), 'dsgcn_pwconv_dgrad_ws_guest': ('dgrad', 17),
+       'dsgcn_pwconv_wgrad_jobs': ('wgrad', 16),
+       'dsgcn_pwconv_bwd': ('bwd', 18), 'dsgcn_pwconv_bwd_guest': ('bwd', 18)}
 rec = collections.OrderedDict()
 
 
-def wrap(name, npos):
+def wrap(name, row, npos):
     fn = getattr(lib, name)
 
     def call(*a):
         n, Ci, Co, T, V = a[npos:npos + 5]
-        stride = a[npos + 5] if name != 'dsgcn_pwconv_bwd' else 1
-        aug = a[npos + 6] if name != 'dsgcn_pwconv_bwd' else 0
-        if name == 'dsgcn_pwconv_fwd':
+        stride = a[npos + 5] if row != 'bwd' else 1
+        aug = a[npos + 6] if row != 'bwd' else 0
+        if row == 'fwd':
             mode = ('2' if a[3] else '') + ('a' if a[1] else '') + ('r' if a[6] else '')
         else:
-            A0 = a[12] if name == 'dsgcn_pwconv_dgrad' else (a[11] if name == 'dsgcn_pwconv_wgrad' else a[10])
+            A0 = a[12] if row == 'dgrad' else (a[11] if row == 'wgrad' else a[10])
             mode = ('2' if a[3] else '') + ('a' if a[1] else '') + ('r' if a[6] else '') + ('+bn' if A0 else '')
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         rc = fn(*a)
         e1.record()
         torch.cuda.synchronize()
-        key = (name[13:], n, Ci, Co, T, V, stride, aug, mode or 'plain')
+        key = (row, n, Ci, Co, T, V, stride, aug, mode or 'plain')
         rec.setdefault(key, []).append(e0.elapsed_time(e1) * 1e3)
         return rc
     setattr(lib, name, call)
@@ -49,8 +53,8 @@ def main():
     for _ in range(2):
         step()
     torch.cuda.synchronize()
-    for name, npos in POS.items():
-        wrap(name, npos)
+    for name, (row, npos) in POS.items():
+        wrap(name, row, npos)
     step()
     tot = collections.defaultdict(float)
     print(f'{"call":6s} {"n":>4s} {"Ci":>4s} {"Co":>4s} {"T":>3s} {"V":>3s} s a {"mode":8s} {"calls":>5s} {"us avg":>8s} {"us/step":>8s}')
