@@ -19,9 +19,12 @@ resident in HBM, host decisions, one launch per batch — or from any map-style 
 ``validate=True`` registers the counterpart of the reference's ``DistEvalHook`` (train.py:134-147 over mmcv's EvalHook):
 every ``evaluation.interval`` epochs the val split goes through ``forward_test`` rank-sharded in dataset order, the parts
 are gathered (``gather_results``), rank 0 computes ``evaluation.metrics`` (top-k / mean-class accuracy) and keeps
-``best_<key>_epoch_<n>.pth`` (``save_best='auto'``: the first metric returned).  ``lr_config`` policies: ``CosineAnnealing``
-by iteration (the DS-GCN configs), ``step`` by epoch (configs/stgcn/stgcn_vanilla_ntu60_xsub_3dkp/j.py:35), ``fixed``; each
-with mmcv's ``warmup`` ('constant' / 'linear' / 'exp', ``warmup_iters``, ``warmup_ratio``, ``warmup_by_epoch``).
+``best_<key>_epoch_<n>.pth`` (``save_best='auto'``: the first metric returned).  ``lr_config`` policies: mmcv's
+``CosineAnnealing`` (the DS-GCN configs: by iteration), ``step`` (configs/stgcn/stgcn_vanilla_ntu60_xsub_3dkp/j.py:35: by
+epoch), ``fixed``, ``Exp``, ``Poly``, ``Inv``, ``CosineRestart``, each by epoch or by iteration, and ``Cyclic`` / ``OneCycle`` by
+iteration (the alternatives configs/_init_/lr_schedual.py names); each with mmcv's ``warmup`` ('constant' / 'linear' /
+'exp', ``warmup_iters``, ``warmup_ratio``, ``warmup_by_epoch``).  ``momentum_config`` policies ``cyclic`` / ``OneCycle`` schedule
+the momentum (SGD) or beta1 (Adam, AdamW): the value lives in device memory, so the update's hipGraph follows it.
 ``optimizer_config.grad_clip=dict(max_norm=..., norm_type=2 | inf)`` (configs/_init_/lr_schedual.py:24) clips the averaged
 gradient by its total norm inside the update's hipGraph; ``grad_norm`` (before clipping) joins the log scalars.
 ``optimizer_config=dict(type='GradientCumulativeOptimizerHook', cumulative_iters=k)`` makes every iteration a
@@ -47,7 +50,8 @@ from .checkpoint import find_resume, load_checkpoint, resume, save_checkpoint
 from .engine import TrainEngine
 from .evaluation import mean_class_accuracy, top_k_accuracy
 from .recognizers import gather_results, reduce_log_vars
-from .train import cosine_lr, step_lr, warmup_lr
+from .train import (ANNEAL, anneal_target, check_momentum, cosine_lr, cosine_restart_lr, cyclic_value, exp_lr, inv_lr,
+                    onecycle_lr_values, onecycle_momentum_values, onecycle_value, poly_lr, step_lr, warmup_lr)
 
 
 def _rank_world():
@@ -128,6 +132,58 @@ class _BatchSource:
         return kp.to(self.device, non_blocking=True), lb.to(self.device, non_blocking=True)
 
 
+# ``lr_config`` / ``momentum_config``: mmcv's policies and the options each takes; anything else raises, naming it
+_LR_COMMON = ('policy', 'by_epoch', 'warmup', 'warmup_iters', 'warmup_ratio', 'warmup_by_epoch')
+_LR_OPTIONS = {
+    'CosineAnnealing': ('min_lr', 'min_lr_ratio'),
+    'Step': ('step', 'gamma', 'min_lr'),
+    'Fixed': (),
+    'Exp': ('gamma',),
+    'Poly': ('power', 'min_lr'),
+    'Inv': ('gamma', 'power'),
+    'CosineRestart': ('periods', 'restart_weights', 'min_lr', 'min_lr_ratio'),
+    'Cyclic': ('target_ratio', 'cyclic_times', 'step_ratio_up', 'anneal_strategy'),
+    'OneCycle': ('max_lr', 'total_steps', 'pct_start', 'anneal_strategy', 'div_factor', 'final_div_factor', 'three_phase'),
+}
+_BY_ITER_ONLY = ('Cyclic', 'OneCycle')
+_MOMENTUM_OPTIONS = {
+    'Cyclic': ('target_ratio', 'cyclic_times', 'step_ratio_up'),
+    'OneCycle': ('base_momentum', 'max_momentum', 'pct_start', 'anneal_strategy', 'three_phase'),
+}
+
+
+def _policy_name(name):
+    """mmcv's hook lookup: a lower-case name is title-cased ('step' -> 'Step', 'cyclic' -> 'Cyclic'), any other is taken
+    as written."""
+    return name.title() if isinstance(name, str) and name == name.lower() else name
+
+
+def _check_options(what, cfg, policy, table, common):
+    if policy not in table:
+        raise NotImplementedError(f'{what} policy {cfg.get("policy")!r}: {", ".join(sorted(table))} are implemented')
+    extra = sorted(set(cfg) - set(common) - set(table[policy]))
+    if extra:
+        raise NotImplementedError(f'{what} policy {policy!r}: option(s) {extra} are not supported '
+                                  f'({", ".join(table[policy]) or "none"})')
+
+
+def _check_cycle(what, cfg, max_iters):
+    """The arguments the Cyclic / OneCycle pairs share, checked where mmcv asserts them."""
+    if cfg.get('anneal_strategy', 'cos') not in ANNEAL:
+        raise ValueError(f'{what}: anneal_strategy must be one of "cos" or "linear", instead got {cfg["anneal_strategy"]!r}')
+    if cfg.get('policy') == 'Cyclic':
+        ratio = cfg.get('target_ratio')
+        if ratio is not None and (not isinstance(ratio, (tuple, list)) or len(ratio) != 2):
+            raise ValueError(f'{what}: target_ratio must be a pair, got {ratio!r}')
+        times = cfg.get('cyclic_times', 1)
+        if isinstance(times, bool) or not isinstance(times, int) or not 1 <= times <= max(max_iters, 1):
+            raise ValueError(f'{what}: cyclic_times must be an integer in 1..max_iters ({max_iters}), got {times!r}')
+        if not 0 <= cfg.get('step_ratio_up', 0.4) < 1.0:
+            raise ValueError(f'{what}: step_ratio_up must be in range [0,1), got {cfg["step_ratio_up"]!r}')
+    if 'pct_start' in cfg and not 0 <= cfg['pct_start'] <= 1:
+        raise ValueError(f'{what}: expected float between 0 and 1 pct_start, but got {cfg["pct_start"]!r}')
+
+
 class EpochRunner:
     """State of a run (``epoch``, ``iter``, ``max_iters``) + the loop; ``log`` collects one dict per logging interval."""
 
@@ -144,13 +200,13 @@ class EpochRunner:
         self.seed = _get(cfg, 'seed', None)
         self.max_epochs = int(_get(cfg, 'total_epochs', 1))
         lr_cfg = dict(_get(cfg, 'lr_config', None) or dict(policy='CosineAnnealing', min_lr=0, by_epoch=False))
-        if lr_cfg.get('policy') not in ('CosineAnnealing', 'step', 'Step', 'fixed', 'Fixed'):
-            raise NotImplementedError(f"lr_config policy {lr_cfg.get('policy')!r}: the skeleton configs use "
-                                      'CosineAnnealing or step')
-        if lr_cfg.get('by_epoch', True) and lr_cfg['policy'] == 'CosineAnnealing':
-            raise NotImplementedError('CosineAnnealing by_epoch=True is not used by the skeleton configs')
-        if lr_cfg['policy'] in ('step', 'Step') and not lr_cfg.get('by_epoch', True):
-            raise NotImplementedError('step policy by_epoch=False is not used by the skeleton configs')
+        self.policy = _policy_name(lr_cfg.get('policy'))
+        _check_options('lr_config', lr_cfg, self.policy, _LR_OPTIONS, _LR_COMMON)
+        # mmcv's LrUpdaterHook counts epochs unless told otherwise; the Cyclic / OneCycle hooks count iterations only
+        self.by_epoch = bool(lr_cfg.get('by_epoch', self.policy not in _BY_ITER_ONLY))
+        if self.by_epoch and self.policy in _BY_ITER_ONLY:
+            raise NotImplementedError(f'lr_config policy {self.policy!r}: by_epoch=True is not supported (mmcv: only '
+                                      'by_epoch=False)')
         # mmcv LrUpdaterHook: warmup None | 'constant' | 'linear' | 'exp' over the first warmup_iters iterations
         # (warmup_by_epoch: warmup_iters counts epochs and is converted below, once iters_per_epoch is known)
         self.warmup = lr_cfg.get('warmup')
@@ -172,6 +228,93 @@ class EpochRunner:
         self.max_iters = self.max_epochs * self.iters_per_epoch
         if self.warmup is not None:
             self.warmup_iters = int(lr_cfg['warmup_iters']) * (self.iters_per_epoch if lr_cfg.get('warmup_by_epoch') else 1)
+        self._check_lr_policy()
+        mom_cfg = _get(cfg, 'momentum_config', None)
+        self.momentum_cfg = None if mom_cfg is None else self._parse_momentum(dict(mom_cfg))
+
+    def _check_lr_policy(self):
+        """What mmcv's hooks assert in their constructors and ``before_run``, once ``max_iters`` is known."""
+        c, policy = self.lr_cfg, self.policy
+        if policy in ('CosineAnnealing', 'CosineRestart'):
+            anneal_target(1.0, c.get('min_lr'), c.get('min_lr_ratio'))
+        if policy == 'Step':
+            step = c.get('step')
+            if isinstance(step, bool) or not (isinstance(step, int) and step > 0 or isinstance(step, (list, tuple)) and step
+                                              and all(isinstance(v, int) and v > 0 for v in step)):
+                raise ValueError(f'lr_config step must be a positive int or a list of them, got {step!r}')
+        if policy in ('Exp', 'Inv') and 'gamma' not in c:
+            raise ValueError(f'lr_config policy {policy!r} needs gamma')
+        if policy == 'CosineRestart':
+            periods = c.get('periods')
+            weights = c.get('restart_weights', [1])
+            if not periods or len(periods) != len(weights):
+                raise ValueError('lr_config CosineRestart: periods and restart_weights should have the same length, got '
+                                 f'{periods!r} and {weights!r}')
+            top = self.max_epochs if self.by_epoch else self.max_iters
+            if sum(periods) < top:
+                raise ValueError(f'lr_config CosineRestart: the periods cover {sum(periods)} of the run\'s {top} '
+                                 f'{"epochs" if self.by_epoch else "iterations"}')
+        if policy in _BY_ITER_ONLY:
+            _check_cycle(f'lr_config {policy}', dict(c, policy=policy), self.max_iters)
+        if policy == 'OneCycle':
+            max_lr = c.get('max_lr')
+            if isinstance(max_lr, (list, tuple)):
+                if len(max_lr) != 1:
+                    raise NotImplementedError(f'lr_config OneCycle: max_lr with one rate per group ({len(max_lr)} entries) is '
+                                              'not supported: a scalar or a one-element list')
+                max_lr = max_lr[0]
+            if not isinstance(max_lr, (int, float)) or isinstance(max_lr, bool):
+                raise ValueError(f'lr_config OneCycle: the type of max_lr must be the one of list or float, got {max_lr!r}')
+            steps = c.get('total_steps')
+            if steps is not None:
+                if isinstance(steps, bool) or not isinstance(steps, int):
+                    raise ValueError(f'lr_config OneCycle: total_steps must be an integer, got {steps!r}')
+                if steps < self.max_iters:
+                    raise ValueError(f'lr_config OneCycle: the total steps must be greater than or equal to max iterations '
+                                     f'{self.max_iters} of runner, but total steps is {steps}')
+            self.total_steps = self.max_iters if steps is None else steps
+            # EVERY group starts from max_lr / div_factor: mmcv overwrites the groups' initial_lr, lr_mult included
+            self.onecycle_base = max_lr / c.get('div_factor', 25)
+
+    def _parse_momentum(self, c):
+        """``momentum_config``: mmcv's CyclicMomentumUpdaterHook ('cyclic') and OneCycleMomentumUpdaterHook ('OneCycle').  The
+        base is the optimizer's momentum (SGD) / betas[0] (Adam, AdamW) of the config; every value the schedule can take
+        must lie in [0, 1) — its extremes are evaluated here."""
+        policy = _policy_name(c.get('policy'))
+        _check_options('momentum_config', c, policy, _MOMENTUM_OPTIONS, ('policy', 'by_epoch'))
+        if c.get('by_epoch', False):
+            raise NotImplementedError(f'momentum_config policy {policy!r}: by_epoch=True is not supported')
+        opt = self.engine.opt
+        if not getattr(opt, 'scheduled_momentum', False):
+            raise ValueError('momentum_config needs an optimizer built with scheduled_momentum=True (train_model and '
+                             'build_optimizer(..., scheduled_momentum=True) do that)')
+        base = opt.initial_momentum
+        if base == 0 and not hasattr(opt, 'betas'):
+            raise ValueError('momentum_config on SGD with momentum=0: there is no momentum to schedule')
+        c['policy'] = policy
+        _check_cycle(f'momentum_config {policy}', c, self.max_iters)
+        if policy == 'Cyclic':
+            ratio = c.setdefault('target_ratio', (0.85 / 0.95, 1))
+            extremes = [base, base * ratio[0], base * ratio[1]]
+        else:
+            extremes = [c.setdefault('base_momentum', 0.85), c.setdefault('max_momentum', 0.95)]
+        for v in extremes:
+            check_momentum(v, f'momentum_config {policy}: scheduled momentum')
+        c['base'] = base
+        return c
+
+    def current_momentum(self):
+        """The momentum / beta1 of iteration ``self.iter`` under ``momentum_config`` (None without one): a pure function of
+        the iteration, so a resumed run continues the schedule with no state of its own."""
+        c = self.momentum_cfg
+        if c is None:
+            return None
+        if c['policy'] == 'Cyclic':
+            return cyclic_value(c['base'], self.iter, self.max_iters, c['target_ratio'], c.get('cyclic_times', 1),
+                                c.get('step_ratio_up', 0.4), 'cos')
+        three = bool(c.get('three_phase', False))
+        return onecycle_value(onecycle_momentum_values(c['base_momentum'], c['max_momentum'], three), self.iter,
+                              self.max_iters, c.get('pct_start', 0.3), c.get('anneal_strategy', 'cos'), three)
 
     def current_lr(self, base=None):
         """The rate of iteration ``self.iter`` for a group whose initial rate is ``base`` (default: the optimizer's
@@ -194,13 +337,32 @@ class EpochRunner:
         return [by_base[b] for b in bases]
 
     def regular_lr(self, base=None):
+        c, policy = self.lr_cfg, self.policy
+        if policy == 'OneCycle':                          # one base for every group, whatever its initial rate
+            three = bool(c.get('three_phase', False))
+            values = onecycle_lr_values(self.onecycle_base, c.get('div_factor', 25), c.get('final_div_factor', 1e4), three)
+            return onecycle_value(values, self.iter, self.total_steps, c.get('pct_start', 0.3),
+                                  c.get('anneal_strategy', 'cos'), three)
         if base is None:
             base = self.engine.opt.base_lr
-        if self.lr_cfg['policy'] == 'CosineAnnealing':
-            return cosine_lr(base, self.iter, self.max_iters, float(self.lr_cfg.get('min_lr', 0) or 0))
-        if self.lr_cfg['policy'] in ('step', 'Step'):     # mmcv StepLrUpdaterHook(by_epoch=True): set before each epoch
-            return step_lr(base, self.epoch, self.lr_cfg['step'], float(self.lr_cfg.get('gamma', 0.1)),
-                           self.lr_cfg.get('min_lr', None))
+        # mmcv's LrUpdaterHook: by_epoch policies are set before each epoch from runner.epoch, the others from runner.iter
+        progress, top = (self.epoch, self.max_epochs) if self.by_epoch else (self.iter, self.max_iters)
+        if policy == 'CosineAnnealing':
+            return cosine_lr(base, progress, top, anneal_target(base, c.get('min_lr'), c.get('min_lr_ratio')))
+        if policy == 'Step':
+            return step_lr(base, progress, c['step'], float(c.get('gamma', 0.1)), c.get('min_lr', None))
+        if policy == 'Exp':
+            return exp_lr(base, progress, c['gamma'])
+        if policy == 'Poly':
+            return poly_lr(base, progress, top, c.get('power', 1.), c.get('min_lr', 0.))
+        if policy == 'Inv':
+            return inv_lr(base, progress, c['gamma'], c.get('power', 1.))
+        if policy == 'CosineRestart':
+            return cosine_restart_lr(base, progress, c['periods'], c.get('restart_weights', [1]), c.get('min_lr'),
+                                     c.get('min_lr_ratio'))
+        if policy == 'Cyclic':
+            return cyclic_value(base, self.iter, self.max_iters, c.get('target_ratio', (10, 1e-4)), c.get('cyclic_times', 1),
+                                c.get('step_ratio_up', 0.4), c.get('anneal_strategy', 'cos'))
         return base
 
     def train_epoch(self):
@@ -213,12 +375,16 @@ class EpochRunner:
             kp, lb = self.source.batch(idx, nxt)
             lr = self.current_lr()                                    # before_train_iter
             lrs = self.current_lrs()                                  # (one rate per group under paramwise_cfg / Adam)
-            logs = self.engine.step(kp, lb, lr if lrs is None else lrs)       # run_iter + after_train_iter (OptimizerHook)
+            mom = self.current_momentum()                             # (None without a momentum_config)
+            if mom is None:
+                logs = self.engine.step(kp, lb, lr if lrs is None else lrs)   # run_iter + after_train_iter (OptimizerHook)
+            else:
+                logs = self.engine.step(kp, lb, lr if lrs is None else lrs, momentum=mom)
             # a replayed hipGraph hands back the SAME static tensors every iteration: keep this iteration's values
             pending.append(({k: v.clone() for k, v in logs.items()}, len(idx)))
             self.iter += 1
             if (b + 1) % self.log_interval == 0 or b + 1 == self.iters_per_epoch:
-                self._flush_log(pending, lr, b + 1, time.perf_counter() - t0)
+                self._flush_log(pending, lr, b + 1, time.perf_counter() - t0, mom)
                 pending, t0 = [], time.perf_counter()
         if getattr(self.engine, 'pending', 0):
             # a group never straddles an epoch end: what a checkpoint or a validation pass sees there is a model whose
@@ -234,7 +400,7 @@ class EpochRunner:
         if self.evaluator is not None:                                # after_train_epoch of the EvalHook
             self.evaluator.after_train_epoch(self)
 
-    def _flush_log(self, pending, lr, inner, dt):
+    def _flush_log(self, pending, lr, inner, dt, momentum=None):
         """The interval's log scalars: sample-weighted means over its iterations, averaged over ranks with ONE collective
         and read back with ONE copy (the reference pays four all-reduces and four ``.item()`` syncs per ITERATION,
         recognizers/base.py:150-156)."""
@@ -245,9 +411,12 @@ class EpochRunner:
         means = OrderedDict((k, (torch.stack([lv[k].double() for lv, _ in pending]) * w).sum() / w.sum()) for k in keys)
         vals = reduce_log_vars(means)
         rec = dict(epoch=self.epoch + 1, iter=inner, lr=lr, time=dt / max(len(pending), 1), **vals)
+        if momentum is not None:                          # (mmcv's text logger prints it once a momentum hook runs)
+            rec['momentum'] = momentum
         self.log.append(rec)
         if self.logger is not None and self.rank == 0:
-            self.logger.info('Epoch [%d][%d/%d]\tlr: %.3e, time: %.3f, %s', rec['epoch'], inner, self.iters_per_epoch, lr,
+            rate = '%.3e' % lr if momentum is None else '%.3e, momentum: %.4f' % (lr, momentum)
+            self.logger.info('Epoch [%d][%d/%d]\tlr: %s, time: %.3f, %s', rec['epoch'], inner, self.iters_per_epoch, rate,
                              rec['time'], ', '.join(f'{k}: {v:.4f}' for k, v in vals.items()))
 
     def save_checkpoint(self):
@@ -487,6 +656,7 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
 
     cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer``,
     ``optimizer_config`` (``grad_clip``; ``type`` + ``cumulative_iters``), ``lr_config`` (policy + warm-up),
+    ``momentum_config`` ('cyclic' | 'OneCycle': the optimizer then keeps its momentum / beta1 on the device),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
     ``auto_resume``, ``matmul_precision`` ('highest' | 'high': the run's training steps and validation passes; absent = the
     process level, ``kernels.set_matmul_precision``); with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
@@ -502,7 +672,8 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     # mmcv's build_optimizer(model, cfg.optimizer): SGD | Adam | AdamW with torch's defaults for absent keys, and
     # paramwise_cfg (train.build_optimizer raises for what is not implemented, naming the key)
     engine = TrainEngine(model, optimizer=opt_cfg, use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip,
-                         accumulate=accumulate, matmul_precision=_get(cfg, 'matmul_precision', None))
+                         accumulate=accumulate, matmul_precision=_get(cfg, 'matmul_precision', None),
+                         scheduled_momentum=_get(cfg, 'momentum_config', None) is not None)
     if logger is not None:
         logger.info('matmul precision: %s', engine.matmul_precision)
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)

@@ -45,11 +45,10 @@ __global__ __launch_bounds__(GN_NT) void k_grad_norm(const float* __restrict__ g
 }
 
 // k_sgd (head.hip) on g * coef.  coef == 1: the product is g itself, p and buf come out as k_sgd leaves them.
-__global__ __launch_bounds__(GN_NT) void k_sgd_clip(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
-                                                    const float* __restrict__ lr, const double* __restrict__ partial,
-                                                    int rows, int inf, float max_norm, float* __restrict__ grad_norm,
-                                                    float mom, float wd, int nesterov, long n4, long n) {
-  __shared__ double red[GN_NT];
+__device__ __forceinline__ void sgd_clip_flat(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                              const float* __restrict__ lr, const double* __restrict__ partial, int rows,
+                                              int inf, float max_norm, float* __restrict__ grad_norm, float mom, float wd,
+                                              int nesterov, long n4, long n, double* red) {
   const int tid = threadIdx.x;
   float total;
   // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
@@ -109,6 +108,27 @@ __global__ __launch_bounds__(GN_NT) void k_sgd_clip(float* __restrict__ p, float
   }
 }
 
+__global__ __launch_bounds__(GN_NT) void k_sgd_clip(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                    const float* __restrict__ lr, const double* __restrict__ partial,
+                                                    int rows, int inf, float max_norm, float* __restrict__ grad_norm,
+                                                    float mom, float wd, int nesterov, long n4, long n) {
+  __shared__ double red[GN_NT];
+  sgd_clip_flat(p, g, buf, lr, partial, rows, inf, max_norm, grad_norm, mom, wd, nesterov, n4, n, red);
+}
+
+// k_sgd_clip with the momentum read on the device (head.hip k_sgd_hyper: one scalar load per wave; 0 leaves buf alone)
+__global__ __launch_bounds__(GN_NT) void k_sgd_clip_hyper(float* __restrict__ p, float* __restrict__ g,
+                                                          float* __restrict__ buf, const float* __restrict__ lr,
+                                                          const double* __restrict__ partial, int rows, int inf,
+                                                          float max_norm, float* __restrict__ grad_norm,
+                                                          const double* __restrict__ hyper, float wd, int nesterov,
+                                                          long n4, long n) {
+  __shared__ double red[GN_NT];
+  const float mom = uniform_f32((float)hyper[0]);
+  sgd_clip_flat(p, g, mom != 0.f ? buf : nullptr, lr, partial, rows, inf, max_norm, grad_norm, mom, wd, nesterov, n4, n,
+                red);
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,6 +167,23 @@ int dsgcn_sgd_step_clip(float* p, float* g, float* buf, const float* lr, const d
   hipLaunchKernelGGL(k_sgd_clip, dim3((unsigned)blocks), dim3(GN_NT), 0, (hipStream_t)stream, p, g,
                      momentum != 0.f ? buf : nullptr, lr, partial, rows, norm_type == 0 ? 1 : 0, max_norm, grad_norm_out,
                      momentum, weight_decay, nesterov, n4, (long)n);
+  DSGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+int dsgcn_sgd_step_clip_hyper(float* p, float* g, float* buf, const float* lr, const double* partial, int rows,
+                              int norm_type, float max_norm, float* grad_norm_out, const double* hyper, float weight_decay,
+                              int nesterov, long long n, void* stream) {
+  if (!p || !g || !buf || !lr || !partial || !grad_norm_out || !hyper || n <= 0 || rows <= 0) return DSGCN_EINVAL;
+  if ((norm_type != 0 && norm_type != 2) || !(max_norm >= 0.f)) return DSGCN_EINVAL;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) || (((uintptr_t)partial | (uintptr_t)hyper) & 7))
+    return DSGCN_EINVAL;
+  const long n4 = (long)(n / 4);
+  const long per = (long)GN_NT * SC_VPT;
+  const long blocks = (n4 + 1 + per - 1) / per;
+  if (blocks > 0x7fffffffL) return DSGCN_EUNSUPPORTED;
+  hipLaunchKernelGGL(k_sgd_clip_hyper, dim3((unsigned)blocks), dim3(GN_NT), 0, (hipStream_t)stream, p, g, buf, lr, partial,
+                     rows, norm_type == 0 ? 1 : 0, max_norm, grad_norm_out, hyper, weight_decay, nesterov, n4, (long)n);
   DSGCN_LAUNCH_CHECK();
   return 0;
 }

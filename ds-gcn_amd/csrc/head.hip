@@ -215,9 +215,8 @@ __global__ __launch_bounds__(256) void k_bn_running_multi(RnJobs jb) {
 
 // SGD with momentum (dampening 0) over the flat buffers, torch.optim.SGD's update order:
 //   g' = g + wd p;  buf = mom buf + g';  step = nesterov ? g' + mom buf : buf;  p -= lr step      (lr read on the device)
-__global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                             const float* __restrict__ lr, float mom, float wd, int nesterov, long n4,
-                                             long n) {
+__device__ __forceinline__ void sgd_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                         const float* __restrict__ lr, float mom, float wd, int nesterov, long n4, long n) {
   const float rate = lr[0];
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   auto one = [&](float pv, float gv, float& bv) { return sgd_update(pv, gv, bv, buf != nullptr, rate, mom, wd, nesterov); };
@@ -242,6 +241,23 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float*
   }
 }
 
+__global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                             const float* __restrict__ lr, float mom, float wd, int nesterov, long n4,
+                                             long n) {
+  sgd_flat(p, g, buf, lr, mom, wd, nesterov, n4, n);
+}
+
+// k_sgd with the momentum read on the device like the rate: hyper[0] (fp64, a torch param group's Python float) is one
+// scalar load per wave, rounded to fp32 as the by-value argument is.  A momentum of exactly 0 leaves buf alone, as
+// dsgcn_sgd_step does when it drops the pointer and as torch does (`if momentum != 0`): a schedule may pass through 0.
+__global__ __launch_bounds__(256) void k_sgd_hyper(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ buf, const float* __restrict__ lr,
+                                                   const double* __restrict__ hyper, float wd, int nesterov, long n4,
+                                                   long n) {
+  const float mom = uniform_f32((float)hyper[0]);
+  sgd_flat(p, g, mom != 0.f ? buf : nullptr, lr, mom, wd, nesterov, n4, n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -253,6 +269,17 @@ int dsgcn_sgd_step(float* p, const float* g, float* buf, const float* lr, float 
   const long n4 = (long)(n / 4);
   hipLaunchKernelGGL(k_sgd, dim3((unsigned)((n4 + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g,
                      momentum != 0.f ? buf : nullptr, lr, momentum, weight_decay, nesterov, n4, (long)n);
+  DSGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+int dsgcn_sgd_step_hyper(float* p, const float* g, float* buf, const float* lr, const double* hyper, float weight_decay,
+                         int nesterov, long long n, void* stream) {
+  if (!p || !g || !buf || !lr || !hyper || n <= 0) return DSGCN_EINVAL;
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) || ((uintptr_t)hyper & 7)) return DSGCN_EINVAL;
+  const long n4 = (long)(n / 4);
+  hipLaunchKernelGGL(k_sgd_hyper, dim3((unsigned)((n4 + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, buf, lr,
+                     hyper, weight_decay, nesterov, n4, (long)n);
   DSGCN_LAUNCH_CHECK();
   return 0;
 }

@@ -11,6 +11,8 @@
 //   k_optim    a workgroup takes 1024 consecutive float4; a float4 inside one tensor resolves its group once, one that
 //              straddles a boundary walks the table per element.  SGD: sgd_update.h with the group's rate and decay.
 //              Adam: torch's single-tensor order (amsgrad=False, maximize=False), every operation rounded on its own.
+//   DEV forms  (the *_hyper entry points) SGD's momentum / Adam's beta1 is read from one fp64 device element instead of the
+//              kernel arguments: a replayed launch follows a momentum schedule.  Same arithmetic, same bits at a same value.
 // The Adam step count is one int per WORKGROUP (all equal): workgroup c reads step[c] and writes step[c] + 1, so no
 // workgroup reads what another one of the same launch writes, and a replayed launch advances the count by itself.
 // Fixed grid, fixed order, no atomics: the same bits on every run.
@@ -49,6 +51,7 @@ struct OpHyper {
   int decoupled;                                    // Adam: AdamW's p *= 1 - lr wd instead of g += wd p
   float mom;                                        // SGD
   int nesterov;                                     // SGD
+  const double* dev;                                // DEV kernels: momentum (SGD) / beta1 (Adam) in device memory
 };
 
 // per-workgroup constants of the Adam update
@@ -89,13 +92,22 @@ __device__ __forceinline__ float op_adam(float pv, float gv, float& mv, float& v
 }
 
 // s1: SGD's momentum buffer (may be NULL) / Adam's exp_avg;  s2: Adam's exp_avg_sq
-template <bool ADAM, bool CLIP>
-__global__ __launch_bounds__(OP_NT) void k_optim(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s1,
+// DEV: hy.dev[0] (fp64, one scalar load per wave) stands in for hy.mom (rounded to fp32 as the by-value argument is) resp.
+// hy.b1 — a replayed launch follows a momentum schedule as it follows the rates.  SGD at a momentum of exactly 0 leaves the
+// buffer alone, as the by-value form does when its caller drops the pointer and as torch does (`if momentum != 0`).
+template <bool ADAM, bool CLIP, bool DEV>
+__global__ __launch_bounds__(OP_NT) void k_optim(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s1_arg,
                                                  float* __restrict__ s2, OpTable tab, OpClip clip, OpHyper hy, long n4,
                                                  long n) {
   __shared__ double red[CLIP ? OP_NT : 1];
   __shared__ float c0s[OP_MAXG], c1s[OP_MAXG], c2s[OP_MAXG];
   const int tid = threadIdx.x;
+  if (DEV) {
+    const double* __restrict__ dev = hy.dev;
+    if (ADAM) hy.b1 = dev[0];
+    else hy.mom = uniform_f32((float)dev[0]);
+  }
+  float* __restrict__ s1 = (DEV && !ADAM && hy.mom == 0.f) ? nullptr : s1_arg;
   float coef = 1.f;
   if (CLIP) {
     float total;
@@ -226,39 +238,50 @@ int op_check_clip(const OpClip& c) {
   return 0;
 }
 
-template <bool ADAM>
+template <bool ADAM, bool DEV>
 int op_launch(float* p, float* g, float* s1, float* s2, const OpTable& tab, const OpClip* clip, const OpHyper& hy,
               long long n, void* stream) {
   const long n4 = (long)(n / 4);
   const unsigned blocks = (unsigned)(n4 / OP_CHUNK4 + 1);           // the thread with float4 index n4 takes the tail
   if (clip)
-    hipLaunchKernelGGL((k_optim<ADAM, true>), dim3(blocks), dim3(OP_NT), 0, (hipStream_t)stream, p, g, s1, s2, tab, *clip, hy,
+    hipLaunchKernelGGL((k_optim<ADAM, true, DEV>), dim3(blocks), dim3(OP_NT), 0, (hipStream_t)stream, p, g, s1, s2, tab, *clip, hy,
                        n4, (long)n);
   else
-    hipLaunchKernelGGL((k_optim<ADAM, false>), dim3(blocks), dim3(OP_NT), 0, (hipStream_t)stream, p, g, s1, s2, tab, OpClip{},
+    hipLaunchKernelGGL((k_optim<ADAM, false, DEV>), dim3(blocks), dim3(OP_NT), 0, (hipStream_t)stream, p, g, s1, s2, tab, OpClip{},
                        hy, n4, (long)n);
   DSGCN_LAUNCH_CHECK();
   return 0;
 }
 
-int op_sgd(float* p, float* g, float* buf, const OpTable& tab, const OpClip* clip, float momentum, int nesterov, long long n,
-           void* stream) {
+// hyper (DEV forms): buf is required whatever the value turns out to be — a schedule may pass through 0 and leave it again
+int op_sgd(float* p, float* g, float* buf, const OpTable& tab, const OpClip* clip, float momentum, const double* hyper,
+           int nesterov, long long n, void* stream) {
   int rc = op_check(p, g, tab, n);
   if (rc) return rc;
+  if (hyper) {
+    if (!buf || op_misaligned(buf, 15) || op_misaligned(hyper, 7)) return DSGCN_EINVAL;
+    if (clip && (rc = op_check_clip(*clip))) return rc;
+    OpHyper hy = {};
+    hy.nesterov = nesterov;
+    hy.dev = hyper;
+    return op_launch<false, true>(p, g, buf, nullptr, tab, clip, hy, n, stream);
+  }
   if (!(momentum >= 0.f) || (momentum != 0.f && !buf) || op_misaligned(buf, 15)) return DSGCN_EINVAL;
   if (clip && (rc = op_check_clip(*clip))) return rc;
   OpHyper hy = {};
   hy.mom = momentum;
   hy.nesterov = nesterov;
-  return op_launch<false>(p, g, momentum != 0.f ? buf : nullptr, nullptr, tab, clip, hy, n, stream);
+  return op_launch<false, false>(p, g, momentum != 0.f ? buf : nullptr, nullptr, tab, clip, hy, n, stream);
 }
 
+// hyper != NULL (DEV forms): beta1 is read from it on the device and the argument beta1 is not looked at
 int op_adam(float* p, float* g, float* m, float* v, int* step, const OpTable& tab, const OpClip* clip, double beta1,
-            double beta2, float eps, int decoupled, long long n, void* stream) {
+            const double* hyper, double beta2, float eps, int decoupled, long long n, void* stream) {
   int rc = op_check(p, g, tab, n);
   if (rc) return rc;
   if (!m || !v || !step || op_misaligned(m, 15) || op_misaligned(v, 15) || op_misaligned(step, 3)) return DSGCN_EINVAL;
-  if (!(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.f)) return DSGCN_EINVAL;
+  if (hyper ? op_misaligned(hyper, 7) : !(beta1 >= 0. && beta1 < 1.)) return DSGCN_EINVAL;
+  if (!(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.f)) return DSGCN_EINVAL;
   if (clip && (rc = op_check_clip(*clip))) return rc;
   OpHyper hy = {};
   hy.step = step;
@@ -266,7 +289,9 @@ int op_adam(float* p, float* g, float* m, float* v, int* step, const OpTable& ta
   hy.b2 = beta2;
   hy.eps = eps;
   hy.decoupled = decoupled ? 1 : 0;
-  return op_launch<true>(p, g, m, v, tab, clip, hy, n, stream);
+  hy.dev = hyper;
+  if (hyper) return op_launch<true, true>(p, g, m, v, tab, clip, hy, n, stream);
+  return op_launch<true, false>(p, g, m, v, tab, clip, hy, n, stream);
 }
 
 }  // namespace
@@ -305,7 +330,7 @@ int dsgcn_sgd_group_step(float* p, float* g, float* buf, const int* ends, const 
                          const double* lr, const double* wd, int groups, float momentum, int nesterov, long long n,
                          void* stream) {
   const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
-  return op_sgd(p, g, buf, tab, nullptr, momentum, nesterov, n, stream);
+  return op_sgd(p, g, buf, tab, nullptr, momentum, nullptr, nesterov, n, stream);
 }
 
 int dsgcn_sgd_group_step_clip(float* p, float* g, float* buf, const int* ends, const int* group, const int* first, int ntens,
@@ -315,14 +340,14 @@ int dsgcn_sgd_group_step_clip(float* p, float* g, float* buf, const int* ends, c
   if (norm_type != 0 && norm_type != 2) return DSGCN_EINVAL;
   const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
   const OpClip clip = {partial, grad_norm_out, rows, norm_type == 0 ? 1 : 0, max_norm};
-  return op_sgd(p, g, buf, tab, &clip, momentum, nesterov, n, stream);
+  return op_sgd(p, g, buf, tab, &clip, momentum, nullptr, nesterov, n, stream);
 }
 
 int dsgcn_adam_step(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group, const int* first,
                     int ntens, const double* lr, const double* wd, int groups, double beta1, double beta2, float eps,
                     int decoupled, long long n, void* stream) {
   const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
-  return op_adam(p, g, m, v, step, tab, nullptr, beta1, beta2, eps, decoupled, n, stream);
+  return op_adam(p, g, m, v, step, tab, nullptr, beta1, nullptr, beta2, eps, decoupled, n, stream);
 }
 
 int dsgcn_adam_step_clip(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
@@ -332,7 +357,44 @@ int dsgcn_adam_step_clip(float* p, float* g, float* m, float* v, int* step, cons
   if (norm_type != 0 && norm_type != 2) return DSGCN_EINVAL;
   const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
   const OpClip clip = {partial, grad_norm_out, rows, norm_type == 0 ? 1 : 0, max_norm};
-  return op_adam(p, g, m, v, step, tab, &clip, beta1, beta2, eps, decoupled, n, stream);
+  return op_adam(p, g, m, v, step, tab, &clip, beta1, nullptr, beta2, eps, decoupled, n, stream);
+}
+
+// ---- the same four with momentum / beta1 in device memory: hyper[0], fp64, NULL is DSGCN_EINVAL ------------------------
+int dsgcn_sgd_group_step_hyper(float* p, float* g, float* buf, const int* ends, const int* group, const int* first, int ntens,
+                               const double* lr, const double* wd, int groups, const double* hyper, int nesterov,
+                               long long n, void* stream) {
+  if (!hyper) return DSGCN_EINVAL;
+  const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
+  return op_sgd(p, g, buf, tab, nullptr, 0.f, hyper, nesterov, n, stream);
+}
+
+int dsgcn_sgd_group_step_clip_hyper(float* p, float* g, float* buf, const int* ends, const int* group, const int* first,
+                                    int ntens, const double* lr, const double* wd, int groups, const double* partial,
+                                    int rows, int norm_type, float max_norm, float* grad_norm_out, const double* hyper,
+                                    int nesterov, long long n, void* stream) {
+  if (!hyper || (norm_type != 0 && norm_type != 2)) return DSGCN_EINVAL;
+  const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
+  const OpClip clip = {partial, grad_norm_out, rows, norm_type == 0 ? 1 : 0, max_norm};
+  return op_sgd(p, g, buf, tab, &clip, 0.f, hyper, nesterov, n, stream);
+}
+
+int dsgcn_adam_step_hyper(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
+                          const int* first, int ntens, const double* lr, const double* wd, int groups, const double* hyper,
+                          double beta2, float eps, int decoupled, long long n, void* stream) {
+  if (!hyper) return DSGCN_EINVAL;
+  const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
+  return op_adam(p, g, m, v, step, tab, nullptr, 0., hyper, beta2, eps, decoupled, n, stream);
+}
+
+int dsgcn_adam_step_clip_hyper(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
+                               const int* first, int ntens, const double* lr, const double* wd, int groups,
+                               const double* partial, int rows, int norm_type, float max_norm, float* grad_norm_out,
+                               const double* hyper, double beta2, float eps, int decoupled, long long n, void* stream) {
+  if (!hyper || (norm_type != 0 && norm_type != 2)) return DSGCN_EINVAL;
+  const OpTable tab = {ends, group, first, lr, wd, ntens, groups};
+  const OpClip clip = {partial, grad_norm_out, rows, norm_type == 0 ? 1 : 0, max_norm};
+  return op_adam(p, g, m, v, step, tab, &clip, 0., hyper, beta2, eps, decoupled, n, stream);
 }
 
 }  // extern "C"

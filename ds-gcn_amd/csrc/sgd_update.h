@@ -4,6 +4,12 @@
 // the clipped step with coefficient 1 is bit-identical to the plain one.
 #pragma once
 
+// A value every lane of the wave holds alike, moved to a scalar register: what depends on it (whether the momentum buffer
+// is touched at all) then branches once per wave, as it does on a by-value kernel argument.
+__device__ __forceinline__ float uniform_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
 __device__ __forceinline__ float sgd_update(float pv, float gv, float& bv, bool has_buf, float rate, float mom, float wd,
                                             int nesterov) {
   gv = fmaf(wd, pv, gv);

@@ -27,7 +27,7 @@ class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
                  warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1, optimizer=None,
-                 matmul_precision=None):
+                 matmul_precision=None, scheduled_momentum=False):
         """optimizer: mmcv's ``optimizer`` dict (``type`` 'SGD' | 'Adam' | 'AdamW', ..., ``paramwise_cfg``; see
         ``train.build_optimizer``) or a ``FlatSGD`` / ``FlatAdam`` built over ``FlatParams(model, gather=True)`` — in place of
         the keywords lr / momentum / weight_decay / nesterov (and, for a built one, of grad_clip / accumulate, which it
@@ -44,6 +44,9 @@ class TrainEngine:
         micro-iteration — forward, backward (its own BatchNorm statistics, its own dropout masks), gradient added to the
         accumulator — and every k-th one also averages the k gradients, exchanges, clips and updates, at the rate passed
         on THAT call: k micro-batches on one GPU are the reference's k ranks.  ``flush()`` closes a short last group.
+        scheduled_momentum: the optimizer built here keeps its momentum (SGD) / beta1 (Adam) in device memory and
+        ``step(..., momentum=...)`` rewrites it: graph B follows a momentum schedule as it follows the rate (a built
+        optimizer carries its own flag).
         matmul_precision: 'highest' | 'high' (``kernels.set_matmul_precision``) or None = the process level at this moment.
         Fixed here: every eager step, capture and replay of this engine runs under it, whatever the process level is set
         to later and whatever level another engine of the process uses."""
@@ -60,10 +63,12 @@ class TrainEngine:
         if isinstance(optimizer, (FlatSGD, FlatAdam)):
             self.opt = optimizer
         elif optimizer is not None:
-            self.opt = build_optimizer(self.flat, optimizer, grad_clip=grad_clip, accumulate=accumulate)
+            self.opt = build_optimizer(self.flat, optimizer, grad_clip=grad_clip, accumulate=accumulate,
+                                       scheduled_momentum=scheduled_momentum)
         else:
             self.opt = FlatSGD(self.flat, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                               capturable=True, grad_clip=grad_clip, accumulate=accumulate)
+                               capturable=True, grad_clip=grad_clip, accumulate=accumulate,
+                               scheduled_momentum=scheduled_momentum)
         if getattr(self.opt, 'table', None) is not None and bool(use_graph) and warmup_eager < 1:
             raise ValueError(f'{type(self.opt).__name__} with per-tensor groups needs warmup_eager >= 1: the first step runs '
                              'eagerly, the parameters that receive no gradient are marked there')
@@ -139,15 +144,20 @@ class TrainEngine:
         return dict(logs, grad_norm=self.opt.grad_norm[0] if static else self.opt.grad_norm[0].clone())
 
     # ---- the step ------------------------------------------------------------------------------------------
-    def step(self, keypoint, label, lr=None):
+    def step(self, keypoint, label, lr=None, momentum=None):
         """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc; grad_norm with grad_clip): no host
-        sync here.  With accumulate > 1: one micro-iteration; grad_norm is the one of the last update."""
+        sync here.  With accumulate > 1: one micro-iteration; grad_norm is the one of the last update.
+        momentum: the momentum (SGD) / beta1 (Adam) of this iteration, for an optimizer with ``scheduled_momentum``.  As
+        mmcv's momentum hooks do it is set before every iteration and the update sees the last one: under accumulation
+        the value given at the stepping call."""
         with kernels.matmul_precision(self.matmul_precision):
-            return self._step(keypoint, label, lr)
+            return self._step(keypoint, label, lr, momentum)
 
-    def _step(self, keypoint, label, lr):
+    def _step(self, keypoint, label, lr, momentum=None):
         if lr is not None:
             self.opt.set_lr(lr)
+        if momentum is not None:
+            self.opt.set_momentum(momentum)
         key = (tuple(keypoint.shape), tuple(label.shape))
         kind = None
         if self.accumulate > 1:
@@ -182,10 +192,10 @@ class TrainEngine:
         self.iter += 1
         return logs
 
-    def flush(self, remainder=None, lr=None):
+    def flush(self, remainder=None, lr=None, momentum=None):
         """Close a short group early: average the ``remainder`` gradients in the accumulator (all of them; None = however
         many there are), exchange, clip and update — mmcv's rule for the last ``max_iters % k`` iterations of a run, which
-        it divides by their own count.  The rate is ``lr`` or the one of the last call.  Eager launches (once per run or
+        it divides by their own count.  The rate (the momentum) is ``lr`` (``momentum``) or the one of the last call.  Eager launches (once per run or
         epoch); no forward runs, so no BatchNorm statistic and no dropout counter moves.  -> {} or {'grad_norm': ...}."""
         if self.accumulate == 1:
             raise RuntimeError('flush(): this engine does not accumulate (accumulate=1)')
@@ -195,6 +205,8 @@ class TrainEngine:
             raise ValueError(f'flush({remainder}): the accumulator holds {self.pending} gradient(s)')
         if lr is not None:
             self.opt.set_lr(lr)
+        if momentum is not None:
+            self.opt.set_momentum(momentum)
         self.flat.flat_g.zero_()                   # the group's gradients are all in the accumulator already
         self.opt.accum_finish(remainder)
         self._exchange()

@@ -180,6 +180,20 @@ SIGNATURES = {
     'dsgcn_adam_step_clip': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
                              ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_double, ctypes.c_double,
                              ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    # the six updates with momentum / beta1 in device memory: `hyper` (const double*) where the parent has the value
+    'dsgcn_sgd_step_hyper': [c_f, c_f, c_f, c_f, ctypes.c_void_p, ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_sgd_step_clip_hyper': [c_f, c_f, c_f, c_f, ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_void_p,
+                                  ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_sgd_group_step_hyper': [c_f, c_f, c_f, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                   ctypes.c_void_p, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_sgd_group_step_clip_hyper': [c_f, c_f, c_f, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                        ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_void_p, c_int,
+                                        ctypes.c_longlong, c_st],
+    'dsgcn_adam_step_hyper': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                              ctypes.c_void_p, ctypes.c_double, ctypes.c_float, c_int, ctypes.c_longlong, c_st],
+    'dsgcn_adam_step_clip_hyper': [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                   ctypes.c_void_p, c_int, c_int, ctypes.c_float, c_f, ctypes.c_void_p, ctypes.c_double,
+                                   ctypes.c_float, c_int, ctypes.c_longlong, c_st],
     'dsgcn_bn_running_multi': [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
                                ctypes.POINTER(ctypes.c_float), c_int, c_st],
 }

@@ -182,6 +182,28 @@ class _FlatOptimizer:
     def zero_grad(self):
         self.flat.zero_grad()
 
+    # ---- a momentum (SGD) / beta1 (Adam) that follows a schedule ----------------------------------------------------------
+    def _setup_hyper(self, scheduled, value):
+        """scheduled_momentum: the value lives in ``hyper_t`` (one fp64 device element, allocated here and only ever written
+        in place), the update launches are the ``*_hyper`` forms that read it there, and ``set_momentum`` rewrites it — so a
+        ``step()`` captured in a hipGraph follows a momentum schedule as it follows the rates.  ``initial_momentum`` is the
+        schedule's base (mmcv's momentum hooks keep it in the param groups)."""
+        self.scheduled_momentum = bool(scheduled)
+        self.hyper_t = self.initial_momentum = None
+        if self.scheduled_momentum:
+            self.initial_momentum = check_momentum(value)
+            self.hyper_t = torch.full((1,), self.initial_momentum, device=self.flat.flat_p.device, dtype=torch.float64)
+
+    def set_momentum(self, value):
+        """The momentum (FlatSGD) / beta1 (FlatAdam) of the next ``step()``: validated, then one in-place fill — like
+        ``set_lr`` the value travels in the launch's arguments, no staging buffer, no sync."""
+        if not self.scheduled_momentum:
+            raise RuntimeError(f'{type(self).__name__}.set_momentum: build the optimizer with scheduled_momentum=True — the '
+                               'update launches of this one take the value as an argument, a captured step would keep it')
+        value = check_momentum(value)
+        self._store_momentum(value)
+        self.hyper_t.fill_(value)
+
 
     # ---- per-tensor groups and parameters without a gradient (FlatAdam; FlatSGD with a group table) --------------------
     def _setup_groups(self, rules, paramwise, default_wd):
@@ -308,7 +330,12 @@ class FlatSGD(_FlatOptimizer):
 
 
     def __init__(self, flat, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, capturable=False, grad_clip=None,
-                 accumulate=1, rules=None, paramwise=True):
+                 accumulate=1, rules=None, paramwise=True, scheduled_momentum=False):
+        """scheduled_momentum: see ``_setup_hyper`` / ``set_momentum``.  Implies ``capturable``; the momentum buffer exists
+        from the start whatever the first value (a schedule may pass through 0 and leave it again: at 0 the buffer is left
+        alone, as torch leaves it)."""
+        if scheduled_momentum:
+            capturable = True
         self.lr = lr
         self.base_lr = lr
         self.momentum = momentum
@@ -321,9 +348,10 @@ class FlatSGD(_FlatOptimizer):
         self.lr_t = None
         if capturable and rules is None:
             self.lr_t = torch.full((1,), float(lr), device=flat.flat_p.device, dtype=flat.flat_p.dtype)
-        if capturable and momentum:
+        if capturable and (momentum or scheduled_momentum):
             self.buf = torch.zeros_like(flat.flat_p)       # torch's first step sets buf = g; momentum * 0 + g is the same value
         self._setup(flat, capturable, grad_clip, accumulate)
+        self._setup_hyper(scheduled_momentum, momentum)
         if rules is not None:
             if not momentum >= 0.0:
                 raise ValueError(f'Invalid momentum value: {momentum}')
@@ -336,11 +364,16 @@ class FlatSGD(_FlatOptimizer):
         if self.lr_t is not None:
             self.lr_t.fill_(self.lr)
 
+    def _store_momentum(self, value):
+        self.momentum = value
+
     @torch.no_grad()
     def _step_grouped(self):
         p, g, t = self.flat.flat_p, self.flat.flat_g, self.table
         if self._fused():
             st = torch.cuda.current_stream().cuda_stream
+            if self.scheduled_momentum:
+                return self._step_grouped_hyper(p, g, t, st)
             buf = self.buf.data_ptr() if self.momentum else None
             if self.clip is not None:
                 self._norm_partials(g, st)
@@ -367,11 +400,45 @@ class FlatSGD(_FlatOptimizer):
                 d = d.add(bv, alpha=self.momentum) if self.nesterov else bv
             pv.add_(d, alpha=-lr)
 
+    def _step_grouped_hyper(self, p, g, t, st):
+        """The grouped launches with the momentum read from ``hyper_t`` (csrc/optim.hip, the DEV forms)."""
+        hyper, nesterov = self.hyper_t.data_ptr(), int(bool(self.nesterov))
+        if self.clip is not None:
+            self._norm_partials(g, st)
+            rc = native.lib().dsgcn_sgd_group_step_clip_hyper(p.data_ptr(), g.data_ptr(), self.buf.data_ptr(), *t.pointers(),
+                                                              self.clip_partial.data_ptr(), self.clip_partial.numel(),
+                                                              self.clip[1], self.clip[0], self.grad_norm.data_ptr(), hyper,
+                                                              nesterov, p.numel(), st)
+            native.check(rc, 'dsgcn_sgd_group_step_clip_hyper')
+        else:
+            rc = native.lib().dsgcn_sgd_group_step_hyper(p.data_ptr(), g.data_ptr(), self.buf.data_ptr(), *t.pointers(), hyper,
+                                                         nesterov, p.numel(), st)
+            native.check(rc, 'dsgcn_sgd_group_step_hyper')
+
+    def _step_hyper(self, p, g):
+        """``dsgcn_sgd_step[_clip]`` with the momentum read from ``hyper_t`` (k_sgd_hyper / k_sgd_clip_hyper)."""
+        st = torch.cuda.current_stream().cuda_stream
+        if self.clip is not None:
+            max_norm, norm_type = self.clip
+            self._norm_partials(g, st)
+            rc = native.lib().dsgcn_sgd_step_clip_hyper(p.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self.lr_t.data_ptr(),
+                                                        self.clip_partial.data_ptr(), self.clip_partial.numel(), norm_type,
+                                                        max_norm, self.grad_norm.data_ptr(), self.hyper_t.data_ptr(),
+                                                        float(self.weight_decay), int(bool(self.nesterov)), p.numel(), st)
+            native.check(rc, 'dsgcn_sgd_step_clip_hyper')
+        else:
+            rc = native.lib().dsgcn_sgd_step_hyper(p.data_ptr(), g.data_ptr(), self.buf.data_ptr(), self.lr_t.data_ptr(),
+                                                   self.hyper_t.data_ptr(), float(self.weight_decay),
+                                                   int(bool(self.nesterov)), p.numel(), st)
+            native.check(rc, 'dsgcn_sgd_step_hyper')
+
     @torch.no_grad()
     def step(self):
         if self.table is not None:
             return self._step_grouped()
         p, g = self.flat.flat_p, self.flat.flat_g
+        if self.scheduled_momentum and self._fused():
+            return self._step_hyper(p, g)
         if self.clip is not None and self._fused():
             # norm partials, then clip + update in one launch (csrc/clip.hip): one extra read of the flat gradient
             max_norm, norm_type = self.clip
@@ -420,6 +487,8 @@ class FlatSGD(_FlatOptimizer):
         group = dict(lr=self.lr, momentum=self.momentum, dampening=0, weight_decay=self.weight_decay,
                      nesterov=self.nesterov, maximize=False, foreach=None, differentiable=False, fused=None,
                      initial_lr=self.base_lr, params=list(range(len(self.flat.params))))
+        if self.scheduled_momentum:
+            group['initial_momentum'] = self.initial_momentum
         return {'state': state, 'param_groups': [group]}
 
     def load_state_dict(self, sd):
@@ -433,7 +502,7 @@ class FlatSGD(_FlatOptimizer):
         g = groups[0]
         self.set_lr(g['lr'])
         self.base_lr = g.get('initial_lr', self.base_lr)
-        self.momentum = g.get('momentum', self.momentum)
+        self._load_momentum(g.get('momentum', self.momentum))
         self.weight_decay = g.get('weight_decay', self.weight_decay)
         self.nesterov = g.get('nesterov', self.nesterov)
         state = sd.get('state', {})
@@ -453,6 +522,14 @@ class FlatSGD(_FlatOptimizer):
                 buf[off:off + n].copy_(mb.reshape(-1))
         self.buf = buf
 
+    def _load_momentum(self, value):
+        """A checkpoint's current momentum: to the device too when it is scheduled (the schedule's base, ``initial_momentum``,
+        always comes from the config)."""
+        if self.scheduled_momentum:
+            self.set_momentum(value)
+        else:
+            self.momentum = value
+
     def _state_dict_grouped(self):
         """The same layout with the parameters numbered over ALL of ``parameters()`` and, under paramwise_cfg, one param
         group per tensor; a tensor that never received a gradient has no state entry."""
@@ -463,12 +540,14 @@ class FlatSGD(_FlatOptimizer):
                     state[self.param_ids[i]] = {'momentum_buffer': self.buf[off:off + n].view(p.shape).detach().cpu().clone()}
         extra = dict(momentum=self.momentum, dampening=0, nesterov=self.nesterov, maximize=False, foreach=None,
                      differentiable=False, fused=None)
+        if self.scheduled_momentum:
+            extra['initial_momentum'] = self.initial_momentum
         return {'state': state, 'param_groups': self._torch_groups(extra)}
 
     def _load_state_dict_grouped(self, sd):
         saved = self._load_groups(sd['param_groups'])
         g0 = sd['param_groups'][0]
-        self.momentum = g0.get('momentum', self.momentum)
+        self._load_momentum(g0.get('momentum', self.momentum))
         self.nesterov = g0.get('nesterov', self.nesterov)
         state = sd.get('state', {})
         if self.buf is not None:
@@ -497,7 +576,9 @@ class FlatAdam(_FlatOptimizer):
     tensor, ``exp_avg``, ``exp_avg_sq``; every param group carries ``initial_lr``)."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, decoupled=False, grad_clip=None,
-                 accumulate=1, rules=None, paramwise=None):
+                 accumulate=1, rules=None, paramwise=None, scheduled_momentum=False):
+        """scheduled_momentum: beta1 follows a schedule (``_setup_hyper`` / ``set_momentum``); torch's behaviour when a param
+        group's ``betas[0]`` changes between steps, bias correction ``1 - beta1 ** t`` with the current value included."""
         from .paramwise import param_rules
         default_wd = 1e-2 if decoupled else 0.0            # torch.optim.AdamW / Adam
         if not 0.0 <= lr:
@@ -512,6 +593,7 @@ class FlatAdam(_FlatOptimizer):
         self.eps = float(eps)
         self.decoupled = bool(decoupled)
         self._setup(flat, True, grad_clip, accumulate)
+        self._setup_hyper(scheduled_momentum, self.betas[0])
         if rules is None:
             rules = param_rules(flat.module, lr, weight_decay)
         self._setup_groups(rules, bool(paramwise), default_wd)
@@ -525,6 +607,9 @@ class FlatAdam(_FlatOptimizer):
         """Updates taken so far (one host read)."""
         return int(self.step_t[0])
 
+    def _store_momentum(self, value):
+        self.betas = (value, self.betas[1])
+
     @torch.no_grad()
     def step(self):
         p, g, t = self.flat.flat_p, self.flat.flat_g, self.table
@@ -532,6 +617,17 @@ class FlatAdam(_FlatOptimizer):
             st = torch.cuda.current_stream().cuda_stream
             head = (p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.step_t.data_ptr()) + t.pointers()
             tail = (self.betas[0], self.betas[1], self.eps, int(self.decoupled), p.numel(), st)
+            if self.scheduled_momentum:                    # beta1 read from hyper_t (csrc/optim.hip, the DEV forms)
+                tail = (self.hyper_t.data_ptr(),) + tail[1:]
+                if self.clip is not None:
+                    self._norm_partials(g, st)
+                    rc = native.lib().dsgcn_adam_step_clip_hyper(*head, self.clip_partial.data_ptr(),
+                                                                 self.clip_partial.numel(), self.clip[1], self.clip[0],
+                                                                 self.grad_norm.data_ptr(), *tail)
+                    native.check(rc, 'dsgcn_adam_step_clip_hyper')
+                else:
+                    native.check(native.lib().dsgcn_adam_step_hyper(*head, *tail), 'dsgcn_adam_step_hyper')
+                return
             if self.clip is not None:
                 self._norm_partials(g, st)
                 rc = native.lib().dsgcn_adam_step_clip(*head, self.clip_partial.data_ptr(), self.clip_partial.numel(),
@@ -569,6 +665,8 @@ class FlatAdam(_FlatOptimizer):
                                                 'exp_avg_sq': self.v[off:off + n].view(p.shape).detach().cpu().clone()}
         extra = dict(betas=self.betas, eps=self.eps, amsgrad=False, maximize=False, foreach=None, capturable=False,
                      differentiable=False, fused=None, decoupled_weight_decay=self.decoupled)
+        if self.scheduled_momentum:
+            extra['initial_momentum'] = self.initial_momentum
         return {'state': state, 'param_groups': self._torch_groups(extra)}
 
     def load_state_dict(self, sd):
@@ -577,6 +675,8 @@ class FlatAdam(_FlatOptimizer):
         saved = self._load_groups(sd['param_groups'])
         g0 = sd['param_groups'][0]
         self.betas = tuple(float(b) for b in g0.get('betas', self.betas))
+        if self.scheduled_momentum:
+            self.set_momentum(self.betas[0])               # the current value, on the device too
         self.eps = float(g0.get('eps', self.eps))
         state = sd.get('state', {})
         self.m.zero_()
@@ -594,9 +694,10 @@ class FlatAdam(_FlatOptimizer):
         self.step_t.fill_(steps.pop() if steps else 0)
 
 
-def build_optimizer(flat, cfg, grad_clip=None, accumulate=1):
+def build_optimizer(flat, cfg, grad_clip=None, accumulate=1, scheduled_momentum=False):
     """mmcv's ``build_optimizer(model, cfg)`` over a ``FlatParams``: ``cfg = dict(type='SGD' | 'Adam' | 'AdamW', ...,
-    paramwise_cfg=...)`` with torch's defaults for absent keys.  SGD without ``paramwise_cfg`` is the plain ``FlatSGD``."""
+    paramwise_cfg=...)`` with torch's defaults for absent keys.  SGD without ``paramwise_cfg`` is the plain ``FlatSGD``.
+    scheduled_momentum: the run has a ``momentum_config`` — momentum / beta1 live on the device (``set_momentum``)."""
     from .paramwise import param_rules
     cfg = dict(cfg)
     kind = cfg.pop('type', 'SGD')
@@ -619,10 +720,11 @@ def build_optimizer(flat, cfg, grad_clip=None, accumulate=1):
             raise ValueError('Nesterov momentum requires a momentum and zero dampening')
         if paramwise_cfg is None:
             return FlatSGD(flat, lr=lr, momentum=momentum, weight_decay=base_wd or 0, nesterov=nesterov, capturable=True,
-                           grad_clip=grad_clip, accumulate=accumulate)
+                           grad_clip=grad_clip, accumulate=accumulate, scheduled_momentum=scheduled_momentum)
         rules = param_rules(flat.module, lr, base_wd, paramwise_cfg)
         return FlatSGD(flat, lr=lr, momentum=momentum, weight_decay=base_wd or 0, nesterov=nesterov, capturable=True,
-                       grad_clip=grad_clip, accumulate=accumulate, rules=rules, paramwise=True)
+                       grad_clip=grad_clip, accumulate=accumulate, rules=rules, paramwise=True,
+                       scheduled_momentum=scheduled_momentum)
     if kind in ('Adam', 'AdamW'):
         if cfg.pop('amsgrad', False):
             raise NotImplementedError('optimizer amsgrad=True is not supported')
@@ -633,7 +735,8 @@ def build_optimizer(flat, cfg, grad_clip=None, accumulate=1):
             raise NotImplementedError(f'{kind} options {sorted(cfg)} are not supported')
         rules = param_rules(flat.module, lr, base_wd, paramwise_cfg)
         return FlatAdam(flat, lr=lr, betas=betas, eps=eps, weight_decay=base_wd, decoupled=kind == 'AdamW',
-                        grad_clip=grad_clip, accumulate=accumulate, rules=rules, paramwise=paramwise_cfg is not None)
+                        grad_clip=grad_clip, accumulate=accumulate, rules=rules, paramwise=paramwise_cfg is not None,
+                        scheduled_momentum=scheduled_momentum)
     raise NotImplementedError(f'optimizer type {kind!r}: SGD, Adam and AdamW are implemented')
 
 
@@ -696,3 +799,107 @@ def step_lr(base_lr, progress, step, gamma=0.1, min_lr=None):
     if min_lr is not None:
         lr = max(lr, min_lr)
     return lr
+
+
+# ---- mmcv's other rate policies and its two momentum policies: pure functions of the run's position -----------------------
+# `progress` is runner.iter or runner.epoch (by_epoch), `max_progress` max_iters or max_epochs.
+
+def cos_anneal(start, end, factor, weight=1):
+    """mmcv annealing_cos: from ``start`` (factor 0) to ``end`` (factor 1) along half a cosine."""
+    return end + 0.5 * weight * (start - end) * (math.cos(math.pi * factor) + 1)
+
+
+def lin_anneal(start, end, factor):
+    """mmcv annealing_linear."""
+    return (end - start) * factor + start
+
+
+ANNEAL = {'cos': cos_anneal, 'linear': lin_anneal}
+
+
+def anneal_target(base, min_lr=None, min_lr_ratio=None):
+    """The floor of the cosine policies: ``min_lr``, or ``base * min_lr_ratio`` — exactly one of the two (mmcv asserts it)."""
+    if (min_lr is None) == (min_lr_ratio is None):
+        raise ValueError('exactly one of min_lr and min_lr_ratio must be given')
+    return base * min_lr_ratio if min_lr_ratio is not None else min_lr
+
+
+def exp_lr(base, progress, gamma):
+    """mmcv ExpLrUpdaterHook."""
+    return base * gamma ** progress
+
+
+def poly_lr(base, progress, max_progress, power=1., min_lr=0.):
+    """mmcv PolyLrUpdaterHook."""
+    coeff = (1 - progress / max_progress) ** power
+    return (base - min_lr) * coeff + min_lr
+
+
+def inv_lr(base, progress, gamma, power=1.):
+    """mmcv InvLrUpdaterHook."""
+    return base * (1 + gamma * progress) ** (-power)
+
+
+def cosine_restart_lr(base, progress, periods, restart_weights=(1,), min_lr=None, min_lr_ratio=None):
+    """mmcv CosineRestartLrUpdaterHook: period i runs from cum[i - 1] to cum[i] and anneals from
+    ``target + restart_weights[i] * (base - target)`` down to the target."""
+    target = anneal_target(base, min_lr, min_lr_ratio)
+    cum = 0
+    for i, period in enumerate(periods):
+        start, cum = cum, cum + period
+        if progress < cum:
+            alpha = min((progress - start) / period, 1)
+            return cos_anneal(base, target, alpha, restart_weights[i])
+    raise ValueError(f'Current iteration {progress} exceeds cumulative_periods {cum}')
+
+
+def cyclic_value(base, it, max_iters, target_ratio=(10, 1e-4), cyclic_times=1, step_ratio_up=0.4, anneal='cos'):
+    """mmcv CyclicLrUpdaterHook / CyclicMomentumUpdaterHook (by iteration): ``cyclic_times`` cycles of
+    ``L = max_iters // cyclic_times`` iterations, each ``base -> base * target_ratio[0]`` over the first
+    ``int(step_ratio_up * L)`` iterations and ``-> base * target_ratio[1]`` over the rest."""
+    length = max_iters // cyclic_times
+    up = int(step_ratio_up * length)
+    c = it % length
+    fn = ANNEAL[anneal]
+    if c < up:
+        return fn(base, base * target_ratio[0], c / up)
+    return fn(base * target_ratio[0], base * target_ratio[1], (c - up) / (length - up))
+
+
+def onecycle_value(values, it, total_steps, pct_start=0.3, anneal='cos', three_phase=False):
+    """The phase walk mmcv's OneCycleLrUpdaterHook and OneCycleMomentumUpdaterHook share (torch's OneCycleLR).  values:
+    the phase end points, ``(v0, v1, v2)`` for two phases (v0 -> v1 until ``pct_start * S - 1``, v1 -> v2 until ``S - 1``),
+    ``(v0, v1, v2, v3)`` for three (the middle one ends at ``2 * pct_start * S - 2``)."""
+    ends = [float(pct_start * total_steps) - 1]
+    if three_phase:
+        ends.append(float(2 * pct_start * total_steps) - 2)
+    ends.append(total_steps - 1)
+    fn = ANNEAL[anneal]
+    start = 0
+    for i, end in enumerate(ends):
+        if it <= end:
+            return fn(values[i], values[i + 1], (it - start) / (end - start))
+        start = end
+    raise ValueError(f'iteration {it} lies beyond the {total_steps} steps of the cycle')
+
+
+def onecycle_lr_values(base, div_factor=25, final_div_factor=1e4, three_phase=False):
+    """Phase end points of the OneCycle rate for a group whose initial rate is ``base`` (= max_lr / div_factor)."""
+    if three_phase:
+        return base * 1, base * div_factor, base * 1, base * (1 / final_div_factor)
+    return base * 1, base * div_factor, base * (1 / final_div_factor)
+
+
+def onecycle_momentum_values(base_momentum=0.85, max_momentum=0.95, three_phase=False):
+    """Phase end points of the OneCycle momentum: max -> base -> max, and with three phases max held to the end."""
+    if three_phase:
+        return max_momentum, base_momentum, max_momentum, max_momentum
+    return max_momentum, base_momentum, max_momentum
+
+
+def check_momentum(value, what='momentum'):
+    """A scheduled momentum / beta1 must lie in [0, 1): the update kernels read it from device memory and use it as it is."""
+    value = float(value)
+    if not 0.0 <= value < 1.0:
+        raise ValueError(f'{what} {value!r} is outside [0, 1)')
+    return value

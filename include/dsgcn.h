@@ -835,6 +835,46 @@ int dsgcn_adam_step_clip(float* p, float* g, float* m, float* v, int* step, cons
                          int rows, int norm_type, float max_norm, float* grad_norm_out, double beta1, double beta2,
                          float eps, int decoupled, long long n, void* stream);
 
+/* The six update launches above with the momentum (SGD) resp. beta1 (Adam) read from DEVICE memory, so that a launch
+ * captured in a hipGraph follows a momentum schedule on replay the way it follows the rate schedule (mmcv's
+ * CyclicMomentumUpdaterHook / OneCycleMomentumUpdaterHook beside the Cyclic / OneCycle rate policies).  Each takes its
+ * parent's arguments in its parent's order, with `const double* hyper` where the parent has `float momentum` /
+ * `double beta1`: ONE fp64 value in device memory, 8-byte aligned — fp64 because it is a Python float of a torch param
+ * group, like lr[groups].  The host rewrites it in place between launches.
+ *   SGD forms   the parent's update with momentum = (float)hyper[0] (round to nearest, as the by-value argument is
+ *               converted).  buf is REQUIRED whatever the value: a schedule may pass through 0 and leave it again.  At a
+ *               value of exactly 0 buf is neither read nor written — what the parent does when its caller passes
+ *               momentum 0, and what torch does (`if momentum != 0`): the next non-zero step continues from the old buffer.
+ *   Adam forms  the parent's update with beta1 = hyper[0], bc1 = 1 - beta1^t in fp64 included: torch's behaviour when a
+ *               param group's betas[0] changes between steps.  beta2 stays by value.
+ * With hyper[0] equal to the parent's by-value argument every output (p, buf / m, v, step, the written-back g,
+ * grad_norm_out) is bit-identical to the parent's, for the same table and clip state.  One launch, no allocation, no
+ * sync, the parents' alignment and tail rules; the value is one scalar load per wave.
+ * The value cannot be checked on the host: the kernel uses it AS IT IS.  Outside [0, 1) (or NaN) the update is whatever
+ * the formulas give — beta1 = 1 divides by bc1 = 0.  The caller validates before it writes (FlatSGD / FlatAdam
+ * .set_momentum do).
+ * DSGCN_EINVAL: what the parent rejects (except its momentum / beta1 range checks), hyper NULL or not 8-byte aligned, and
+ * in the SGD forms buf NULL. */
+int dsgcn_sgd_step_hyper(float* p, const float* g, float* buf, const float* lr, const double* hyper, float weight_decay,
+                         int nesterov, long long n, void* stream);
+int dsgcn_sgd_step_clip_hyper(float* p, float* g, float* buf, const float* lr, const double* partial, int rows,
+                              int norm_type, float max_norm, float* grad_norm_out, const double* hyper, float weight_decay,
+                              int nesterov, long long n, void* stream);
+int dsgcn_sgd_group_step_hyper(float* p, float* g, float* buf, const int* ends, const int* group, const int* first, int ntens,
+                               const double* lr, const double* wd, int groups, const double* hyper, int nesterov,
+                               long long n, void* stream);
+int dsgcn_sgd_group_step_clip_hyper(float* p, float* g, float* buf, const int* ends, const int* group, const int* first,
+                                    int ntens, const double* lr, const double* wd, int groups, const double* partial,
+                                    int rows, int norm_type, float max_norm, float* grad_norm_out, const double* hyper,
+                                    int nesterov, long long n, void* stream);
+int dsgcn_adam_step_hyper(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
+                          const int* first, int ntens, const double* lr, const double* wd, int groups, const double* hyper,
+                          double beta2, float eps, int decoupled, long long n, void* stream);
+int dsgcn_adam_step_clip_hyper(float* p, float* g, float* m, float* v, int* step, const int* ends, const int* group,
+                               const int* first, int ntens, const double* lr, const double* wd, int groups,
+                               const double* partial, int rows, int norm_type, float max_norm, float* grad_norm_out,
+                               const double* hyper, double beta2, float eps, int decoupled, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
