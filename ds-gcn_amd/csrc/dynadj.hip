@@ -435,8 +435,9 @@ __global__ __launch_bounds__(NT) void k_dynadj_bwd(
     float* pwe = par + KSUB * VV + 6;
     float* pbe_ = pwe + EM * m;
     // the long tiles split K in two when the scratch T (SC | SCp: dead after the Gram step) holds both halves of both
-    // operands; the halves are added, in order, when dproj is written
-    const int KS = ksplit, kh = ((EM / KS + 3) & ~3);
+    // operands; the halves are added, in order, when dproj is written.  kh: the first half, the ceiling of EM / 2 rounded
+    // up to a k-step (rounding the floor up dropped the last row of We at EM = 8j + 1, e.g. E = 33, mid = 9)
+    const int KS = ksplit, kh = (((EM + KS - 1) / KS + 3) & ~3);
     const int nlong = 2 * ct * vt * KS;
     for (int job = wave; job < nlong + mt * ct; job += NW) {
       if (job < nlong) {
@@ -516,6 +517,16 @@ size_t dyn_lds_bytes(int mid, int V, int E, bool bwd, int pm) {
   return f * sizeof(float);
 }
 
+constexpr size_t DYN_LDS_MAX = 158 * 1024;      // dynamic LDS of a launch (the backward adds 128 static bytes)
+
+// Channel windows per (sample, subset) of the forward, 0 = no launch holds the shape.  Two where they fill the chip at
+// small batches (windows of >= 8 channels); otherwise one, and two again where only the half-width P / Q image fits.
+int dyn_fwd_windows(int n, int mid, int V, int E) {
+  int split = (n <= 128 && mid >= 16) ? 2 : 1;
+  if (split == 1 && mid >= 2 && dyn_lds_bytes(mid, V, E, false, mid) > DYN_LDS_MAX) split = 2;
+  return dyn_lds_bytes(mid, V, E, false, (mid + split - 1) / split) <= DYN_LDS_MAX ? split : 0;
+}
+
 }  // namespace
 
 // the model's (V, mid) combinations get their own instantiation, everything else the run-time form
@@ -533,6 +544,14 @@ extern "C" {
 // floats per sample of the backward's parameter-partial buffer
 int dsgcn_dynadj_partial_stride(int mid, int V, int E) { return KSUB * V * V + 6 + E * mid * mid + E * mid; }
 
+// The range of both launches, stated once: V <= 32 joints, mid <= 64, rows of at least V joints, and an LDS image (the
+// carve above lds_G) within DYN_LDS_MAX — the forward's in one or two channel windows, the backward's in one.
+int dsgcn_dynadj_supported(int n, int mid, int V, int ld, int E, int backward) {
+  if (n < 1 || mid < 1 || V < 1 || E < 1 || V > 32 || mid > 64 || ld < V) return DSGCN_EUNSUPPORTED;
+  if (backward) return dyn_lds_bytes(mid, V, E, true, mid) <= DYN_LDS_MAX ? 0 : DSGCN_EUNSUPPORTED;
+  return dyn_fwd_windows(n, mid, V, E) ? 0 : DSGCN_EUNSUPPORTED;
+}
+
 int dsgcn_dynadj_fwd_jobs(const float* proj, const float* A, const float* alpha, const float* beta, const float* we,
                           const float* be, const int* node_type, const int* edge_type, float* ahat, int n, int mid, int V,
                           int ld, int P, int E, const dsgcn_bn_fin_job* jobs, int njobs, void* stream) {
@@ -547,12 +566,10 @@ int dsgcn_dynadj_fwd_jobs(const float* proj, const float* A, const float* alpha,
   }
   if (!bnj_fin_ok(jt)) return DSGCN_EINVAL;
   const int jblocks = bnj_total_blocks(jt);
-  if (V > 32 || mid > 64 || ld < V) return DSGCN_EUNSUPPORTED;      // (the LDS check below is what bounds mid for a given E)
-  // channel windows per (sample, subset): enough workgroups to fill the chip at small batches, windows of >= 8 channels
-  int split = (n <= 128 && mid >= 16) ? 2 : 1;
+  if (int rc = dsgcn_dynadj_supported(n, mid, V, ld, E, 0)) return rc;
+  const int split = dyn_fwd_windows(n, mid, V, E);
   size_t lds = dyn_lds_bytes(mid, V, E, false, (mid + split - 1) / split);
   if (njobs && lds < 2048) lds = 2048;          // the hosted job blocks reduce through 2 KB of it
-  if (lds > 158 * 1024) return DSGCN_EUNSUPPORTED;
   DynDims d{n, ld, mid, V, P, E, 0, mid};
 #define DYN_FWD(VT, MD)                                                                                               \
   {                                                                                                                   \
@@ -595,11 +612,10 @@ int dsgcn_dynadj_bwd_jobs(const float* proj, const float* alpha, const float* be
   }
   if (!bnj_coef_ok(jt)) return DSGCN_EINVAL;
   const int jblocks = bnj_total_blocks(jt);
-  if (V > 32 || mid > 64 || ld < V) return DSGCN_EUNSUPPORTED;      // (the LDS check below is what bounds mid for a given E)
+  if (int rc = dsgcn_dynadj_supported(n, mid, V, ld, E, 1)) return rc;
   if (pstride < dsgcn_dynadj_partial_stride(mid, V, E)) return DSGCN_EINVAL;
   size_t lds = dyn_lds_bytes(mid, V, E, true, mid);
   if (njobs && lds < 2048) lds = 2048;
-  if (lds > 158 * 1024) return DSGCN_EUNSUPPORTED;
   DynDims d{n, ld, mid, V, P, E, 0, mid};
 #define DYN_BWD(VT, MD)                                                                                               \
   {                                                                                                                   \

@@ -165,7 +165,12 @@ class dgphgcn1(nn.Module):
     Rejected (NotImplementedError naming the flag): target_specific with decompose (a node-typed `pre` conv), ctr / ada
     other than 'T', activations other than tanh / softmax / ReLU, K != 3, and on the flag path V > 32, mid > 64,
     edge_num > 16, num_types > 16.  Under decompose subset 2 pairs conv1_se with itself: conv2_se is created and never
-    used (quirk Q1)."""
+    used (quirk Q1).
+
+    Range of the shipped flag set (K-B, ``dsgcn_dynadj_supported``): V <= 32; forward mid <= 64 at any batch size;
+    backward mid <= 37 at V = 25 with 15 edge classes (mid <= 27 at V = 32) — its LDS image is the larger one.  The
+    constructor default ratio = 0.25 gives mid = 64 at 256 channels: such a unit evaluates under ``torch.no_grad()``, and a
+    forward that would record a backward raises NotImplementedError naming mid, V, E and the largest mid that trains."""
 
     def __init__(self, in_channels, out_channels, A, edge_type, node_type, ratio=0.25, decompose=False, ctr='T',
                  ada='T', node_attention=False, edge_attention=False, ada_attention=False, target_specific=False,
@@ -204,6 +209,7 @@ class dgphgcn1(nn.Module):
         self.norm_num = K - S
         # the shipped arithmetic (sub_att / add_type do not enter it at K = 3) stays on today's K-B
         self._shipped = bool(decompose and node_attention and edge_attention and subset_wise and not ada_attention)
+        self._kb_trains = None          # shipped path: whether K-B's backward holds this (mid, V, edge_num); asked on first use
         V = A.size(-1)
         nt = torch.as_tensor(node_type).to(torch.int32).contiguous()
         et = torch.as_tensor(edge_type).to(torch.int32).contiguous()
@@ -275,6 +281,15 @@ class dgphgcn1(nn.Module):
                 self.node_type_idx.reshape(-1), self.edge_type_idx.reshape(-1),
                 self.num_types if self.node_attention else 1, self.edge_num, self.subset_wise)
         cs, el = self.conv1_se, self.edge_linears
+        if self._kb_trains is None:               # K-B's forward holds wider mid than its backward (dsgcn_dynadj_supported)
+            V = self.A.shape[-1]
+            self._kb_trains = kernels.native.lib().dsgcn_dynadj_supported(1, self.mid_channels, V, max(V, 32),
+                                                                          self.edge_num, 1) == 0
+        if not self._kb_trains and torch.is_grad_enabled() and (xbar.requires_grad or any(p.requires_grad for p in (
+                self.A, self.alpha, self.beta, c1.weight, c1.bias, c2.weight, c2.bias, cs.weight, cs.bias, el.weight, el.bias))):
+            # (raises: the call would record a backward that cannot launch; the same unit evaluates under no_grad)
+            kernels.native.dynadj_require_backward(self.mid_channels, self.A.shape[-1], self.edge_num,
+                                                   max(32, self.A.shape[-1]), 'dgphgcn1')
         kw = {} if host is None else dict(host=host)
         if proj_req is not None:
             kw['proj_req'] = proj_req

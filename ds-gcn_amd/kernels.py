@@ -857,7 +857,8 @@ def aggregate(zp, ap, relu, ahat):
 
 class _DynAdj(torch.autograd.Function):
     """proj (n, (4+P)*mid, ld) rows [a | b | s-typed] (ld >= V: padded joint stride) -> Ahat (n, 3*mid, V, V)
-    (K-B, one HIP launch each way)."""
+    (K-B, one HIP launch each way).  A call that records a backward the kernel could not launch raises before anything is
+    launched (``native.dynadj_require_backward``); the same shape without gradients runs."""
 
     @staticmethod
     def forward(ctx, proj, A, alpha, beta, we, be, node_type, edge_type, single_use=True, host=None):
@@ -870,6 +871,8 @@ class _DynAdj(torch.autograd.Function):
         E = we.shape[0] // mid
         P = (R // mid - 4)
         assert A.shape[0] == 3 and node_type.dtype == torch.int32 and edge_type.dtype == torch.int32
+        if any(ctx.needs_input_grad):
+            native.dynadj_require_backward(mid, V, E, ld)
         ahat = torch.empty((n, 3 * mid, V, V), device=proj.device, dtype=torch.float32)
         jobs = host.take() if host is not None else []
         if len(jobs) > native.BN_JOBS_MAX:

@@ -125,6 +125,7 @@ SIGNATURES = {
     'dsgcn_skeleton_prep': [ctypes.c_void_p] * 11 + [c_int] * 10 + [c_st],
     'dsgcn_skeleton_prep_streams': [ctypes.c_void_p] * 10 + [ctypes.POINTER(ctypes.c_void_p)] + [c_int] * 10 + [c_st],
     'dsgcn_dynadj_partial_stride': [c_int, c_int, c_int],
+    'dsgcn_dynadj_supported': [c_int] * 6,
     'dsgcn_dynadj_fwd': [c_f] * 6 + [c_i, c_i, c_f] + [c_int] * 6 + [c_st],
     'dsgcn_dynadj_bwd': [c_f] * 5 + [c_i, c_i] + [c_f] * 4 + [c_int] * 7 + [c_st],
     'dsgcn_pwconv_group_ok': [c_int] * 5,
@@ -396,3 +397,24 @@ def check(code, what):
     if code != 0:
         kind = 'argument rejected' if code < 0 else 'hipError_t'
         raise DsgcnError(f'{what} failed: {kind} {code}')
+
+
+_dynadj_range = {}
+
+
+def dynadj_require_backward(mid, V, E, ld=32, who='dynadj'):
+    """K-B's forward holds shapes its backward does not (the backward keeps P_e / Q_e of all ``mid`` channels plus its
+    gradient scratch in LDS; ``dsgcn_dynadj_supported`` is the one statement of both ranges).  Raises NotImplementedError
+    where a backward of this shape could not launch — asked before the forward runs, by whoever is about to record one."""
+    key = (mid, V, E, ld)
+    if key not in _dynadj_range:
+        ok = lib().dsgcn_dynadj_supported
+        msg = None
+        if ok(1, mid, V, ld, E, 1) != 0:
+            top = max([m for m in range(1, 65) if ok(1, m, V, ld, E, 1) == 0], default=0)
+            if top:                     # (no mid fits: V, E or ld is out of range, and the forward's launch says so)
+                msg = (f'mid = {mid} at V = {V} joints, E = {E} edge classes: the K-B backward holds mid <= {top} at '
+                       'this V and E (its LDS image), so this shape evaluates under torch.no_grad() but cannot train')
+        _dynadj_range[key] = msg
+    if _dynadj_range[key] is not None:
+        raise NotImplementedError(f'{who}: {_dynadj_range[key]}')

@@ -76,11 +76,16 @@ int dsgcn_aggregate_bwd(const float* zp, const float* scale, const float* shift,
  *        of the unit input (computed by dsgcn_pwconv_fwd on xbar viewed as (n,Ci,1,ld)); ld >= V is the joint stride of a
  *        row (32: rows zero-padded so the K-C kernels take their 16-byte-per-lane path);
  *   A (3,V,V); alpha,beta (3);  we (E*mid,mid) row e*mid+c, be (E*mid)
- *   node_type (V) int32 in [0,P);  edge_type (V*V) int32 in [0,E);  ahat out (n,3*mid,V,V).  V <= 32, mid <= 32.
+ *   node_type (V) int32 in [0,P);  edge_type (V*V) int32 in [0,E);  ahat out (n,3*mid,V,V).  Range: dsgcn_dynadj_supported.
  * Backward: dd_ws workspace (n,3*mid,V,V); outputs dproj (n,(4+P)*mid,ld) (padding columns zero) and ppar (n, pstride >=
  * dsgcn_dynadj_partial_stride): per-sample partials [sum_c dAhat (3*V*V) | dalpha (3) | dbeta (3) | dwe (E*mid*mid) |
  * dbe (E*mid)] — their sum over samples (dsgcn_colsum: ordered, no float atomics) gives dA, dalpha, dbeta, dwe, dbe. */
 int dsgcn_dynadj_partial_stride(int mid, int V, int E);
+/* The range of the two launches, which both ask here: 0, or DSGCN_EUNSUPPORTED where V > 32, mid > 64, ld < V or the
+ * launch's LDS image passes 158 KB.  Forward (backward = 0): the image holds P_e / Q_e of one channel window, half of mid
+ * where the full width does not fit; at V = 25, E = 15 that is every mid <= 64, at any n.  Backward (backward = 1): all of
+ * mid plus the gradient scratch; at E = 15 mid <= 60 at V = 17, 37 at V = 25, 27 at V = 32.  Needs no device. */
+int dsgcn_dynadj_supported(int n, int mid, int V, int ld, int E, int backward);
 int dsgcn_dynadj_fwd(const float* proj, const float* A, const float* alpha, const float* beta, const float* we,
                      const float* be, const int* node_type, const int* edge_type, float* ahat, int n, int mid, int V,
                      int ld, int P, int E, void* stream);

@@ -117,9 +117,41 @@ def test_dynadj(n, Ci, mid, V, layout):
     check_dynadj(n, Ci, mid, V, layout)
 
 
-def check_dynadj(n, Ci, mid, V, layout, single_use=True):
-    """single_use=False: what dggcn passes (its A feeds two calls; the parameter sums are never deferred)."""
-    t, nt, et = _dyn_inputs(n, Ci, mid, V, layout, seed=Ci + mid)
+def _dyn_host_chunks(t, nt, et, dah, order, single_use, chunk=16):
+    """The fp64 statement on the HOST, a few samples at a time: parameter gradients add over the chunks, the per-sample one
+    (xbar) concatenates.  Only a failing full-size comparison pays for it."""
+    n = dah.shape[0]
+    grads = {}
+    for s in range(0, n, chunk):
+        tt = {k: v.detach().clone().double() for k, v in t.items()}
+        tt['xbar'] = tt['xbar'][s:s + chunk].clone()
+        for v in tt.values():
+            v.requires_grad_()
+        out = R.dynadj(*[tt[k] for k in order], nt, et, single_use=single_use)
+        out.backward(dah[s:s + chunk].double())
+        for k, v in tt.items():
+            if k == 'xbar':
+                grads.setdefault(k, []).append(v.grad)
+            else:
+                grads[k] = v.grad if k not in grads else grads[k] + v.grad
+    grads['xbar'] = torch.cat(grads['xbar'])
+    return grads
+
+
+def _dyn_diagnosis(k, got, gpu_ref, n, host):
+    """What goes into the message of a failing gradient comparison at full size (n >= 64: the fp64 statement ran on the
+    GPU): the same gradient against a host evaluation of the statement, so that the failure says which side moved."""
+    if n < 64:
+        return ()
+    h = host()[k]
+    return ('rel(kernel, host) %.3e' % rel(got, h), 'rel(gpu_ref, host) %.3e' % rel(gpu_ref, h),
+            'rel(kernel, gpu_ref) %.3e' % rel(got, gpu_ref))
+
+
+def check_dynadj(n, Ci, mid, V, layout, single_use=True, inputs=None):
+    """single_use=False: what dggcn passes (its A feeds two calls; the parameter sums are never deferred).
+    inputs: (t, node_type, edge_type) of ``dynadj_cases.dyn_inputs`` in place of a layout's graph (any V, P, E)."""
+    t, nt, et = _dyn_inputs(n, Ci, mid, V, layout, seed=Ci + mid) if inputs is None else inputs
     g = torch.Generator().manual_seed(7)
     dah = torch.randn(n, 3 * mid, V, V, generator=g)
     order = list(t)
@@ -135,7 +167,8 @@ def check_dynadj(n, Ci, mid, V, layout, single_use=True):
     # forward: tanh/exp in fp32 (ocml, ~1-2 ulp) + <=256-term dot products
     assert rel(out.cpu(), ro) < 2e-6, rel(out.cpu(), ro)
     for k in order:
-        assert rel(grads[k].cpu(), rg[k]) < 2e-5, (k, rel(grads[k].cpu(), rg[k]))      # fp32 chain rule
+        assert rel(grads[k].cpu(), rg[k]) < 2e-5, (k, rel(grads[k].cpu(), rg[k])) + _dyn_diagnosis(      # fp32 chain rule
+            k, grads[k], rg[k], n, lambda: _dyn_host_chunks(t, nt, et, dah, order, single_use))
     # no float atomics anywhere in K-B (per-sample partials + ordered column sums): bit-reproducible run to run
     out2, grads2 = run(K, torch.float32, DEV)
     assert torch.equal(out, out2) and all(torch.equal(grads[k], grads2[k]) for k in order)
