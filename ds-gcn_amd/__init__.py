@@ -13,7 +13,7 @@ from .evaluation import top_k_accuracy, mean_class_accuracy, confusion_matrix
 from .losses import CrossEntropyLoss
 from .heads import GCNHead, SimpleHead
 from .gcn_units import dggcn, dghgcn, dgphgcn1, unit_aagcn, unit_gcn, unit_ctrgcn, unit_ctrhgcn, CTRGC, CTRHGC, Deferred
-from .tcn_units import dgmstcn, mstcn, msmlp, unitmlp, unit_tcn, MSTCN
+from .tcn_units import dgmstcn, dgmsmlp, mstcn, msmlp, unitmlp, unit_tcn, MSTCN
 from .backbones import DGSTGCN, STGCN, CTRGCN, AAGCN, DGBlock, STGCNBlock, CTRGCNBlock, AAGCNBlock
 from .recognizers import RecognizerGCN, reduce_log_vars, gather_results
 from . import kernels

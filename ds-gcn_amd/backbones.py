@@ -16,7 +16,7 @@ from . import kernels
 from .builder import BACKBONES
 from .gcn_units import dggcn, dghgcn, dgphgcn1, unit_aagcn, unit_ctrgcn, unit_ctrhgcn, unit_gcn, flush_running_stats
 from .graph import Graph
-from .tcn_units import MSTCN, dgmstcn, msmlp, mstcn, unit_tcn, unitmlp
+from .tcn_units import MSTCN, dgmsmlp, dgmstcn, msmlp, mstcn, unit_tcn, unitmlp
 
 EPS = 1e-4
 
@@ -69,7 +69,7 @@ class _FusedBlock(nn.Module):
         x = xc
         r = hold = None
         batch = getattr(kernels.ops(), 'bn_batch', None)
-        if self.residual_kind == 'conv' and batch is not None and type(self.tcn) is dgmstcn:
+        if self.residual_kind == 'conv' and batch is not None and type(self.tcn) in (dgmstcn, dgmsmlp):
             # the residual conv reads only the block input: issued FIRST, its BatchNorm finalize waits (kernels.bn_batch) for
             # the transform conv's at the end of the temporal unit — one launch for the two (and one coefficient launch for
             # the two in fuse_out's backward)
@@ -120,8 +120,10 @@ class DGBlock(_FusedBlock):
             self.tcn = unit_tcn(out_channels, out_channels, 9, stride=stride, **tcn_kwargs)
         elif tcn_type == 'dgmstcn':
             self.tcn = dgmstcn(out_channels, out_channels, stride=stride, **tcn_kwargs)
+        elif tcn_type == 'mstcn':
+            self.tcn = mstcn(out_channels, out_channels, stride=stride, **tcn_kwargs)
         else:
-            raise NotImplementedError(f'tcn_type={tcn_type} is outside the DS-GCN hot path (SURVEY §8f)')
+            self.tcn = dgmsmlp(out_channels, out_channels, stride=stride, **tcn_kwargs)
         gcn_type = gcn_kwargs.pop('type', 'dghgcn')
         assert gcn_type in ['dghgcn', 'dgphgcn', 'dgphgcn1', 'dggcn']
         if gcn_type == 'dggcn':                      # the original DG-STGCN unit (dgstgcn.py:42-43)

@@ -1594,7 +1594,12 @@ class _TapBranches(torch.autograd.Function):
     strided copy — one HIP launch per direction.  Window i reads channels [ci0,ci0+cin) and writes [co0,co0+cout)."""
 
     @staticmethod
-    def forward(ctx, h, stride, KT, Cout, types, ci0s, co0s, cins, couts, dils, *wb):
+    def forward(ctx, *args):
+        return _TapBranches._run(ctx, torch.empty, *args)
+
+    @staticmethod
+    def _run(ctx, alloc, h, stride, KT, Cout, types, ci0s, co0s, cins, couts, dils, *wb):
+        """alloc: torch.empty (every channel of o and of dh belongs to a window), or torch.zeros (_TapBranchesZero)"""
         _require_cuda(h)
         h = _f32c(h)
         n, Cin, T, V1 = h.shape
@@ -1602,7 +1607,8 @@ class _TapBranches(torch.autograd.Function):
         ws = [_f32c(t) for t in wb[:nbr]]
         bs = [_f32c(t) for t in wb[nbr:]]
         Tout = (T + stride - 1) // stride
-        o = torch.empty((n, Cout, Tout, V1), device=h.device, dtype=torch.float32)
+        ctx.alloc = alloc
+        o = alloc((n, Cout, Tout, V1), device=h.device, dtype=torch.float32)
         rc = native.lib().dsgcn_tapconv_fwd(_ptr(h), _ptr(o), n, Cin, Cout, T, V1, stride, KT, nbr, _int_array(types),
                                             _int_array(ci0s), _int_array(co0s), _int_array(cins), _int_array(couts),
                                             _int_array(dils), _ptr_array(ws), _ptr_array(bs), _stream())
@@ -1625,7 +1631,7 @@ class _TapBranches(torch.autograd.Function):
         ws = [next(it) if t == 0 else None for t in types]
         tabs = (_int_array(types), _int_array(ci0s), _int_array(co0s), _int_array(cins), _int_array(couts),
                 _int_array(dils))
-        dh = torch.empty_like(h)
+        dh = ctx.alloc(h.shape, device=h.device, dtype=torch.float32)
         rc = lib.dsgcn_tapconv_dgrad(_ptr(h), _ptr(go), _ptr(dh), n, Cin, Cout, T, V1, stride, KT, nbr, *tabs,
                                      _ptr_array(ws), _stream())
         native.check(rc, 'dsgcn_tapconv_dgrad')
@@ -1918,6 +1924,22 @@ def temporal_ms(z, zaug, scale, shift, n_act, branch_cfg, widths, conv_w, conv_b
     if want_bn:
         _bn_attach(out[1], bn, out[3], out[4], gamma, eps, float(o.shape[0] * o.shape[2] * (o.shape[3] - 1)), o.shape[1])
     return out
+
+
+class _TapBranchesZero(_TapBranches):
+    """_TapBranches whose windows do not cover every channel: the channels of o (forward) and of dh (backward) that no
+    window names are zero."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _TapBranches._run(ctx, torch.zeros, *args)
+
+
+# dgmsmlp's mlp windows (kernels_mlpwin.dgmlp_windows): '1' = csrc/mlpwin.hip wherever dsgcn_mlpwin_supported takes the
+# shape, '0' = the staged launches (dwcausal, block-diagonal 1x1, add), 'auto' (default) = the kernel for calls that record
+# no backward, the staged launches for those that do: at the three widths of DGSTGCN the kernel's forward is level or
+# ahead, its backward behind (profiles/dgmsmlp/README.md).  Tests and tools set True / False.
+MLPWIN = _os.environ.get('DSGCN_MLPWIN', 'auto')
 
 
 class _PlaneStats(torch.autograd.Function):
@@ -3081,3 +3103,6 @@ from .kernels_head import head_target  # noqa: E402,F401
 
 # the position-typed 1x1 conv of CTRHGC's target_specific / full_channels arms (csrc/typedconv.hip) likewise
 from .kernels_typedconv import TypedPlan, typed_conv, typed_plan  # noqa: E402,F401
+# dgmsmlp's temporal stage and its mlp-window kernel (csrc/mlpwin.hip)
+from .kernels_mlpwin import (_MlpWin, _mlpwin_tables, dgmlp_windows, mlpwin_supported,  # noqa: E402,F401
+                             temporal_dgmlp)

@@ -562,3 +562,136 @@ class msmlp(dgmstcn):
             self.merge_after, self.stride, g_, b_, eps, want), lambda f: f.shape[0] * f.shape[2] * f.shape[3])
         zt, _, a2 = conv_bn(f, a1, None, None, True, self.transform[2], 1, False, self.bn)
         return Deferred(zt, a2, None, None, False)
+
+
+class dgmsmlp(dgmstcn):
+    """The "mlp" temporal unit of DGSTGCN (reference: tcn.py:432-523) = ``dgmstcn`` (multi-scale, with the global joint)
+    with ``unitmlp`` in place of the dilated-conv branches; ``add_tcn=False`` (the class default) runs the taps and the
+    1x1 conv alone.  HIP chain: the stacked branch conv with the global-joint column (one K-C launch + statistics),
+    branch_act, tapconv (alpha-scaled dilated convs / max-pool / strided copy), the mlp windows (csrc/mlpwin.hip: one
+    launch), combine + the statistics of transform.0; transform's BN rides to its conv as a deferred affine."""
+
+    def __init__(self, in_channels, out_channels, mid_channels=None, num_joints=25, dropout=0.,
+                 ms_cfg=[(3, 1), (3, 2), (3, 3), (3, 4), ('max', 3), '1x1'], stride=1, channel_annention=False,
+                 adaptive=True, add_tcn=False, merge_after=False):
+        nn.Module.__init__(self)
+        if channel_annention:
+            raise NotImplementedError('dgmsmlp(channel_annention=True) has no HIP path')
+        self.ms_cfg = [tuple(c) if isinstance(c, (list, tuple)) else c for c in ms_cfg]
+        seen_plain = False
+        for cfg in self.ms_cfg:
+            if cfg == '1x1':
+                seen_plain = True
+                continue
+            if seen_plain:
+                raise NotImplementedError("dgmsmlp: '1x1' branches must come last in ms_cfg on the HIP path")
+            if cfg[0] == 'max':
+                if cfg[1] != 3:
+                    raise NotImplementedError(f'dgmsmlp: max-pool kernel {cfg[1]} in ms_cfg (only 3 has a HIP path)')
+            elif cfg[0] not in (3, 5, 9):
+                raise NotImplementedError(f'dgmsmlp: kernel size {cfg[0]} in ms_cfg (the HIP path covers 3, 5 and 9)')
+        if len({c[0] for c in self.ms_cfg if c != '1x1' and c[0] != 'max'}) > 1:
+            raise NotImplementedError('dgmsmlp: the mlp branches of ms_cfg must share one kernel size on the HIP path')
+        num_branches = len(ms_cfg)
+        self.num_branches, self.in_channels, self.out_channels, self.stride = num_branches, in_channels, out_channels, stride
+        self.act = nn.ReLU()
+        self.num_joints = num_joints
+        self.add_tcn, self.merge_after = add_tcn, merge_after
+        self.add_coeff = nn.Parameter(torch.zeros(self.num_joints))
+        if mid_channels is None:
+            mid_channels = out_channels // num_branches
+            rem_mid_channels = out_channels - mid_channels * (num_branches - 1)
+        else:
+            assert isinstance(mid_channels, float) and mid_channels > 0
+            mid_channels = int(out_channels * mid_channels)
+            rem_mid_channels = mid_channels
+        self.mid_channels, self.rem_mid_channels = mid_channels, rem_mid_channels
+        branches, self.widths = [], []
+        for i, cfg in enumerate(self.ms_cfg):
+            bc = rem_mid_channels if i == 0 else mid_channels
+            self.widths.append(bc)
+            if cfg == '1x1':
+                branches.append(nn.Conv2d(in_channels, bc, kernel_size=1, stride=(stride, 1)))
+            elif cfg[0] == 'max':
+                branches.append(nn.Sequential(
+                    nn.Conv2d(in_channels, bc, kernel_size=1), nn.BatchNorm2d(bc), self.act,
+                    nn.MaxPool2d(kernel_size=(cfg[1], 1), stride=(stride, 1), padding=(1, 0))))
+            else:
+                branches.append(nn.Sequential(
+                    nn.Conv2d(in_channels, bc, kernel_size=1), nn.BatchNorm2d(bc), self.act,
+                    unitmlp(bc, bc, kernel_size=cfg[0], stride=stride, dilation=cfg[1], norm=None, adaptive=adaptive,
+                            channel_annention=channel_annention, add_tcn=add_tcn, merge_after=merge_after)))
+        self.branches = nn.ModuleList(branches)
+        tin_channels = mid_channels * (num_branches - 1) + rem_mid_channels
+        self.transform = nn.Sequential(nn.BatchNorm2d(tin_channels), self.act,
+                                       nn.Conv2d(tin_channels, out_channels, kernel_size=1))
+        self.bn = nn.BatchNorm2d(out_channels)
+        self.drop = nn.Dropout(dropout, inplace=True)
+        self.n_act = sum(w for w, c in zip(self.widths, self.ms_cfg) if c != '1x1')
+        mlps = self._mlps()
+        self.mlp_size = mlps[0].mlp_size if mlps else 2
+        dil = []
+        for w, cfg in zip(self.widths, self.ms_cfg):
+            dil += [int(cfg[1]) if (cfg != '1x1' and cfg[0] != 'max') else 0] * w
+        self.register_buffer('dw_dil', torch.tensor(dil, dtype=torch.int32), persistent=False)
+
+    def _mlps(self):
+        return [b[3] for b in self.branches if not isinstance(b, nn.Conv2d) and isinstance(b[3], unitmlp)]
+
+    def forward_deferred(self, g, hold=None):
+        """(see dgmstcn.forward_deferred) g: tensor or Deferred -> Deferred(zt, affine of self.bn)."""
+        ops = kernels.ops()
+        d = as_deferred(g)
+        n, _, T, V = d.x1.shape
+        convs = self._first_convs()
+        wb = kernels.cat_rows([c.weight.flatten(1) for c in convs])
+        bb = kernels.cat_rows([c.bias for c in convs])
+        bns = [b[1] for b in self.branches if not isinstance(b, nn.Conv2d)]
+        count = n * T * (V + 1)
+        if any(_need_stats(bn) for bn in bns):
+            gamma = kernels.cat_rows([bn.weight for bn in bns])
+            beta = kernels.cat_rows([bn.bias for bn in bns])
+            z, zaug, scale, shift, m, var = ops.pwconv(d.x1, d.a1, d.x2, d.a2, d.relu, wb, bb, 1, True, gamma, beta,
+                                                      bns[0].eps, self.n_act, True)
+            c0 = 0
+            for bn in bns:
+                record_running(bn, m[c0:c0 + bn.num_features], var[c0:c0 + bn.num_features], count)
+                c0 += bn.num_features
+        else:
+            z, zaug = ops.pwconv(d.x1, d.a1, d.x2, d.a2, d.relu, wb, bb, 1, True)[:2]
+            aff = [eval_affine(bn) for bn in bns]
+            rest = self.out_channels - self.n_act
+            scale = torch.cat([a[0] for a in aff] + ([z.new_ones(rest)] if rest else []))
+            shift = torch.cat([a[1] for a in aff] + ([z.new_zeros(rest)] if rest else []))
+        mlps = self._mlps()
+        tw = tb = None
+        if self.add_tcn:      # the dilated convs carry their window's alpha (KB-sized products; autograd returns d alpha)
+            tw = [u.conv2.weight * u.alpha for u in mlps]
+            tb = [u.conv2.bias * u.alpha for u in mlps]
+        # depthwise taps by channel: zero rows outside the mlp windows
+        rows_w, rows_b = [], []
+        it = iter(mlps)
+        for w, cfg in zip(self.widths, self.ms_cfg):
+            if cfg != '1x1' and cfg[0] != 'max':
+                u = next(it)
+                rows_w.append(u.conv.weight.flatten(1))
+                rows_b.append(u.conv.bias)
+            else:
+                rows_w.append(z.new_zeros(w, self.mlp_size))
+                rows_b.append(z.new_zeros(w))
+        dw_w, dw_b = kernels.cat_rows(rows_w), kernels.cat_rows(rows_b)
+        w1s = [u.conv1.weight.flatten(1) for u in mlps]
+        b1s = [u.conv1.bias for u in mlps]
+        bn1 = self.transform[0]
+        args = (z, zaug, scale, shift, self.n_act, self.ms_cfg, self.widths, tw, tb, dw_w, dw_b, self.dw_dil, w1s, b1s,
+                self.add_coeff, self.merge_after, self.stride)
+        if _need_stats(bn1):
+            f, s1, h1, m1, v1 = ops.temporal_dgmlp(*args, bn1.weight, bn1.bias, bn1.eps, True)
+            record_running(bn1, m1, v1, f.shape[0] * f.shape[2] * f.shape[3])
+            a1 = (s1, h1)
+        else:
+            f = ops.temporal_dgmlp(*args)[0]
+            a1 = eval_affine(bn1)
+        with (hold if hold is not None else contextlib.nullcontext()):
+            zt, _, a2 = conv_bn(f, a1, None, None, True, self.transform[2], 1, False, self.bn)
+        return Deferred(zt, a2, None, None, False)

@@ -521,6 +521,32 @@ int dsgcn_dwcausal_fwd(const float* h, const float* w, const float* b, const int
 int dsgcn_dwcausal_bwd(const float* h, const float* w, const int* dil, const float* dy, float* dh, float* part, int n,
                        int C, int T, int V, int stride, int KM, void* stream);
 
+/* The mlp windows of dgmsmlp (csrc/mlpwin.hip; tcn.py:432-523 over unitmlp 525-614) as one launch per direction, on the
+ * (V+1)-column planes between dsgcn_branch_act / dsgcn_tapconv and dsgcn_tms_combine.  h (n,C,T,V1); o, u (n,C,T',V1),
+ * T' = ceil(T/stride); tapw (C,KM), tapb (C) the depthwise causal taps (the formula of dsgcn_dwcausal) by channel.
+ * Window tables: parallel HOST arrays, nwin <= 8, the windows tile [0,C) in order: type (0 mlp / 1 copy), c0, width,
+ * dil, add (mlp: 0 = no addend, 1 = u = W1.(dw + o) + b1, 2 = u = W1.dw + b1 + o; copy: u = o), w1[i] (width,width) and
+ * b1[i] (width) device pointers (NULL for copy windows).  Every element of u is written; a channel of o that is neither
+ * copied nor added is never read (o may be NULL when there is none).  The width x width mix runs on the fp32-input MFMA
+ * (exact fp32; dsgcn_set_matmul_precision does not apply).
+ * Range (dsgcn_mlpwin_supported = 1, else 0; asked before anything launches): width <= 64, KM in {2,3,5}, V1 <= 33,
+ * stride 1 or 2, at least one mlp window.  Outside it the launches return DSGCN_EUNSUPPORTED.
+ * Backward: from du it writes every element of dh (n,C,T,V1) (zero outside the mlp windows), of dout (n,C,T',V1) (du for
+ * copy windows and add = 2, W1^T.du for add = 1, zero for add = 0) and of part (n, pstride), pstride =
+ * dsgcn_mlpwin_partial_stride: row = [dtapw (C*KM) | dtapb (C) | per mlp window in order: dW1 (width*width), db1 (width)];
+ * dsgcn_colsum over the rows finishes them (no float atomics).  gbuf (n,C,T',V1): work buffer, required unless every mlp
+ * window has add = 1.  o is read under add = 1 only. */
+int dsgcn_mlpwin_supported(int n, int C, int T, int V1, int stride, int KM, int nwin, const int* type, const int* c0,
+                           const int* width, const int* dil, const int* add);
+int dsgcn_mlpwin_partial_stride(int C, int KM, int nwin, const int* type, const int* width);
+int dsgcn_mlpwin_fwd(const float* h, const float* o, float* u, const float* tapw, const float* tapb, int n, int C, int T,
+                     int V1, int stride, int KM, int nwin, const int* type, const int* c0, const int* width, const int* dil,
+                     const int* add, const float* const* w1, const float* const* b1, void* stream);
+int dsgcn_mlpwin_bwd(const float* h, const float* o, const float* du, const float* tapw, const float* tapb, float* dh,
+                     float* dout, float* gbuf, float* part, int n, int C, int T, int V1, int stride, int KM, int nwin, const int* type,
+                     const int* c0, const int* width, const int* dil, const int* add, const float* const* w1, int pstride,
+                     void* stream);
+
 /* K-D, fused (csrc/tms.hip): the whole multi-scale temporal stage between the two 1x1 convs of dgmstcn / mstcn / MSTCN
  * (reference: pyskl/models/gcns/utils/tcn.py:383-396,409-420 and msg3d_utils.py:84-117) as ONE launch per direction on
  * the (n, C, T, V) layout, any V:
