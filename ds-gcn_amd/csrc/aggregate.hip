@@ -54,9 +54,6 @@ __device__ __forceinline__ void load_plane_to_lds(const float* __restrict__ src,
 #include "lab/aggregate_valu.h"   // superseded VALU formulation, A/B measurements only
 #endif
 
-// MFMA C/D row of accumulator register r for this lane (32x32 tile): (r&3) + 8*(r>>2) + 4*(lane>>5)
-__device__ __forceinline__ int mfma_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 template <int V>
 __global__ __launch_bounds__(64) void k_aggregate_fwd(const float* __restrict__ zp, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, int relu,
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(64) void k_aggregate_fwd(const float* __restrict__ 
     for (int tile = 0; tile < 2; ++tile) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int t = tile * 32 + mfma_row(r, mk);
+        const int t = tile * 32 + mfma_row32(r, mk);
         if (t < rows) ldsP[t * V + mi] = acc[tile][r];
       }
     }
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(64 * KA_WPB) void k_aggregate_fwd_pipe(const float*
         for (int tile = 0; tile < NTILE; ++tile) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int t = tile * 32 + mfma_row(r, mk);
+            const int t = tile * 32 + mfma_row32(r, mk);
             if (t < rows) yo[t * V + mi] = acc[tile][r];
           }
         }
@@ -269,7 +266,7 @@ __global__ __launch_bounds__(64 * KA_WPB) void k_aggregate_fwd_pipe(const float*
         for (int tile = 0; tile < NTILE; ++tile) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int t = tile * 32 + mfma_row(r, mk);
+            const int t = tile * 32 + mfma_row32(r, mk);
             if (t < rows) ldsP[t * V + mi] = acc[tile][r];
           }
         }
@@ -364,7 +361,7 @@ __global__ __launch_bounds__(64) void k_aggregate_bwd(const float* __restrict__ 
         if (mi < V) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int tt = tile * 32 + mfma_row(r, mk);
+            const int tt = tile * 32 + mfma_row32(r, mk);
             if (tt < rows) {
               const float z = ldsZ[tt * V + mi];
               const float pre = fmaf(z, s, h);
@@ -398,7 +395,7 @@ __global__ __launch_bounds__(64) void k_aggregate_bwd(const float* __restrict__ 
   if (mi < V) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int u = mfma_row(r, mk);
+      const int u = mfma_row32(r, mk);
       if (u < V) dA[u * V + mi] = accA[r];
     }
   }
@@ -510,7 +507,7 @@ __global__ __launch_bounds__(64 * KA_WPB) void k_aggregate_bwd_pipe(const float*
       if (mi < V) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int u = mfma_row(r, mk);
+          const int u = mfma_row32(r, mk);
           if (u < V) __builtin_nontemporal_store(accA[r], &dA[u * V + mi]);
         }
       }
@@ -520,7 +517,7 @@ __global__ __launch_bounds__(64 * KA_WPB) void k_aggregate_bwd_pipe(const float*
       if (mi < V) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int u = mfma_row(r, mk);
+          const int u = mfma_row32(r, mk);
           if (u < V) ldsA[u * V + mi] = accA[r];
         }
       }
@@ -545,7 +542,7 @@ __global__ __launch_bounds__(64 * KA_WPB) void k_aggregate_bwd_pipe(const float*
         if (mi < V) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int tt = tile * 32 + mfma_row(r, mk);
+            const int tt = tile * 32 + mfma_row32(r, mk);
             if (tt < rows) {
               const float z = ldsZ[tt * V + mi];
               const float pre = fmaf(z, s, h);
@@ -658,8 +655,7 @@ __global__ __launch_bounds__(64 * NW) void k_aggregate_bwd_pair(const float* __r
     }
     const long next = unit + gridDim.x;
     if (next < units) issue(next);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     float bt[KS];
 #pragma unroll
     for (int q = 0; q < KS; ++q) {
@@ -696,7 +692,7 @@ __global__ __launch_bounds__(64 * NW) void k_aggregate_bwd_pair(const float* __r
       float* dd = ldsD + (wave - 1) * V * V;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int u = mfma_row(r, mk);
+        const int u = mfma_row32(r, mk);
         if (u < V) dd[u * V + mi] = accA[r];
       }
     }
@@ -717,7 +713,7 @@ __global__ __launch_bounds__(64 * NW) void k_aggregate_bwd_pair(const float* __r
       if (mi < V) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int tt = mfma_row(r, mk);
+          const int tt = mfma_row32(r, mk);
           if (tt < rows) {
             const float z = ldsZ[tt * V + mi];
             const float pre = fmaf(z, s, h);
@@ -729,13 +725,12 @@ __global__ __launch_bounds__(64 * NW) void k_aggregate_bwd_pair(const float* __r
         }
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     if (wave == 0 && mi < V) {
       float* __restrict__ dA = dahat + (size_t)unit * V * V;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int u = mfma_row(r, mk);
+        const int u = mfma_row32(r, mk);
         if (u < V) {
           float v = accA[r];
           for (int w = 0; w < NW - 1; ++w) v += ldsD[w * V * V + u * V + mi];

@@ -19,8 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int as_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 template <int V>
 __device__ __forceinline__ void as_load_plane(const float* __restrict__ src, float* lds, int cnt, int lane, bool vec) {
   constexpr int NP4 = (64 * V / 4 + 63) / 64;
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(64) void k_aggsum_fwd(const float* __restrict__ p, 
       for (int tile = 0; tile < 2; ++tile) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int t = tile * 32 + as_row(r, mk);
+          const int t = tile * 32 + mfma_row32(r, mk);
           if (t < rows) {
             const float v = acc[tile][r];
             yo[t * V + mi] = v;
@@ -232,7 +230,7 @@ __global__ __launch_bounds__(64) void k_aggsum_bwd(const float* __restrict__ p, 
           if (mi < V) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int tt = tile * 32 + as_row(r, mk);
+              const int tt = tile * 32 + mfma_row32(r, mk);
               if (tt < rows) dpo[tt * V + mi] = acc[r];
             }
           }
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(64) void k_aggsum_bwd(const float* __restrict__ p, 
     if (mi < V) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int u = as_row(r, mk);
+        const int u = mfma_row32(r, mk);
         if (u < V) dA[u * V + mi] = accA[r];
       }
     }
@@ -356,7 +354,7 @@ __global__ __launch_bounds__(64) void k_aggsum_fwd_pipe(const float* __restrict_
       if (mi < V) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int t = as_row(r, mk);
+          const int t = mfma_row32(r, mk);
           if (t < rows) {
             const float v = acc[r];
             ldsP[t * V + mi] = v;
@@ -594,7 +592,7 @@ __global__ __launch_bounds__(64 * NW, NW == 2 ? 3 : 2) void k_aggsum_bwd_pipe(co
       } else if (NW > 1 && wave > 0 && mi < V) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int u = as_row(r, mk);
+          const int u = mfma_row32(r, mk);
           if (u < V) ldsD[u * V + mi] = accA[r];
         }
       }
@@ -617,7 +615,7 @@ __global__ __launch_bounds__(64 * NW, NW == 2 ? 3 : 2) void k_aggsum_bwd_pipe(co
         if (mi < V) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int tt = as_row(r, mk);
+            const int tt = mfma_row32(r, mk);
             if (tt < rows) ldsZ[tt * V + mi] = acc[r];
           }
         }
@@ -639,7 +637,7 @@ __global__ __launch_bounds__(64 * NW, NW == 2 ? 3 : 2) void k_aggsum_bwd_pipe(co
         float* __restrict__ dA = dahat + n * d_ns + k * d_ks + c * d_cs;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int u = as_row(r, mk);
+          const int u = mfma_row32(r, mk);
           if (u < V) dA[u * V + mi] = accA[r] + (NW > 1 ? ldsD[u * V + mi] : 0.f);
         }
       }
@@ -652,7 +650,7 @@ __global__ __launch_bounds__(64 * NW, NW == 2 ? 3 : 2) void k_aggsum_bwd_pipe(co
     for (int j = 0; j < KACC; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int u = as_row(r, mk);
+        const int u = mfma_row32(r, mk);
         if (u < V) out[(size_t)j * V * V + u * V + mi] = accS[j][r];
       }
   }

@@ -17,7 +17,6 @@
 namespace {
 
 constexpr int BF_NT = 256, BF_KC = 64, BF_LS = BF_KC + 2, BF_Q = BF_KC / 4, BF_J = 64 * BF_Q / BF_NT;   // 4 slots
-constexpr int BF_OOB = 0x7ffffff0;
 
 struct BfArgs {
   const float* x1; const float* s1; const float* h1;
@@ -27,16 +26,6 @@ struct BfArgs {
   float* dx; float* dx2; float* dwp; float* dbp; float* ipart;  // ipart (splits, Ci, 3) or NULL
   int pstride, n, Ci, Co, L, cpn, total_chunks, cps;
 };
-
-typedef float bf_f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bf_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bf_load(__amdgpu_buffer_rsrc_t r, int voff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ int bf_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 #ifdef DSGCN_LAB
 // wall-clock stamps (10 ns) of workgroup 0, thread 0: start, tables ready, then per unit (committed + barrier, products +
@@ -73,7 +62,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
   float* Xs = lds + 64 * BF_LS;                     // [64][LS] the ACTIVATED virtual input v (zero rows >= Ci)
   float* Os = lds + 128 * BF_LS;                    // [64][LS] dv tile of the unit (before mask / scale)
   float* Ws = lds + 192 * BF_LS;                    // [64 co][65] W[co][ci], zero padded
-  bf_f2* Cs = reinterpret_cast<bf_f2*>(Ws + 64 * 65);      // [64] (A0, B0)
+  f32x2v* Cs = reinterpret_cast<f32x2v*>(Ws + 64 * 65);      // [64] (A0, B0)
   f32x4* Ps = reinterpret_cast<f32x4*>(Cs + 64);           // [64] (s1, h1, s2, h2)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
     Ws[i] = (co < Co && ci < Ci) ? a.w[(size_t)co * Ci + ci] : 0.f;
   }
   if (tid < 64) {
-    Cs[tid] = (HASC && tid < Co) ? bf_f2{a.A0[tid], a.B0[tid]} : bf_f2{0.f, 0.f};
+    Cs[tid] = (HASC && tid < Co) ? f32x2v{a.A0[tid], a.B0[tid]} : f32x2v{0.f, 0.f};
     f32x4 p = {1.f, 0.f, 1.f, 0.f};
     if (AFF && tid < Ci) {
       if (a.s1) { p.x = a.s1[tid]; p.y = a.h1[tid]; }
@@ -108,19 +97,19 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
   auto issue = [&](int ch) {
     const int n = ch / a.cpn, c0 = (ch - n * a.cpn) * BF_KC;
     const bool pv = c0 + col < L;                                // L % 4 == 0: a float4 is entirely in or out
-    const __amdgpu_buffer_rsrc_t rg = bf_rsrc(a.gz + (size_t)n * Co * L, Co * L4);
-    const __amdgpu_buffer_rsrc_t rz = bf_rsrc((HASC ? a.z : a.gz) + (size_t)n * Co * L, HASC ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rx = bf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
-    const __amdgpu_buffer_rsrc_t ry = bf_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, HAS2 ? Ci * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.gz + (size_t)n * Co * L, Co * L4);
+    const __amdgpu_buffer_rsrc_t rz = buf_rsrc((HASC ? a.z : a.gz) + (size_t)n * Co * L, HASC ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, HAS2 ? Ci * L4 : 0);
 #pragma unroll
     for (int j = 0; j < BF_J; ++j) {
       const int row = row0 + 16 * j;
-      const int vd = (pv && row < Co) ? (row * L + c0 + col) * 4 : BF_OOB;
-      const int vx = (pv && row < Ci) ? (row * L + c0 + col) * 4 : BF_OOB;
-      gr[j] = bf_load(rg, vd);
-      if constexpr (HASC) zr[j] = bf_load(rz, vd);
-      xr[j] = bf_load(rx, vx);
-      if constexpr (HAS2) yr[j] = bf_load(ry, vx);
+      const int vd = (pv && row < Co) ? (row * L + c0 + col) * 4 : BUF_OOB;
+      const int vx = (pv && row < Ci) ? (row * L + c0 + col) * 4 : BUF_OOB;
+      gr[j] = buf_load<4>(rg, vd);
+      if constexpr (HASC) zr[j] = buf_load<4>(rz, vd);
+      xr[j] = buf_load<4>(rx, vx);
+      if constexpr (HAS2) yr[j] = buf_load<4>(ry, vx);
     }
   };
   auto commit = [&](int ch) {
@@ -131,15 +120,15 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
       const int row = row0 + 16 * j;
       f32x4 d = gr[j];
       if constexpr (HASC) {
-        const bf_f2 c = Cs[row];
+        const f32x2v c = Cs[row];
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] += fmaf(c.y, zr[j][e], c.x);
       }
       if (!(pv && row < Co)) d = f32x4{0.f, 0.f, 0.f, 0.f};
       dsum[j] += (d.x + d.y) + (d.z + d.w);
-      bf_f2* dd = reinterpret_cast<bf_f2*>(Ds + row * BF_LS + col);
-      dd[0] = bf_f2{d.x, d.y};
-      dd[1] = bf_f2{d.z, d.w};
+      f32x2v* dd = reinterpret_cast<f32x2v*>(Ds + row * BF_LS + col);
+      dd[0] = f32x2v{d.x, d.y};
+      dd[1] = f32x2v{d.z, d.w};
       f32x4 v = xr[j];
       if constexpr (AFF) {
         const f32x4 p = Ps[row];
@@ -153,9 +142,9 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
         }
       }
       if (!(pv && row < Ci)) v = f32x4{0.f, 0.f, 0.f, 0.f};
-      bf_f2* dxs = reinterpret_cast<bf_f2*>(Xs + row * BF_LS + col);
-      dxs[0] = bf_f2{v.x, v.y};
-      dxs[1] = bf_f2{v.z, v.w};
+      f32x2v* dxs = reinterpret_cast<f32x2v*>(Xs + row * BF_LS + col);
+      dxs[0] = f32x2v{v.x, v.y};
+      dxs[1] = f32x2v{v.z, v.w};
     }
   };
 
@@ -180,8 +169,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
   if (ch0 < ch1) issue(ch0);
   for (int ch = ch0; ch < ch1; ++ch) {
     commit(ch);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     BF_STAMP();
     if (ch + 1 < ch1) issue(ch + 1);
     // ---- weight gradient ---- (two accumulators: a single one is a chain of dependent MFMAs, and only two waves
@@ -190,14 +178,14 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
       // operands of steps w+2, w+3 are read from LDS BEFORE the four products of steps w, w+1 are issued (pinned): left to
       // itself hipcc emits read, read, s_waitcnt lgkmcnt(0), four MFMAs — every pair of steps pays an LDS round trip in
       // series with its 256 matrix cycles (round-5 disassembly), and the co-resident workgroup does not always cover it
-      bf_f2 av0 = *reinterpret_cast<const bf_f2*>(Ap), bv0 = *reinterpret_cast<const bf_f2*>(Bp);
-      bf_f2 av1 = *reinterpret_cast<const bf_f2*>(Ap + 4), bv1 = *reinterpret_cast<const bf_f2*>(Bp + 4);
+      f32x2v av0 = *reinterpret_cast<const f32x2v*>(Ap), bv0 = *reinterpret_cast<const f32x2v*>(Bp);
+      f32x2v av1 = *reinterpret_cast<const f32x2v*>(Ap + 4), bv1 = *reinterpret_cast<const f32x2v*>(Bp + 4);
 #pragma unroll
       for (int w = 0; w < BF_Q; w += 2) {
-        bf_f2 an0 = av0, bn0 = bv0, an1 = av1, bn1 = bv1;
+        f32x2v an0 = av0, bn0 = bv0, an1 = av1, bn1 = bv1;
         if (w + 2 < BF_Q) {
-          an0 = *reinterpret_cast<const bf_f2*>(Ap + 4 * (w + 2)); bn0 = *reinterpret_cast<const bf_f2*>(Bp + 4 * (w + 2));
-          an1 = *reinterpret_cast<const bf_f2*>(Ap + 4 * (w + 3)); bn1 = *reinterpret_cast<const bf_f2*>(Bp + 4 * (w + 3));
+          an0 = *reinterpret_cast<const f32x2v*>(Ap + 4 * (w + 2)); bn0 = *reinterpret_cast<const f32x2v*>(Bp + 4 * (w + 2));
+          an1 = *reinterpret_cast<const f32x2v*>(Ap + 4 * (w + 3)); bn1 = *reinterpret_cast<const f32x2v*>(Bp + 4 * (w + 3));
         }
         __builtin_amdgcn_sched_barrier(0);
         accw = __builtin_amdgcn_mfma_f32_32x32x2f32(av0.x, bv0.x, accw, 0, 0, 0);
@@ -238,10 +226,9 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        Os[(32 * cit + bf_row32(r, half)) * BF_LS + 32 * pt + l31] = accd[r] + accd2[r];
+        Os[(32 * cit + mfma_row32(r, half)) * BF_LS + 32 * pt + l31] = accd[r] + accd2[r];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                 // raw barrier: the next unit's loads stay in flight
+    block_lds_sync();                                 // raw barrier: the next unit's loads stay in flight
     BF_STAMP();
     {
       // finish the data gradient in the staging layout (16 B per lane, the raw inputs are still in registers):
@@ -252,8 +239,8 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
         for (int j = 0; j < BF_J; ++j) {
           const int row = row0 + 16 * j;
           if (row < Ci) {
-            const bf_f2* o = reinterpret_cast<const bf_f2*>(Os + row * BF_LS + col);
-            const bf_f2 lo2 = o[0], hi2 = o[1];
+            const f32x2v* o = reinterpret_cast<const f32x2v*>(Os + row * BF_LS + col);
+            const f32x2v lo2 = o[0], hi2 = o[1];
             f32x4 dv = {lo2.x, lo2.y, hi2.x, hi2.y};
             f32x4 p = {1.f, 0.f, 1.f, 0.f};
             if constexpr (AFF) {
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64(BfArgs a, P4GuestArg<bf_host
     const int ci = 32 * nt + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = 32 * mt + bf_row32(r, half);
+      const int co = 32 * mt + mfma_row32(r, half);
       if (wg_on && co < Co && ci < Ci) dw[(size_t)co * Ci + ci] = accw[r] + accw2[r];
     }
   }
@@ -383,17 +370,17 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a, P4GuestArg<bf_hos
   float dsum = 0.f, r0 = 0.f, r1 = 0.f;
   auto issue = [&](int ch, Raw& R) {
     const int n = ch / a.cpn, c0 = (ch - n * a.cpn) * 32;
-    const __amdgpu_buffer_rsrc_t rg = bf_rsrc(a.gz + (size_t)n * Co * L, Co * L4);
-    const __amdgpu_buffer_rsrc_t rz = bf_rsrc((HASC ? a.z : a.gz) + (size_t)n * Co * L, HASC ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t r1_ = bf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.gz + (size_t)n * Co * L, Co * L4);
+    const __amdgpu_buffer_rsrc_t rz = buf_rsrc((HASC ? a.z : a.gz) + (size_t)n * Co * L, HASC ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t r1_ = buf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int p = c0 + 8 * q + 4 * h;                              // (L % 4 == 0: a quad is inside or outside the plane)
-      const int vd = (rd && p < L) ? (row * L + p) * 4 : BF_OOB;
-      const int vx = (rx && p < L) ? (row * L + p) * 4 : BF_OOB;
-      R.g[h] = bf_load(rg, vd);
-      if constexpr (HASC) R.z[h] = bf_load(rz, vd);
-      R.x[h] = bf_load(r1_, vx);
+      const int vd = (rd && p < L) ? (row * L + p) * 4 : BUF_OOB;
+      const int vx = (rx && p < L) ? (row * L + p) * 4 : BUF_OOB;
+      R.g[h] = buf_load<4>(rg, vd);
+      if constexpr (HASC) R.z[h] = buf_load<4>(rz, vd);
+      R.x[h] = buf_load<4>(r1_, vx);
     }
   };
   auto commit = [&](int ch, const Raw& R) {
@@ -500,8 +487,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a, P4GuestArg<bf_hos
   auto unit = [&](int ch, Raw& R) {
     commit(ch, R);
     if (ch + 2 < ch1) issue(ch + 2, R);                            // (the set is free: commit kept what the finish needs)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                 // images complete (raw barrier: loads stay in flight)
+    block_lds_sync();                                 // images complete (raw barrier: loads stay in flight)
     BF_STAMP();
     if (wg0) {
       accw = six(accw, Af, 64 * BB_RB, Bf, 64 * BB_RB);
@@ -519,10 +505,9 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a, P4GuestArg<bf_hos
       for (int ks = 0; ks < 4; ++ks)
         if (ks < KSD) accd = six(accd, Wf + 32 * ks, 64 * BB_RT, Df + 32 * ks, 32 * BB_RT);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Os[(32 * cit + bf_row32(r, half)) * BB_OS + l31] = accd[r];
+      for (int r = 0; r < 16; ++r) Os[(32 * cit + mfma_row32(r, half)) * BB_OS + l31] = accd[r];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                 // dv tile complete; the images are free
+    block_lds_sync();                                 // dv tile complete; the images are free
     BF_STAMP();
     {
       const int n = ch / a.cpn, c0 = (ch - n * a.cpn) * 32;
@@ -560,7 +545,7 @@ __global__ __launch_bounds__(BF_NT, 2) void k_bwd64b(BfArgs a, P4GuestArg<bf_hos
   float* dw = a.dwp + (size_t)split * a.pstride;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int co = 32 * mt + bf_row32(r, half);
+    const int co = 32 * mt + mfma_row32(r, half);
     if (wg0 && co < Co && l31 < Ci) dw[(size_t)co * Ci + l31] = accw[r];
     if (wg1 && co < Co && 32 + l31 < Ci) dw[(size_t)co * Ci + 32 + l31] = accw1[r];
   }

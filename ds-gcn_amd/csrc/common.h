@@ -20,8 +20,11 @@
 // 1 = high (three).  One atomic in version.hip, read by the HOST launch code only — never by a kernel.
 __attribute__((visibility("hidden"))) int dsgcn_precision_level();
 
+typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -41,6 +44,23 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// Sum / maximum over a 256-thread workgroup (four waves), the same bits in every thread.  red: >= 4 floats of LDS.
+__device__ __forceinline__ float block_sum(float v, float* red, int tid) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ __forceinline__ float block_max(float v, float* red, int tid) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((tid & 63) == 0) red[tid >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
 // relu?(x*s+h)
 __device__ __forceinline__ float affine_act(float x, float s, float h, int relu) {
   float v = fmaf(x, s, h);
@@ -53,6 +73,63 @@ __device__ __forceinline__ float affine_act(float x, float s, float h, int relu)
 __device__ __forceinline__ void wave_lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
+}
+
+// The workgroup's form of the same: "all my DS ops are done", then the raw s_barrier.  Again no s_waitcnt vmcnt(0): the
+// global loads a wave has in flight stay in flight across the barrier.
+__device__ __forceinline__ void block_lds_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+}
+
+// MFMA C/D row of accumulator register r for this lane (32x32 tile): (r&3) + 8*(r>>2) + 4*(lane>>5)
+__device__ __forceinline__ int mfma_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// ---- raw buffer loads -----------------------------------------------------------------------------------------------
+// A buffer resource over `bytes` bytes at p, stride 0 (raw: the offsets are bytes).  The last descriptor word (the literal below)
+// selects DATA_FORMAT = 4 (one 32-bit element; bits 15-18 of the word) and leaves every other field zero: no swizzle, no
+// thread-id addressing, and with stride 0 the raw range check (offset >= num_records).  A load past `bytes` returns 0 and
+// a store there is dropped: the kernels use that instead of per-lane predication.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, size_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
+}
+
+// A vector offset that is out of range for every resource (num_records is an int) and stays so, without wrapping, under
+// the 16-byte-aligned row offsets the kernels add to it.
+constexpr int BUF_OOB = 0x7ffffff0;
+
+// N consecutive floats at byte offset voff (per lane: VGPR) + soff (wave-uniform: SGPR operand); N = 1, 2, 4.
+template <int N> struct buf_vec;
+template <> struct buf_vec<1> { typedef float T; };
+template <> struct buf_vec<2> { typedef f32x2v T; };
+template <> struct buf_vec<4> { typedef f32x4 T; };
+
+template <int N>
+__device__ __forceinline__ typename buf_vec<N>::T buf_load(__amdgpu_buffer_rsrc_t r, int voff, int soff = 0) {
+  if constexpr (N == 4) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+  else if constexpr (N == 2) return __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+  else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+
+// Vector offset of a per-row access: base + rowoff (rowoff = row * plane bytes), or an out-of-range offset for an invalid
+// row / position (unsigned sum: no wrap below 2^32).  The row depends on the lane's half, so it must NOT go into the scalar
+// offset: hipcc then wraps every access in a readfirstlane loop that runs once per distinct value (two passes with half the
+// lanes each; 35-195 such loops per kernel in the disassembly of the first version).
+__device__ __forceinline__ int buf_rowoff(bool ok, int base, int rowoff) {
+  return (int)((unsigned)(ok ? base : BUF_OOB) + (unsigned)rowoff);
+}
+
+// Sum of half of row l31 of a wave's [32][36] LDS tile (lane (half, l31); the caller adds the two halves).
+template <typename ACC>
+__device__ __forceinline__ ACC tile36_rowsum(const float* Tw, int half, int l31) {
+  const f32x4* rowp = reinterpret_cast<const f32x4*>(Tw + l31 * 36 + half * 16);
+  ACC s = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = rowp[q];
+    s += ((ACC)v.x + (ACC)v.y) + ((ACC)v.z + (ACC)v.w);
+  }
+  return s;
 }
 
 // t = e / V, v = e % V for 0 <= e < 2^22 with invV = 1.f / V (float reciprocal + one fix-up step: exact)
@@ -98,9 +175,6 @@ __device__ __forceinline__ void plane_to_lds(const float* __restrict__ src, floa
 // instantiations (term count 2) of the bodies of the three-term ones.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned b3_pack(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{a, b}, bf16x2));   // v_cvt_pk_bf16_f32: lo = a, hi = b

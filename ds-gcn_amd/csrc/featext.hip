@@ -20,8 +20,6 @@ constexpr int FX_PT = 32;         // positions per block = one MFMA tile edge
 constexpr int FX_J = 8;           // positions a wave has in flight per pass of the dot-product form
 constexpr int FX_CU = 4;          // channels a thread pools at a time
 
-__device__ __forceinline__ int fx_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 struct FxShape {
   int clips, M, C, T, V, K;
   int nq, nm, nt, nv;             // pooled extents (1 where the axis is kept)
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(FX_NT) void k_feat_ext(const float* __restrict__ x,
         const int p = p0 + mi, pr = p / s.Sp, ps = p - pr * s.Sp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int k = k0 + fx_row(r, mk);
+          const int k = k0 + mfma_row32(r, mk);
           if (k < K) {
             const float v = ((acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r])) + (b ? b[k] : 0.f);
             fx_store(out32, out16, ((orow + pr) * K + k) * s.Sp + ps, v);

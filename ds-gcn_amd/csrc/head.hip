@@ -15,22 +15,6 @@ namespace {
 
 constexpr int HD_NT = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* red, int tid) {      // red: >= 4 floats; all threads get the sum
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ float block_max(float v, float* red, int tid) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // One workgroup per clip n.  LDS: pl[C] pooled features, sc[K] scores.
 //   pooled[n, c] = (1/M) sum_m feat[n*M + m, c];  score[n, k] = <pooled[n], W[k]> + b[k]  (a wave per class: lanes split C)
 //   prob = softmax(score);  clip[n] = (-log prob[label], rank < 1, rank < 5) with rank = classes that a stable ascending

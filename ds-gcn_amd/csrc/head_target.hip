@@ -17,22 +17,6 @@ namespace {
 
 constexpr int HT_NT = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* red, int tid) {      // red: >= 4 floats; all threads get the sum
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ float block_max(float v, float* red, int tid) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // One workgroup per clip n.  LDS: pl[C] pooled features, sc[K] scores (the front half is k_head_fwd's, op for op: the
 // scores of the two kernels are the same bits).  clip[n] = (L_n, D_n, top-1 hit, top-5 hit); ds[n, k] = dscore / g.
 template <int MODE>

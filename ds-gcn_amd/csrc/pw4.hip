@@ -65,7 +65,7 @@ constexpr int PG_KC = 32, PG_RB = PG_KC * 2 + 16, PG_T = 128, PG_TAM = 144;
 
 template <int MODE, int EPI>
 __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
-  typedef VQ<4>::T vq;
+  typedef f32x4 vq;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   char* Ab = reinterpret_cast<char*>(lds);                               // [3][128 rows][RB]
   // W^T arrives four consecutive ROWS per loader thread: written in row order the 8-byte stores of a wave would sit 320 B
@@ -95,11 +95,11 @@ __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
   if (L - pos < 4) { skip = 4 - (L - pos); pos = L - 4; }
   const int L4 = L * 4;
   const int nrem = a.n - n < a.span ? a.n - n : a.span;
-  const __amdgpu_buffer_rsrc_t r1 = p4_rsrc(a.b1 + (size_t)n * K * L, nrem * K * L4);
-  const __amdgpu_buffer_rsrc_t r2 = p4_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, MODE == 2 ? nrem * K * L4 : 0);
+  const __amdgpu_buffer_rsrc_t r1 = buf_rsrc(a.b1 + (size_t)n * K * L, nrem * K * L4);
+  const __amdgpu_buffer_rsrc_t r2 = buf_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, MODE == 2 ? nrem * K * L4 : 0);
   // loader roles.  B: channels 4*cg .. 4*cg+3 of the chunk (cg = tid / 32) at the lane's own position quad.
   const int cg = tid >> 5;
-  const int voffB = pok ? ds * K * L4 + pos * 4 : P4_OOB;
+  const int voffB = pok ? ds * K * L4 + pos * 4 : BUF_OOB;
   // A, k contiguous in memory (forward): rows (tid / 8) + 32*i, k = 4*(tid % 8) ..+3;  m contiguous (data gradient: W^T):
   // k = 4*(tid / 32) + e, rows 4*(tid % 32) ..+3
   constexpr bool mfast = EPI == 1;                 // data gradient: A = W^T, m contiguous in memory
@@ -109,13 +109,13 @@ __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int c = ch0 + 4 * cg + e;                 // per half-wave: the channel goes into the vector offset
-      const int vo = c < K ? voffB + c * L4 : P4_OOB;
-      bw[e] = p4_load<4>(r1, vo, 0);
-      if constexpr (MODE == 2) bw2[e] = p4_load<4>(r2, vo, 0);
+      const int vo = c < K ? voffB + c * L4 : BUF_OOB;
+      bw[e] = buf_load<4>(r1, vo);
+      if constexpr (MODE == 2) bw2[e] = buf_load<4>(r2, vo);
     }
   };
   // weights through a buffer resource too: rows / channels past the matrix are out-of-range offsets (zeros), no branches
-  const __amdgpu_buffer_rsrc_t rw = p4_rsrc(a.w, M * K * 4);
+  const __amdgpu_buffer_rsrc_t rw = buf_rsrc(a.w, M * K * 4);
   const int offA0 = mfast ? (4 * cg * a.w_ldk + mBase0 + 4 * l31) * 4 : ((mBase0 + (tid >> 3)) * a.w_ldm + 4 * (tid & 7)) * 4;
   const int stepE = mfast ? a.w_ldk * 4 : 32 * a.w_ldm * 4;             // between this thread's four loads
   const int stepC = mfast ? a.w_ldk * 4 : 4;                            // per channel of chunk advance
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const bool ok = (kA + ch0 + (mfast ? e : 0) < K) & (mA + (mfast ? 0 : 32 * e) < M);
-      aw[e] = p4_load<4>(rw, ok ? offA0 + e * stepE + ch0 * stepC : P4_OOB, 0);
+      aw[e] = buf_load<4>(rw, ok ? offA0 + e * stepE + ch0 * stepC : BUF_OOB);
     }
   };
   const float lo = a.relu ? 0.f : -__builtin_inff();
@@ -186,19 +186,17 @@ __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
   f32x16 acc[1][4];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = mBase + p4_row32(i, half);
+    const int row = mBase + mfma_row32(i, half);
     const float b0 = (EPI == 0 && a.bias && row < M) ? a.bias[row] : 0.f;
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[0][q][i] = b0;
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                    // Ps visible (raw barrier: the operand loads stay in flight)
+  block_lds_sync();                    // Ps visible (raw barrier: the operand loads stay in flight)
   const char* Af = Ab + (mfast ? 36 * (l31 & 3) + 8 * wave + (l31 >> 2) : 32 * wave + l31) * PG_RB + 16 * half;
   const char* Bf = Bb + l31 * PG_RB + 16 * half;
   auto chunk = [&](int ch0, vq (&bw)[4], vq (&bw2)[MODE == 2 ? 4 : 1]) {
     commit(ch0, bw, bw2);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     __builtin_amdgcn_sched_barrier(0);
     issueA(ch0 + PG_KC);                           // (past K: zeros)
     issueB(ch0 + 2 * PG_KC, bw, bw2);              // this set is free again: two chunks ahead
@@ -225,8 +223,7 @@ __global__ __launch_bounds__(P4_NT, 2) void k_pwg(Pw4Args a) {
         acc[0][q] = c;
       }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                  // raw barrier: the loads in flight stay in flight
+    block_lds_sync();                  // raw barrier: the loads in flight stay in flight
   };
   // (pairs in the loop, an odd last chunk outside it: with the second call conditional inside the loop the compiler
   // must allow for a first-call -> first-call path, on which the set just refilled is the next one consumed: vmcnt(0))
@@ -287,7 +284,7 @@ constexpr int G3_BBUF = 3 * PG_T * PG_RB;          // one activation buffer: [3 
 // plane / rows are simply not touched): two split steps, two LDS rows and two A fragments per value instead of three.
 template <int MODE, int EPI, int MT, int NT>
 __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short* __restrict__ wfr, int RT, int bid, float* lds) {
-  typedef VQ<4>::T vq;
+  typedef f32x4 vq;
 #ifdef DSGCN_LAB
   int nst = 0;
 #endif
@@ -315,24 +312,24 @@ __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short
   if (L - pos < 4) { skip = 4 - (L - pos); pos = L - 4; }
   const int L4 = L * 4;
   const int nrem = a.n - n < a.span ? a.n - n : a.span;
-  const __amdgpu_buffer_rsrc_t r1 = p4_rsrc(a.b1 + (size_t)n * K * L, nrem * K * L4);
-  const __amdgpu_buffer_rsrc_t r2 = p4_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, MODE == 2 ? nrem * K * L4 : 0);
+  const __amdgpu_buffer_rsrc_t r1 = buf_rsrc(a.b1 + (size_t)n * K * L, nrem * K * L4);
+  const __amdgpu_buffer_rsrc_t r2 = buf_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, MODE == 2 ? nrem * K * L4 : 0);
   // B loader: channels 4*cg .. 4*cg+3 of the chunk (cg = tid / 32) at the lane's own position quad
   const int cg = tid >> 5;
-  const int voffB = pok ? ds * K * L4 + pos * 4 : P4_OOB;
+  const int voffB = pok ? ds * K * L4 + pos * 4 : BUF_OOB;
   vq bw[4], bw2[MODE == 2 ? 4 : 1];
   auto issueB = [&](int ch0) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int c = ch0 + 4 * cg + e;
-      const int vo = c < K ? voffB + c * L4 : P4_OOB;
-      bw[e] = p4_load<4>(r1, vo, 0);
-      if constexpr (MODE == 2) bw2[e] = p4_load<4>(r2, vo, 0);
+      const int vo = c < K ? voffB + c * L4 : BUF_OOB;
+      bw[e] = buf_load<4>(r1, vo);
+      if constexpr (MODE == 2) bw2[e] = buf_load<4>(r2, vo);
     }
   };
   // A fragments: (term t, row tile m of this wave, k-step ks) = 1 KB at ((t*RT + rt)*KS + ks) KB of the image
   const int KS = Kpad >> 4;
-  const __amdgpu_buffer_rsrc_t rw = p4_rsrc(wfr, 3 * RT * KS * 1024);
+  const __amdgpu_buffer_rsrc_t rw = buf_rsrc(wfr, 3 * RT * KS * 1024);
   // (the fragment's KB index is wave-uniform: it rides in the scalar offset, one vector register addresses all of them)
   const int fragA0 = __builtin_amdgcn_readfirstlane(mBase >> 5);
   u32x4v af0[MT][NT], af1[MT][NT];                 // k-steps of even / odd index
@@ -341,7 +338,7 @@ __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short
     for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int t = 0; t < NT; ++t)
-        af[m][t] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(rw, lane * 16, ((t * RT + fragA0 + m) * KS + ks) * 1024, 0));
+        af[m][t] = __builtin_bit_cast(u32x4v, buf_load<4>(rw, lane * 16, ((t * RT + fragA0 + m) * KS + ks) * 1024));
   };
   const float lo = a.relu ? 0.f : -__builtin_inff();
   // the chunk in registers -> the operand values, in place (deferred-BatchNorm affine, second stream, ReLU): done as soon
@@ -381,20 +378,20 @@ __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int c = PG_KC + 4 * cg + e;
-    const int vo = c < K ? voffB + c * L4 : P4_OOB;
-    bwN[e] = p4_load<4>(r1, vo, 0);
-    if constexpr (MODE == 2) bw2N[e] = p4_load<4>(r2, vo, 0);
+    const int vo = c < K ? voffB + c * L4 : BUF_OOB;
+    bwN[e] = buf_load<4>(r1, vo);
+    if constexpr (MODE == 2) bw2N[e] = buf_load<4>(r2, vo);
   }
   __builtin_amdgcn_sched_barrier(0);
   f32x16 acc[MT][4];
-  const __amdgpu_buffer_rsrc_t rbias = p4_rsrc(a.bias, (EPI == 0 && a.bias) ? M * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rbias = buf_rsrc(a.bias, (EPI == 0 && a.bias) ? M * 4 : 0);
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = mBase + 32 * m + p4_row32(i, half);
+      const int row = mBase + 32 * m + mfma_row32(i, half);
       float b0 = 0.f;                              // (rows past M / no bias: the bounds check returns zero, no branches)
-      if constexpr (EPI == 0) b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rbias, row * 4, 0, 0));
+      if constexpr (EPI == 0) b0 = buf_load<1>(rbias, row * 4);
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[m][q][i] = b0;
     }
@@ -413,8 +410,7 @@ __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short
   __builtin_amdgcn_sched_barrier(0);
   issueA(0, af0);
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                    // Ps visible (raw barrier: the operand loads stay in flight)
+  block_lds_sync();                    // Ps visible (raw barrier: the operand loads stay in flight)
   PWG_STAMP();
   combine(0);
 #pragma unroll
@@ -424,8 +420,7 @@ __device__ __forceinline__ void pwg3_body(const Pw4Args& a, const unsigned short
     bw[e] = bwN[e];
     if constexpr (MODE == 2) bw2[e] = bw2N[e];
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  block_lds_sync();
   PWG_STAMP();
 
   const int fragoff = l31 * PG_RB + 16 * half;

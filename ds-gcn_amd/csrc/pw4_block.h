@@ -40,58 +40,15 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_guest_plan(const dsgcn_guest_
 namespace {
 
 constexpr int P4_NT = 256;
-constexpr int P4_OOB = 0x7ffffff0;
 constexpr int P4_NT_STORE = 2;                   // cache-policy bits of the output stores: non-temporal (written once, read by a later launch)
 
-template <int NQ> struct VQ;
-template <> struct VQ<4> { typedef float T __attribute__((ext_vector_type(4))); };
-template <> struct VQ<2> { typedef float T __attribute__((ext_vector_type(2))); };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t p4_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
-}
-
 template <int NQ>
-__device__ __forceinline__ typename VQ<NQ>::T p4_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
+__device__ __forceinline__ void p4_store(typename buf_vec<NQ>::T v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
   if constexpr (NQ == 4) {
-    return __builtin_bit_cast(typename VQ<4>::T, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), r, voff, soff, P4_NT_STORE);
   } else {
-    return __builtin_bit_cast(typename VQ<2>::T, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, v), r, voff, soff, P4_NT_STORE);
   }
-}
-
-__device__ __forceinline__ int p4_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// Vector offset of row `row` (rowoff = row * plane bytes) for the epilogue's per-row accesses.  The row depends on the
-// lane's half, so it must NOT go into the scalar offset: hipcc then wraps every access in a readfirstlane loop that runs
-// once per distinct value (two passes with half the lanes each — found in the round-4 disassembly: 35-195 such loops per
-// kernel).  An invalid row / position keeps an out-of-range offset (unsigned sum: no wrap below 2^32).
-__device__ __forceinline__ int p4_rowoff(bool ok, int ooff, int rowoff) {
-  return (int)((unsigned)(ok ? ooff : P4_OOB) + (unsigned)rowoff);
-}
-
-template <int NQ>
-__device__ __forceinline__ void p4_store(typename VQ<NQ>::T v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  if constexpr (NQ == 4) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, P4_NT_STORE);
-  } else {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, voff, soff, P4_NT_STORE);
-  }
-}
-
-// Sum of half of row l31 of a wave's [32][36] LDS tile (lane (half, l31); the caller adds the two halves).
-template <typename ACC>
-__device__ __forceinline__ ACC p4_rowread(const float* Tw, int half, int l31) {
-  const f32x4* rowp = reinterpret_cast<const f32x4*>(Tw + l31 * 36 + half * 16);
-  ACC s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x4 v = rowp[q];
-    s += ((ACC)v.x + (ACC)v.y) + ((ACC)v.z + (ACC)v.w);
-  }
-  return s;
 }
 
 // MODE 0: B' = b1;  1: relu?(b1*s1+h1);  2: relu?(b1*s1+h1 + b2*s2+h2).   EPI 0: forward (bias, statistics);  1: data gradient.
@@ -107,7 +64,7 @@ struct P4Tile { int wave, half, l31, tid, mBase, n, nrem, ds, pos, grp; bool wli
 // lab stamps, profiles/r03 / r04).  EPD = 0: the original form (the compiler's own schedule).
 template <int MT, int NQ, int EPI, bool OWNROWS, int NWV = 4, int EPD = 0, bool X2 = true>
 __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][NQ], float* lds, const P4Tile& t) {
-  typedef typename VQ<NQ>::T vq;
+  typedef typename buf_vec<NQ>::T vq;
   const int wave = t.wave, half = t.half, l31 = t.l31, tid = t.tid, mBase = t.mBase, n = t.n, nrem = t.nrem, ds = t.ds,
             pos = t.pos, grp = t.grp;
   const bool wlive = t.wlive, pok = t.pok;
@@ -119,8 +76,8 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
   // and are dropped by the bounds check: no branches); per-channel sums through LDS transposes of the wave's tiles.
   constexpr int NTL = EPI == 0 ? 2 : 3;            // transposed tiles per wave
   float* Tw = lds + wave * (NTL * 32 * 36);
-  const __amdgpu_buffer_rsrc_t ro = p4_rsrc(a.out + (size_t)n * M * L, wlive ? nrem * M * L4 : 0);
-  const int ooff = pok ? ds * M * L4 + pos * 4 : P4_OOB;
+  const __amdgpu_buffer_rsrc_t ro = buf_rsrc(a.out + (size_t)n * M * L, wlive ? nrem * M * L4 : 0);
+  const int ooff = pok ? ds * M * L4 + pos * 4 : BUF_OOB;
   if (EPI == 0) {
     double* Ss = reinterpret_cast<double*>(lds + NWV * NTL * 32 * 36);  // [waves][MT*32][2]
     const bool stats = a.partial != nullptr;
@@ -128,7 +85,7 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
     for (int m = 0; m < MT; ++m) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = p4_row32(r, half);
+        const int row = mfma_row32(r, half);
         const int co = mBase + 32 * m + row;
         vq val;
         float s = 0.f, qq = 0.f;
@@ -140,7 +97,7 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
             qq = fmaf(val[q], val[q], qq);
           }
         }
-        p4_store<NQ>(val, ro, p4_rowoff(co < M, ooff, co * L4), 0);
+        p4_store<NQ>(val, ro, buf_rowoff(co < M, ooff, co * L4), 0);
         if (stats) {
           const bool ok = co < M && pok;
           Tw[row * 36 + l31] = ok ? s : 0.f;
@@ -149,8 +106,8 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
       }
       if (stats) {
         wave_lds_sync();
-        double sd = p4_rowread<double>(Tw, half, l31);
-        double qd = p4_rowread<double>(Tw + 32 * 36, half, l31);
+        double sd = tile36_rowsum<double>(Tw, half, l31);
+        double qd = tile36_rowsum<double>(Tw + 32 * 36, half, l31);
         wave_lds_sync();
         sd += __shfl_xor(sd, 32, 64);
         qd += __shfl_xor(qd, 32, 64);
@@ -199,9 +156,9 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
       Es[et] = p;
     }
     __syncthreads();
-    const __amdgpu_buffer_rsrc_t rx1 = p4_rsrc(a.ex1 + (size_t)n * M * L, (wlive && need_x) ? nrem * M * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rx2 = p4_rsrc((has2 ? a.ex2 : a.ex1) + (size_t)n * M * L, (wlive && has2) ? nrem * M * L4 : 0);
-    const __amdgpu_buffer_rsrc_t ro2 = p4_rsrc((a.out2 ? a.out2 : a.out) + (size_t)n * M * L, (wlive && a.out2) ? nrem * M * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rx1 = buf_rsrc(a.ex1 + (size_t)n * M * L, (wlive && need_x) ? nrem * M * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rx2 = buf_rsrc((has2 ? a.ex2 : a.ex1) + (size_t)n * M * L, (wlive && has2) ? nrem * M * L4 : 0);
+    const __amdgpu_buffer_rsrc_t ro2 = buf_rsrc((a.out2 ? a.out2 : a.out) + (size_t)n * M * L, (wlive && a.out2) ? nrem * M * L4 : 0);
     constexpr int G = MT * 4;                       // row groups of the wave's tile
     constexpr int PD = EPD > 0 ? (EPD < G ? EPD : G) : 1;
     vq xa[PD][4], xb[(X2 || EPD == 0) ? PD : 1][4];
@@ -209,9 +166,9 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
       const int m = g >> 2, rb = (g & 3) * 4;
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        const int ci = mBase + 32 * m + p4_row32(rb + rr, half);
-        xa[slot][rr] = p4_load<NQ>(rx1, p4_rowoff(ci < M, ooff, ci * L4), 0);      // zeros when the input is not needed
-        if constexpr (X2 || EPD == 0) xb[slot][rr] = p4_load<NQ>(rx2, p4_rowoff(ci < M, ooff, ci * L4), 0);
+        const int ci = mBase + 32 * m + mfma_row32(rb + rr, half);
+        xa[slot][rr] = buf_load<NQ>(rx1, buf_rowoff(ci < M, ooff, ci * L4), 0);      // zeros when the input is not needed
+        if constexpr (X2 || EPD == 0) xb[slot][rr] = buf_load<NQ>(rx2, buf_rowoff(ci < M, ooff, ci * L4), 0);
       }
     };
     if constexpr (EPD > 0) {
@@ -227,7 +184,7 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int r = rb + rr;
-        const int row = p4_row32(r, half);
+        const int row = mfma_row32(r, half);
         const int ci = mBase + 32 * m + row;
         const f32x4 e = Es[32 * m + row];
         float u0 = 0.f, u1 = 0.f, u2 = 0.f;
@@ -249,8 +206,8 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
             u2 = fmaf(dv, xbq, u2);
           }
         }
-        p4_store<NQ>(d1, ro, p4_rowoff(ci < M, ooff, ci * L4), 0);
-        if constexpr (X2 || EPD == 0) p4_store<NQ>(d2, ro2, p4_rowoff(ci < M, ooff, ci * L4), 0);   // zero-sized resource when there is no dx2
+        p4_store<NQ>(d1, ro, buf_rowoff(ci < M, ooff, ci * L4), 0);
+        if constexpr (X2 || EPD == 0) p4_store<NQ>(d2, ro2, buf_rowoff(ci < M, ooff, ci * L4), 0);   // zero-sized resource when there is no dx2
         if (sums) {
           const bool ok = ci < M && pok;
           Tw[row * 36 + l31] = ok ? u0 : 0.f;
@@ -265,9 +222,9 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
       }
       if ((g & 3) == 3 && sums) {
         wave_lds_sync();
-        float s0 = p4_rowread<float>(Tw, half, l31);
-        float s1 = p4_rowread<float>(Tw + 32 * 36, half, l31);
-        float s2 = p4_rowread<float>(Tw + 2 * 32 * 36, half, l31);
+        float s0 = tile36_rowsum<float>(Tw, half, l31);
+        float s1 = tile36_rowsum<float>(Tw + 32 * 36, half, l31);
+        float s2 = tile36_rowsum<float>(Tw + 2 * 32 * 36, half, l31);
         wave_lds_sync();
         s0 += __shfl_xor(s0, 32, 64);
         s1 += __shfl_xor(s1, 32, 64);
@@ -315,7 +272,7 @@ __device__ __forceinline__ void p4_epilogue(const Pw4Args& a, f32x16 (&acc)[MT][
 // accumulator start, same epilogue: a guest gives the bits of its stand-alone launch.
 template <int MT, int NQ, int MODE, int PD, int EPI, bool KSP = false>
 __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float* lds) {
-  typedef typename VQ<NQ>::T vq;
+  typedef typename buf_vec<NQ>::T vq;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
@@ -356,9 +313,9 @@ __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float*
   if (L - pos < NQ) { skip = NQ - (L - pos); pos = L - NQ; }
   const int L4 = L * 4;
   const int nrem = a.n - n < a.span ? a.n - n : a.span;     // samples the wave can touch
-  const int voff = pok ? ds * K * L4 + (half * L + pos) * 4 : P4_OOB;
-  const __amdgpu_buffer_rsrc_t r1 = p4_rsrc(a.b1 + (size_t)n * K * L, wlive ? nrem * K * L4 : 0);
-  const __amdgpu_buffer_rsrc_t r2 = p4_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, (wlive && MODE == 2) ? nrem * K * L4 : 0);
+  const int voff = pok ? ds * K * L4 + (half * L + pos) * 4 : BUF_OOB;
+  const __amdgpu_buffer_rsrc_t r1 = buf_rsrc(a.b1 + (size_t)n * K * L, wlive ? nrem * K * L4 : 0);
+  const __amdgpu_buffer_rsrc_t r2 = buf_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)n * K * L, (wlive && MODE == 2) ? nrem * K * L4 : 0);
 
   f32x16 acc[MT][NQ];
   const float lo = a.relu ? 0.f : -__builtin_inff();
@@ -393,9 +350,9 @@ __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float*
     if (e0 == 0) {
 #pragma unroll
       for (int u = 0; u < PD; ++u) {
-        const int s0 = ks0 + u < kse ? 2 * (ks0 + u) * L4 : P4_OOB;   // (channels past K: out of range, zeros)
-        buf1[u] = p4_load<NQ>(r1, voff, s0);
-        if constexpr (MODE == 2) buf2[u] = p4_load<NQ>(r2, voff, s0);
+        const int s0 = ks0 + u < kse ? 2 * (ks0 + u) * L4 : BUF_OOB;   // (channels past K: out of range, zeros)
+        buf1[u] = buf_load<NQ>(r1, voff, s0);
+        if constexpr (MODE == 2) buf2[u] = buf_load<NQ>(r2, voff, s0);
       }
     }
 #pragma unroll
@@ -413,7 +370,7 @@ __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float*
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = mBase + 32 * m + p4_row32(i, half);
+      const int row = mBase + 32 * m + mfma_row32(i, half);
       const float b0 = (EPI == 0 && a.bias && row < M && (!KSP || wave == 0)) ? a.bias[row] : 0.f;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) acc[m][q][i] = b0;
@@ -431,8 +388,7 @@ __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float*
       Ps[i] = p;
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                    // raw barrier: the operand prefetch stays in flight
+  block_lds_sync();                    // raw barrier: the operand prefetch stays in flight
 
   // Software pipeline, pinned with scheduling barriers.  Step ks: start the LDS reads of step ks+1 (A fragment, affine
   // row; double-buffered by step parity), apply the affine to the operand loaded PD steps ago, run the MT*NQ MFMAs, then
@@ -471,9 +427,9 @@ __device__ __forceinline__ void p4_block(const Pw4Args& a, const int bid, float*
         for (int q = 0; q < NQ; ++q) acc[m][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(avb[cur][m], b[q], acc[m][q], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       // past K: the scalar offset jumps out of the buffer's range (zeros, no traffic: the bounds check covers it)
-      const int sn = ks + PD < kse ? 2 * (ks + PD) * L4 : P4_OOB;
-      buf1[u] = p4_load<NQ>(r1, voff, sn);
-      if constexpr (MODE == 2) buf2[u] = p4_load<NQ>(r2, voff, sn);
+      const int sn = ks + PD < kse ? 2 * (ks + PD) * L4 : BUF_OOB;
+      buf1[u] = buf_load<NQ>(r1, voff, sn);
+      if constexpr (MODE == 2) buf2[u] = buf_load<NQ>(r2, voff, sn);
       __builtin_amdgcn_sched_barrier(0);
     }
   }

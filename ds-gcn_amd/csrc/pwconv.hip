@@ -35,8 +35,6 @@ struct PwArgs {
   int n, Ci, Co, T, V, Tout, stride, aug, TR, NPpad, vec, stats, roll, nbx, cc;
 };
 
-__device__ __forceinline__ int mfma_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 __device__ __forceinline__ float virt1(float a, float b, bool has2, float s1, float h1, float s2, float h2,
                                        int relu) {
   float v = fmaf(a, s1, h1);
@@ -54,15 +52,6 @@ __device__ __forceinline__ float virt1(float a, float b, bool has2, float s1, fl
 constexpr int KW = 64;             // K (input-channel) chunk of the LDS weight tile
 constexpr int KWS = KW + 1;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, size_t bytes) {
-  // raw buffer, stride 0: reads past num_records return 0 (used instead of per-lane predication)
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-constexpr int OOB_OFF = 0x7ffffff0;
-
 // MODE 0: v = x1 ; 1: v = relu?(x1*s1+h1) ; 2: v = relu?(x1*s1+h1 + x2*s2+h2)
 // K is walked in groups of UNR k-steps (2 channels each) with two register sets in ping-pong: the loads of group
 // g+1 are issued before the MFMAs of group g.  No per-step branches (they made hipcc sink every load next to its
@@ -79,8 +68,8 @@ __device__ __forceinline__ void f2_load(float (&xb)[UNR][NW], float (&yb)[UNR][N
     const int soff = (cbase + 2 * u) * cstride4;              // wave-uniform: SGPR operand of the buffer load
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
-      xb[u][j] = buf_load(r1, voff[j], soff);
-      if (MODE == 2) yb[u][j] = buf_load(r2, voff[j], soff);
+      xb[u][j] = buf_load<1>(r1, voff[j], soff);
+      if (MODE == 2) yb[u][j] = buf_load<1>(r2, voff[j], soff);
     }
   }
 }
@@ -174,13 +163,12 @@ __device__ __forceinline__ void fwd2_roll(const PwArgs& a, f32x16 (&acc)[MT][1],
   };
 #pragma unroll
   for (int u = 0; u < 32; ++u) {
-    xr[u] = buf_load(r1, voff, (2 * u) * cstride4);
-    if (MODE == 2) yr[u] = buf_load(r2, voff, (2 * u) * cstride4);
+    xr[u] = buf_load<1>(r1, voff, (2 * u) * cstride4);
+    if (MODE == 2) yr[u] = buf_load<1>(r2, voff, (2 * u) * cstride4);
   }
   loadW(0);
   for (int c = 0; c < nch; ++c) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                 // the previous chunk's weight tile is consumed (first: Ps4 written)
+    block_lds_sync();                 // the previous chunk's weight tile is consumed (first: Ps4 written)
 #pragma unroll
     for (int q = 0; q < 2 * MT; ++q) {
       const int f = tid + PW_NT * q;
@@ -188,8 +176,7 @@ __device__ __forceinline__ void fwd2_roll(const PwArgs& a, f32x16 (&acc)[MT][1],
 #pragma unroll
       for (int e = 0; e < 4; ++e) Ws[rowi * KWS + kq + e] = wr[q][e];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     const bool more = c + 1 < nch;
     const int cn = (c + 1) * KW;
     if (more) loadW(cn);
@@ -207,8 +194,8 @@ __device__ __forceinline__ void fwd2_roll(const PwArgs& a, f32x16 (&acc)[MT][1],
         if (a.relu) v = fmaxf(v, 0.f);
       }
       if (more) {
-        xr[u] = buf_load(r1, voff, (cn + 2 * u) * cstride4);
-        if (MODE == 2) yr[u] = buf_load(r2, voff, (cn + 2 * u) * cstride4);
+        xr[u] = buf_load<1>(r1, voff, (cn + 2 * u) * cstride4);
+        if (MODE == 2) yr[u] = buf_load<1>(r2, voff, (cn + 2 * u) * cstride4);
       }
 #pragma unroll
       for (int m = 0; m < MT; ++m) acc[m][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m], v, acc[m][0], 0, 0, 0);
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(PW_NT) void k_pwconv_fwd2(PwArgs a) {
     const int pc = pok[j] ? pos : 0;
     const int row = pc / V;
     const int goff = (row * a.stride) * V + (pc - row * V);
-    voff[j] = pok[j] ? (int)(((size_t)n * Ci + half) * cstride + goff) * 4 : OOB_OFF;
+    voff[j] = pok[j] ? (int)(((size_t)n * Ci + half) * cstride + goff) * 4 : BUF_OOB;
   }
   for (int i = tid; i < Ci; i += PW_NT) {
     f32x4 p;
@@ -260,8 +247,8 @@ __global__ __launch_bounds__(PW_NT) void k_pwconv_fwd2(PwArgs a) {
     Ps4[i] = p;
   }
   const size_t xbytes = (size_t)a.n * Ci * cstride * 4;
-  const __amdgpu_buffer_rsrc_t r1 = make_rsrc(a.x1, xbytes);
-  const __amdgpu_buffer_rsrc_t r2 = make_rsrc(has2 ? a.x2 : a.x1, xbytes);
+  const __amdgpu_buffer_rsrc_t r1 = buf_rsrc(a.x1, xbytes);
+  const __amdgpu_buffer_rsrc_t r2 = buf_rsrc(has2 ? a.x2 : a.x1, xbytes);
 
   f32x16 acc[MT][NW];
 #pragma unroll
@@ -694,11 +681,11 @@ __device__ __forceinline__ void d2_load(float (&g)[F2_UNR][NW], float (&zz)[F2_U
     const int soffa = (cbase + 2 * u) * astride4;
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
-      g[u][j] = has_g ? buf_load(rg, voff[j], soff) : 0.f;
-      zz[u][j] = has_c ? buf_load(rz, voff[j], soff) : 0.f;
+      g[u][j] = has_g ? buf_load<1>(rg, voff[j], soff) : 0.f;
+      zz[u][j] = has_c ? buf_load<1>(rz, voff[j], soff) : 0.f;
       if (AUG) {
-        ga[u][j] = buf_load(rga, voffa[j], soffa);
-        za[u][j] = has_c ? buf_load(rza, voffa[j], soffa) : 0.f;
+        ga[u][j] = buf_load<1>(rga, voffa[j], soffa);
+        za[u][j] = has_c ? buf_load<1>(rza, voffa[j], soffa) : 0.f;
       }
     }
   }
@@ -753,13 +740,12 @@ __device__ __forceinline__ void dgrad2_roll(const PwBwdArgs& a, f32x16 (&acc)[MT
   };
 #pragma unroll
   for (int u = 0; u < 32; ++u) {
-    gr[u] = has_g ? buf_load(rg, voff, (2 * u) * cstride4) : 0.f;
-    zr[u] = has_c ? buf_load(rz, voff, (2 * u) * cstride4) : 0.f;
+    gr[u] = has_g ? buf_load<1>(rg, voff, (2 * u) * cstride4) : 0.f;
+    zr[u] = has_c ? buf_load<1>(rz, voff, (2 * u) * cstride4) : 0.f;
   }
   loadW(0);
   for (int c = 0; c < nch; ++c) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
 #pragma unroll
     for (int q = 0; q < 2 * MT; ++q) {
       const int f = tid + PW_NT * q;
@@ -767,8 +753,7 @@ __device__ __forceinline__ void dgrad2_roll(const PwBwdArgs& a, f32x16 (&acc)[MT
 #pragma unroll
       for (int e = 0; e < 4; ++e) Ws[rowi * WS2 + cq + e] = wr[q][e];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     const bool more = c + 1 < nch;
     const int cn = (c + 1) * KW;
     if (more) loadW(cn);
@@ -781,8 +766,8 @@ __device__ __forceinline__ void dgrad2_roll(const PwBwdArgs& a, f32x16 (&acc)[MT
       const float2 cf = Cs[c * KW + kl];                      // (A0, B0)
       const float d = gr[u] + fmaf(cf.y, zr[u], cf.x);
       if (more) {
-        gr[u] = has_g ? buf_load(rg, voff, (cn + 2 * u) * cstride4) : 0.f;
-        zr[u] = has_c ? buf_load(rz, voff, (cn + 2 * u) * cstride4) : 0.f;
+        gr[u] = has_g ? buf_load<1>(rg, voff, (cn + 2 * u) * cstride4) : 0.f;
+        zr[u] = has_c ? buf_load<1>(rz, voff, (cn + 2 * u) * cstride4) : 0.f;
       }
 #pragma unroll
       for (int m = 0; m < MT; ++m) acc[m][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m], d, acc[m][0], 0, 0, 0);
@@ -818,15 +803,15 @@ __global__ __launch_bounds__(PW_NT) void k_pwconv_dgrad2(PwBwdArgs a) {
     const int pc = pok[j] ? pos : 0;
     const int row = pc / V;
     goff[j] = (row * a.stride) * V + (pc - row * V);
-    voff[j] = pok[j] ? (int)(((size_t)n * Co + half) * L + pc) * 4 : OOB_OFF;
-    voffa[j] = pok[j] ? (int)(((size_t)n * Co + half) * a.Tout + row) * 4 : OOB_OFF;
+    voff[j] = pok[j] ? (int)(((size_t)n * Co + half) * L + pc) * 4 : BUF_OOB;
+    voffa[j] = pok[j] ? (int)(((size_t)n * Co + half) * a.Tout + row) * 4 : BUF_OOB;
   }
   for (int i = tid; i < Co; i += PW_NT) Cs[i] = has_c ? float2{a.A0[i], a.B0[i]} : float2{0.f, 0.f};
   const size_t zbytes = (size_t)a.n * Co * L * 4, abytes = (size_t)a.n * Co * a.Tout * 4;
-  const __amdgpu_buffer_rsrc_t rg = make_rsrc(has_g ? a.gz : a.x1, has_g ? zbytes : 0);
-  const __amdgpu_buffer_rsrc_t rz = make_rsrc(has_c ? a.z : a.x1, has_c ? zbytes : 0);
-  const __amdgpu_buffer_rsrc_t rga = make_rsrc((AUG && a.gzaug) ? a.gzaug : a.x1, (AUG && a.gzaug) ? abytes : 0);
-  const __amdgpu_buffer_rsrc_t rza = make_rsrc((AUG && has_c) ? a.zaug : a.x1, (AUG && has_c) ? abytes : 0);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(has_g ? a.gz : a.x1, has_g ? zbytes : 0);
+  const __amdgpu_buffer_rsrc_t rz = buf_rsrc(has_c ? a.z : a.x1, has_c ? zbytes : 0);
+  const __amdgpu_buffer_rsrc_t rga = buf_rsrc((AUG && a.gzaug) ? a.gzaug : a.x1, (AUG && a.gzaug) ? abytes : 0);
+  const __amdgpu_buffer_rsrc_t rza = buf_rsrc((AUG && has_c) ? a.zaug : a.x1, (AUG && has_c) ? abytes : 0);
 
   f32x16 acc[MT][NW];
 #pragma unroll

@@ -23,7 +23,6 @@ namespace {
 
 constexpr int TC_NT = 256;
 constexpr int TC_MAXBR = 8;
-constexpr int TC_OOB = 0x7ffffff0;
 
 struct TBranch {
   int type;            // 0 conv, 1 max, 2 copy
@@ -45,13 +44,6 @@ struct TArgs {
   TBranch br[TC_MAXBR];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tc_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ float tc_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ int tc_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 __device__ __forceinline__ int tc_cp(const TBranch& br) { return (min(64, max(br.cin, 1)) + 7) & ~7; }
 
 // weight tile (co0l.., ci0l..) of W (cout, cin, KT) -> LDS [co_l][tap*CP + ci_l], zero padded to 64 rows
@@ -105,7 +97,7 @@ __device__ __forceinline__ void tc_accum(f32x16 (&acc)[2], const float* Ws, __am
 #pragma unroll
     for (int tap = 0; tap < KT; ++tap)
 #pragma unroll
-      for (int u = 0; u < NG * 4; ++u) x[tap][u] = tc_load(rs, voff[tap], (sbase + 2 * u) * cstride4);
+      for (int u = 0; u < NG * 4; ++u) x[tap][u] = buf_load<1>(rs, voff[tap], (sbase + 2 * u) * cstride4);
 #pragma unroll
     for (int tap = 0; tap < KT; ++tap)
 #pragma unroll
@@ -124,10 +116,10 @@ __device__ __forceinline__ void tc_accum(f32x16 (&acc)[2], const float* Ws, __am
   for (int tap = 0; tap < KT; ++tap) {
     float xa[4], xb[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) xa[u] = tc_load(rs, voff[tap], (sbase + 2 * u) * cstride4);
+    for (int u = 0; u < 4; ++u) xa[u] = buf_load<1>(rs, voff[tap], (sbase + 2 * u) * cstride4);
     for (int k0 = 0; k0 < nsp; k0 += 16) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u) xb[u] = tc_load(rs, voff[tap], (sbase + k0 + 8 + 2 * u) * cstride4);
+      for (int u = 0; u < 4; ++u) xb[u] = buf_load<1>(rs, voff[tap], (sbase + k0 + 8 + 2 * u) * cstride4);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int kl = k0 + 2 * u + half;
@@ -142,7 +134,7 @@ __device__ __forceinline__ void tc_accum(f32x16 (&acc)[2], const float* Ws, __am
       }
       if (k0 + 8 < nsp) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) xa[u] = tc_load(rs, voff[tap], (sbase + k0 + 16 + 2 * u) * cstride4);
+        for (int u = 0; u < 4; ++u) xa[u] = buf_load<1>(rs, voff[tap], (sbase + k0 + 16 + 2 * u) * cstride4);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int kl = k0 + 8 + 2 * u + half;
@@ -181,7 +173,7 @@ __device__ __forceinline__ void tc_conv(const TArgs& a, const TBranch& br, float
   const int ndst_all = FWD ? br.cout : br.cin;
   const int d0 = chunk * 64, nd = min(64, ndst_all - d0);
   const size_t src_bytes = (size_t)a.n * Csrc * Tsrc * V1 * 4;
-  const __amdgpu_buffer_rsrc_t rs = tc_rsrc(FWD ? a.h : a.go, src_bytes);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(FWD ? a.h : a.go, src_bytes);
   const int cstride4 = Tsrc * V1 * 4;
   int voff[KT];
 #pragma unroll
@@ -196,7 +188,7 @@ __device__ __forceinline__ void tc_conv(const TArgs& a, const TBranch& br, float
       rs_row = num / a.stride;
       ok = ok && num >= 0 && (num - rs_row * a.stride) == 0 && rs_row < a.Tout;
     }
-    voff[tap] = ok ? (int)((((size_t)n * Csrc + sch0 + half) * Tsrc + rs_row) * V1 + col) * 4 : TC_OOB;
+    voff[tap] = ok ? (int)((((size_t)n * Csrc + sch0 + half) * Tsrc + rs_row) * V1 + col) * 4 : BUF_OOB;
   }
   f32x16 acc[2];
 #pragma unroll
@@ -221,7 +213,7 @@ __device__ __forceinline__ void tc_conv(const TArgs& a, const TBranch& br, float
     for (int m = 0; m < 2; ++m) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int ch = 32 * m + tc_row32(r, half);
+        const int ch = 32 * m + mfma_row32(r, half);
         if (ch < nd) {
           const float bias = (FWD && br.b) ? br.b[d0 + ch] : 0.f;
           dst[((size_t)(n * Cdst + dch0 + ch) * Tdst) * V1 + pos] = acc[m][r] + bias;
@@ -408,7 +400,7 @@ __global__ __launch_bounds__(W8 ? 512 : TC_NT) void k_tapconv_wgrad(TArgs a) {
   if (ci < nci) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = 32 * mt + tc_row32(r, half);
+      const int co = 32 * mt + mfma_row32(r, half);
       if (co < nco) {
 #pragma unroll
         for (int k = 0; k < KTG; ++k)
@@ -496,7 +488,7 @@ __global__ __launch_bounds__(TC_NT) void k_tapconv_wgrad_narrow(TArgs a) {
   if (l31 < nci) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = tc_row32(r, half);
+      const int co = mfma_row32(r, half);
       if (co < nco) {
 #pragma unroll
         for (int k = 0; k < KT; ++k) dwp[((size_t)co * br.cin + l31) * KT + k] = acc[k][r];
@@ -526,14 +518,6 @@ __global__ __launch_bounds__(TC_NT) void k_tapconv_wgrad_narrow(TArgs a) {
 // their channels in a per-thread loop of dependent loads and recomputed the pooling argmax from global memory
 // (tools/tc_bench.py, 128 samples: forward 53..93 us, data gradient 71..134 us per layer before).
 // ---------------------------------------------------------------------------------------------------------------
-typedef float f32x2t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x4 t4_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x2t t4_load2(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(f32x2t, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
 
 template <bool FWD, int MT, bool S2>
 __device__ __forceinline__ void t4_conv(const TArgs& a, const TBranch& br, float* Ws, int grp, int lane, int wave) {
@@ -556,7 +540,7 @@ __device__ __forceinline__ void t4_conv(const TArgs& a, const TBranch& br, float
   int p = g0 - n0 * L + 4 * l31, ds = 0;
   while (p >= L) { p -= L; ++ds; }
   const bool pok = wlive && n0 + ds < a.n;
-  const __amdgpu_buffer_rsrc_t rs = tc_rsrc(FWD ? a.h : a.go, (size_t)a.n * Csrc * L4);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(FWD ? a.h : a.go, (size_t)a.n * Csrc * L4);
   const int rowbase = ((n0 + ds) * Csrc + sch0 + half) * Ls;  // (the launch checks the tensor stays below 2^31 bytes)
   // operand offsets of the lane's two position pairs, per tap.  Stride 1: a tap shifts by whole rows, the centre tap is
   // one 16-byte load.  Stride 2 (forward: output row t' reads input rows 2t' + (tap-1)*dil; data gradient: input row t
@@ -569,7 +553,7 @@ __device__ __forceinline__ void t4_conv(const TArgs& a, const TBranch& br, float
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int q = p + (tap - 1) * sh + 2 * j;
-        vP[tap][j] = (pok && q >= 0 && q <= Ls - 2) ? (rowbase + q) * 4 : TC_OOB;
+        vP[tap][j] = (pok && q >= 0 && q <= Ls - 2) ? (rowbase + q) * 4 : BUF_OOB;
       }
   } else {
     const float invV1 = 1.f / (float)V1;
@@ -589,14 +573,14 @@ __device__ __forceinline__ void t4_conv(const TArgs& a, const TBranch& br, float
           row = num >> 1;
           ok = ok && num >= 0 && !(num & 1) && row < a.Tout;
         }
-        vP[tap][j] = ok ? (rowbase + row * V1 + x) * 4 : TC_OOB;
+        vP[tap][j] = ok ? (rowbase + row * V1 + x) * 4 : BUF_OOB;
       }
     }
   }
   auto load = [&](int tap, int ks) -> f32x4 {
     const int soff = 2 * ks * L4;
-    if (!S2 && tap == 1) return t4_load4(rs, vP[1][0], soff);
-    const f32x2t lo = t4_load2(rs, vP[tap][0], soff), hi = t4_load2(rs, vP[tap][1], soff);
+    if (!S2 && tap == 1) return buf_load<4>(rs, vP[1][0], soff);
+    const f32x2v lo = buf_load<2>(rs, vP[tap][0], soff), hi = buf_load<2>(rs, vP[tap][1], soff);
     return f32x4{lo.x, lo.y, hi.x, hi.y};
   };
 
@@ -643,16 +627,16 @@ __device__ __forceinline__ void t4_conv(const TArgs& a, const TBranch& br, float
     }
   }
   float* dst = FWD ? a.o : a.dh;
-  const __amdgpu_buffer_rsrc_t ro = tc_rsrc(dst, (size_t)a.n * Cdst * L * 4);
+  const __amdgpu_buffer_rsrc_t ro = buf_rsrc(dst, (size_t)a.n * Cdst * L * 4);
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int ch = 32 * m + tc_row32(r, half);
+      const int ch = 32 * m + mfma_row32(r, half);
       const float bias = (FWD && br.b && ch < ndst) ? br.b[ch] : 0.f;
       const f32x4 v = {acc[m][0][r] + bias, acc[m][1][r] + bias, acc[m][2][r] + bias, acc[m][3][r] + bias};
-      const int voff = (pok && ch < ndst) ? (((n0 + ds) * Cdst + dch0 + ch) * L + p) * 4 : TC_OOB;
+      const int voff = (pok && ch < ndst) ? (((n0 + ds) * Cdst + dch0 + ch) * L + p) * 4 : BUF_OOB;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ro, voff, 0, 0);
     }
   }
@@ -803,22 +787,22 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
   const int per = (units + a.splits - 1) / a.splits;
   const int u0 = blockIdx.x * per, u1 = min(units, u0 + per);
 
-  const __amdgpu_buffer_rsrc_t rg = tc_rsrc(a.go, (size_t)a.n * a.Cout * L * 4);
-  const __amdgpu_buffer_rsrc_t rh = tc_rsrc(a.h, (size_t)a.n * a.Cin * L * 4);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.go, (size_t)a.n * a.Cout * L * 4);
+  const __amdgpu_buffer_rsrc_t rh = buf_rsrc(a.h, (size_t)a.n * a.Cin * L * 4);
   // staging slots: f = tid + 256*j -> (row, float4 column); fixed per thread
   int vD[JD], lD[JD], vX[JX], lX[JX], segX[JX];
 #pragma unroll
   for (int j = 0; j < JD; ++j) {
     const int f = tid + TC_NT * j, row = f / GW4, c4 = f - row * GW4;
     const bool ok = row < nco;
-    vD[j] = ok ? (row * L + 4 * c4) * 4 : TC_OOB;
+    vD[j] = ok ? (row * L + 4 * c4) * 4 : BUF_OOB;
     lD[j] = ok ? row * LSd + 4 * c4 : -1;
   }
 #pragma unroll
   for (int j = 0; j < JX; ++j) {
     const int f = tid + TC_NT * j, row = f / XW4, c4 = f - row * XW4;
     const bool ok = row < nci;
-    vX[j] = ok ? (row * L + 4 * c4) * 4 : TC_OOB;
+    vX[j] = ok ? (row * L + 4 * c4) * 4 : BUF_OOB;
     lX[j] = ok ? row * LSx + 4 * c4 : -1;
     segX[j] = c4 / SEG4;                                             // 0 = halo before, 1 = the unit, 2 = halo after
   }
@@ -832,29 +816,29 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
     const int sx = ((n * a.Cin + br.ci0) * L + (t0 - TW_H) * V1) * 4;    // may be negative: only used with valid slots
     const bool before = t0 >= TW_H, after = t0 + TW_R < T;
 #pragma unroll
-    for (int j = 0; j < JD; ++j) gr[j] = t4_load4(rg, vD[j], sg);
+    for (int j = 0; j < JD; ++j) gr[j] = buf_load<4>(rg, vD[j], sg);
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const bool ok = segX[j] == 1 || (segX[j] == 0 ? before : after);
-      xr[j] = t4_load4(rh, ok ? vX[j] + sx : TC_OOB, 0);
+      xr[j] = buf_load<4>(rh, ok ? vX[j] + sx : BUF_OOB);
     }
   };
   auto commit = [&]() {
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       if (lD[j] >= 0) {
-        f32x2t* d = reinterpret_cast<f32x2t*>(Ds + lD[j]);
-        d[0] = f32x2t{gr[j].x, gr[j].y};
-        d[1] = f32x2t{gr[j].z, gr[j].w};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Ds + lD[j]);
+        d[0] = f32x2v{gr[j].x, gr[j].y};
+        d[1] = f32x2v{gr[j].z, gr[j].w};
         dsum[j] += (gr[j].x + gr[j].y) + (gr[j].z + gr[j].w);
       }
     }
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       if (lX[j] >= 0) {
-        f32x2t* d = reinterpret_cast<f32x2t*>(Xs + lX[j]);
-        d[0] = f32x2t{xr[j].x, xr[j].y};
-        d[1] = f32x2t{xr[j].z, xr[j].w};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Xs + lX[j]);
+        d[0] = f32x2v{xr[j].x, xr[j].y};
+        d[1] = f32x2v{xr[j].z, xr[j].w};
       }
     }
   };
@@ -877,14 +861,13 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
   if (u0 < u1) issue(u0);
   for (int u = u0; u < u1; ++u) {
     commit();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     if (u + 1 < u1) issue(u + 1);
     for (int g = g0; g < g1; ++g) {
-      const f32x2t av = *reinterpret_cast<const f32x2t*>(Ap + 4 * g);
-      const f32x2t b0 = *reinterpret_cast<const f32x2t*>(Bp + 4 * g - sh);
-      const f32x2t b1 = *reinterpret_cast<const f32x2t*>(Bp + 4 * g);
-      const f32x2t b2 = *reinterpret_cast<const f32x2t*>(Bp + 4 * g + sh);
+      const f32x2v av = *reinterpret_cast<const f32x2v*>(Ap + 4 * g);
+      const f32x2v b0 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g - sh);
+      const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g);
+      const f32x2v b2 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g + sh);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b2.x, acc[2], 0, 0, 0);
@@ -892,8 +875,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b2.y, acc[2], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                   // raw barrier: the next unit's loads stay in flight
+    block_lds_sync();                   // raw barrier: the next unit's loads stay in flight
   }
 
   float* dw = br.dwp + (size_t)blockIdx.x * a.pstride;
@@ -904,7 +886,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
 #pragma unroll
     for (int k = 0; k < KT; ++k)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + tc_row32(r, half)) * 33 + l31] = acc[k][r];
+      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + mfma_row32(r, half)) * 33 + l31] = acc[k][r];
     __syncthreads();
     for (int o = tid; o < KT * nco * nci; o += TC_NT) {
       const int co = o / (nci * KT), r2 = o - co * nci * KT, ci = r2 / KT, k = r2 - ci * KT;
@@ -919,7 +901,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw(TArgs a, int n
     if (ci < nci) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = 32 * mt + tc_row32(r, half);
+        const int co = 32 * mt + mfma_row32(r, half);
         if (co < nco) {
 #pragma unroll
           for (int k = 0; k < KT; ++k) dw[((size_t)co * nci + ci) * KT + k] = acc[k][r];
@@ -970,14 +952,14 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
   const int units = a.n * (To / TW_R);
   const int per = (units + a.splits - 1) / a.splits;
   const int u0 = blockIdx.x * per, u1 = min(units, u0 + per);
-  const __amdgpu_buffer_rsrc_t rg = tc_rsrc(a.go, (size_t)a.n * a.Cout * Lo * 4);
-  const __amdgpu_buffer_rsrc_t rh = tc_rsrc(a.h, (size_t)a.n * a.Cin * L * 4);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.go, (size_t)a.n * a.Cout * Lo * 4);
+  const __amdgpu_buffer_rsrc_t rh = buf_rsrc(a.h, (size_t)a.n * a.Cin * L * 4);
   int vD[JD], lD[JD], vX[JX], lX[JX], rX[JX];
 #pragma unroll
   for (int j = 0; j < JD; ++j) {
     const int f = tid + TC_NT * j, row = f / GW4, c4 = f - row * GW4;
     const bool ok = row < nco;
-    vD[j] = ok ? (row * Lo + 4 * c4) * 4 : TC_OOB;
+    vD[j] = ok ? (row * Lo + 4 * c4) * 4 : BUF_OOB;
     lD[j] = ok ? row * LSd + 4 * c4 : -1;
   }
   const int xslots = KT * TW_R * nci * PV;                           // (tap, frame r, channel, pair)
@@ -987,12 +969,12 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
     const int pp = f % PV, q = f / PV, ch = q % nci, tr = q / nci;   // tr = tap*4 + r
     const bool ok = f < xslots;
     const int tap = tr >> 2, r = tr & 3;
-    vX[j] = ok ? (ch * L + 2 * pp) * 4 : TC_OOB;                     // + input row offset per unit
+    vX[j] = ok ? (ch * L + 2 * pp) * 4 : BUF_OOB;                     // + input row offset per unit
     lX[j] = ok ? (tap * CH + ch) * LSd + r * V1 + 2 * pp : -1;
     rX[j] = 2 * r + (tap - 1) * br.dil;                              // input row relative to 2*t0
   }
   f32x4 gr[JD];
-  f32x2t xr[JX];
+  f32x2v xr[JX];
   float dsum[JD];
 #pragma unroll
   for (int j = 0; j < JD; ++j) dsum[j] = 0.f;
@@ -1001,27 +983,27 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
     const int sg = ((n * a.Cout + br.co0) * Lo + t0 * V1) * 4;
     const int sx = (n * a.Cin + br.ci0) * L * 4;
 #pragma unroll
-    for (int j = 0; j < JD; ++j) gr[j] = t4_load4(rg, vD[j], sg);
+    for (int j = 0; j < JD; ++j) gr[j] = buf_load<4>(rg, vD[j], sg);
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const int row = 2 * t0 + rX[j];
       const bool ok = row >= 0 && row < T;
-      xr[j] = t4_load2(rh, ok ? vX[j] + row * V1 * 4 : TC_OOB, sx);
+      xr[j] = buf_load<2>(rh, ok ? vX[j] + row * V1 * 4 : BUF_OOB, sx);
     }
   };
   auto commit = [&]() {
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       if (lD[j] >= 0) {
-        f32x2t* d = reinterpret_cast<f32x2t*>(Ds + lD[j]);
-        d[0] = f32x2t{gr[j].x, gr[j].y};
-        d[1] = f32x2t{gr[j].z, gr[j].w};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Ds + lD[j]);
+        d[0] = f32x2v{gr[j].x, gr[j].y};
+        d[1] = f32x2v{gr[j].z, gr[j].w};
         dsum[j] += (gr[j].x + gr[j].y) + (gr[j].z + gr[j].w);
       }
     }
 #pragma unroll
     for (int j = 0; j < JX; ++j)
-      if (lX[j] >= 0) *reinterpret_cast<f32x2t*>(Xs + lX[j]) = xr[j];
+      if (lX[j] >= 0) *reinterpret_cast<f32x2v*>(Xs + lX[j]) = xr[j];
   };
   f32x16 acc[KT];
 #pragma unroll
@@ -1037,14 +1019,13 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
   if (u0 < u1) issue(u0);
   for (int u = u0; u < u1; ++u) {
     commit();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     if (u + 1 < u1) issue(u + 1);
     for (int g = g0; g < g1; ++g) {
-      const f32x2t av = *reinterpret_cast<const f32x2t*>(Ap + 4 * g);
-      const f32x2t b0 = *reinterpret_cast<const f32x2t*>(Bp + 4 * g);
-      const f32x2t b1 = *reinterpret_cast<const f32x2t*>(Bp + CH * LSd + 4 * g);
-      const f32x2t b2 = *reinterpret_cast<const f32x2t*>(Bp + 2 * CH * LSd + 4 * g);
+      const f32x2v av = *reinterpret_cast<const f32x2v*>(Ap + 4 * g);
+      const f32x2v b0 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g);
+      const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bp + CH * LSd + 4 * g);
+      const f32x2v b2 = *reinterpret_cast<const f32x2v*>(Bp + 2 * CH * LSd + 4 * g);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b2.x, acc[2], 0, 0, 0);
@@ -1052,8 +1033,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b2.y, acc[2], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
   }
 
   float* dw = br.dwp + (size_t)blockIdx.x * a.pstride;
@@ -1063,7 +1043,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
 #pragma unroll
     for (int k = 0; k < KT; ++k)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + tc_row32(r, half)) * 33 + l31] = acc[k][r];
+      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + mfma_row32(r, half)) * 33 + l31] = acc[k][r];
     __syncthreads();
     for (int o = tid; o < KT * nco * nci; o += TC_NT) {
       const int co = o / (nci * KT), r2 = o - co * nci * KT, ci = r2 / KT, k = r2 - ci * KT;
@@ -1078,7 +1058,7 @@ __global__ __launch_bounds__(TC_NT, CH == 32 ? 2 : 1) void k_tapw2(TArgs a, int 
     if (ci < nci) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = 32 * mt + tc_row32(r, half);
+        const int co = 32 * mt + mfma_row32(r, half);
         if (co < nco) {
 #pragma unroll
           for (int k = 0; k < KT; ++k) dw[((size_t)co * nci + ci) * KT + k] = acc[k][r];
@@ -1241,7 +1221,7 @@ int dsgcn_tapconv_fwd(const float* h, float* o, int n, int Cin, int Cout, int T,
                       const float* const* w, const float* const* b, void* stream) {
   if (!h || !o || n <= 0 || Cin <= 0 || Cout <= 0 || T <= 0 || V1 <= 0 || stride <= 0 || nbr <= 0 || nbr > TC_MAXBR)
     return DSGCN_EINVAL;
-  if ((size_t)n * Cin * T * V1 * 4 >= (size_t)TC_OOB) return DSGCN_EUNSUPPORTED;
+  if ((size_t)n * Cin * T * V1 * 4 >= (size_t)BUF_OOB) return DSGCN_EUNSUPPORTED;
   TArgs a = {};
   a.h = h; a.o = o; a.n = n; a.Cin = Cin; a.Cout = Cout; a.T = T; a.V1 = V1; a.stride = stride; a.nbr = nbr;
   a.Tout = (T + stride - 1) / stride;
@@ -1277,7 +1257,7 @@ int dsgcn_tapconv_dgrad(const float* h, const float* go, float* dh, int n, int C
   TArgs a = {};
   a.h = h; a.go = go; a.dh = dh; a.n = n; a.Cin = Cin; a.Cout = Cout; a.T = T; a.V1 = V1; a.stride = stride; a.nbr = nbr;
   a.Tout = (T + stride - 1) / stride;
-  if ((size_t)n * Cout * a.Tout * V1 * 4 >= (size_t)TC_OOB) return DSGCN_EUNSUPPORTED;
+  if ((size_t)n * Cout * a.Tout * V1 * 4 >= (size_t)BUF_OOB) return DSGCN_EUNSUPPORTED;
   const int cp = tc_fill(a, nbr, type, ci0, co0, cin, cout, dil);
   if (cp < 0) return cp;
   for (int i = 0; i < nbr; ++i) {

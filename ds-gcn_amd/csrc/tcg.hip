@@ -34,7 +34,6 @@ namespace {
 constexpr int TG_NT = 256;                       // 4 waves (k_tcg); the weight gradient brings 8
 constexpr int TG_KC = 32;                        // channels per chunk
 constexpr int TG_RB = TG_KC * 2 + 16;            // LDS row: 32 bf16 + 16 B pad (conflict-free 16-byte fragment reads)
-constexpr int TG_OOB = 0x7ffffff0;
 constexpr int TG_MAXIT = 12;                     // staging items per thread and chunk (rows <= 384, 8 channel groups each)
 constexpr int TG_PASS = 6;                       // staging items loaded together
 constexpr int TW_NT = 512;
@@ -54,14 +53,6 @@ struct TcgArgs {
   int n, K, M, V, KT, R, tps, cc, Mp, Kp;                                  // R output frames per tile, tps tiles per sample
   int Ts, To, st, up;          // frames of the B source / of the output; forward stride (lane row stride); source upsampling (data gradient of a strided conv)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tg_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float tg_load(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ int tg_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // sum over the 32 lanes of a half-wave (lanes l and l^32 keep their own)
 __device__ __forceinline__ float half_sum(float v) {
@@ -97,8 +88,8 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
   const int f0 = ti * R;                           // first output frame of the tile
   const int mBase0 = cz * 32 * WM;
   const float invV = 1.f / (float)V;
-  const __amdgpu_buffer_rsrc_t r1 = tg_rsrc(a.b1 + (size_t)ns * K * Ls, K * Ls * 4);
-  const __amdgpu_buffer_rsrc_t r2 = tg_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)ns * K * Ls, MODE == 2 ? K * Ls * 4 : 0);
+  const __amdgpu_buffer_rsrc_t r1 = buf_rsrc(a.b1 + (size_t)ns * K * Ls, K * Ls * 4);
+  const __amdgpu_buffer_rsrc_t r2 = buf_rsrc((MODE == 2 ? a.b2 : a.b1) + (size_t)ns * K * Ls, MODE == 2 ? K * Ls * 4 : 0);
   // staging items: (image row j, channel group cg = 4 channels); item = tid + TG_NT*i
   const int nit = (NR * 8 + TG_NT - 1) / TG_NT;
   int soff[QS ? 1 : TG_MAXIT], sdst[QS ? 1 : TG_MAXIT];
@@ -110,7 +101,7 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
     const int fv = a.st * f0 - pad + fr;           // frame on the (upsampled) source grid
     const int f = a.up == 1 ? fv : fv / a.up;
     const bool ok = i < nit && j < NR && fv >= 0 && f * a.up == fv && f < a.Ts;
-    soff[i] = ok ? (f * V + v + 4 * cg * Ls) * 4 : TG_OOB;              // + ch0*Ls*4 per chunk
+    soff[i] = ok ? (f * V + v + 4 * cg * Ls) * 4 : BUF_OOB;              // + ch0*Ls*4 per chunk
     sdst[i] = (i < nit && j < NR) ? j * TG_RB + cg * 8 : -1;
   }
   // Staging of a chunk: loads, activation, split and LDS stores in passes of TG_PASS items (the raw values are not held
@@ -147,9 +138,9 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const int c = ch0 + 4 * (tid & 7) + e;                    // (item & 7 == tid & 7: TG_NT is a multiple of 8)
-              const int vo = (c < K && soff[i] != TG_OOB) ? soff[i] + e * Ls * 4 : TG_OOB;
-              bw[ii][e] = tg_load(r1, vo, ch0 * Ls * 4);
-              if constexpr (MODE == 2) bw2[ii][e] = tg_load(r2, vo, ch0 * Ls * 4);
+              const int vo = (c < K && soff[i] != BUF_OOB) ? soff[i] + e * Ls * 4 : BUF_OOB;
+              bw[ii][e] = buf_load<1>(r1, vo, ch0 * Ls * 4);
+              if constexpr (MODE == 2) bw2[ii][e] = buf_load<1>(r2, vo, ch0 * Ls * 4);
             }
           }
         }
@@ -158,7 +149,7 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
           const int i = i0 + ii;
           if (i < nit && sdst[i] >= 0) {
             float v[4];
-            const bool ok = soff[i] != TG_OOB;      // rows outside the sample's frames: zero AFTER the activation
+            const bool ok = soff[i] != BUF_OOB;      // rows outside the sample's frames: zero AFTER the activation
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               float x = bw[ii][e];
@@ -220,10 +211,10 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int c = ch0 + 4 * (tid & 7) + e;
-            const int vo = ((c < K) & qok) ? ((4 * (tid & 7) + e) * Ls + p4) * 4 : TG_OOB;
-            bw[ii][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r1, vo, ch0 * Ls * 4, 0));
+            const int vo = ((c < K) & qok) ? ((4 * (tid & 7) + e) * Ls + p4) * 4 : BUF_OOB;
+            bw[ii][e] = buf_load<4>(r1, vo, ch0 * Ls * 4);
             if constexpr (MODE == 2)
-              bw2[ii][e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2, vo, ch0 * Ls * 4, 0));
+              bw2[ii][e] = buf_load<4>(r2, vo, ch0 * Ls * 4);
           }
         }
 #pragma unroll
@@ -280,7 +271,7 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
   f32x16 acc[NQW];
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = mBase0 + 32 * rt + tg_row32(i, half);
+    const int row = mBase0 + 32 * rt + mfma_row32(i, half);
     const float b0 = (EPI == 0 && a.bias && row < M) ? a.bias[row] : 0.f;
 #pragma unroll
     for (int q = 0; q < NQW; ++q) acc[q][i] = b0;
@@ -306,13 +297,11 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
   }
   for (int ch0 = 0; ch0 < a.Kp; ch0 += TG_KC) {
     if (ch0 > 0) {                                 // every wave is done with the previous chunk's image
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
+      block_lds_sync();
     }
     if constexpr (QS) stageBq(ch0);
     else stageB(ch0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
 #pragma unroll 1
     for (int tap = 0; tap < KT; ++tap) {
       if constexpr (PF2) {                         // the weights of the step after next
@@ -362,16 +351,16 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
   const size_t obase = (size_t)ns * M * L;
   if (EPI == 0) {
     const bool stats = a.partial != nullptr;
-    const __amdgpu_buffer_rsrc_t ro = tg_rsrc(a.out + obase, M * L * 4);      // dead slots / rows: out-of-range offsets, no branches
+    const __amdgpu_buffer_rsrc_t ro = buf_rsrc(a.out + obase, M * L * 4);      // dead slots / rows: out-of-range offsets, no branches
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row32 = tg_row32(r, half), row = mBase0 + 32 * rt + row32;
+      const int row32 = mfma_row32(r, half), row = mBase0 + 32 * rt + row32;
       float s = 0.f, qq = 0.f;
 #pragma unroll
       for (int q = 0; q < NQW; ++q) {
         const bool ok = ovalid[q] && row < M;
         const float v = ok ? acc[q][r] : 0.f;
-        const int vo = (int)((unsigned)(ok ? opos[q] * 4 : TG_OOB) + (unsigned)(row * L * 4));
+        const int vo = (int)((unsigned)(ok ? opos[q] * 4 : BUF_OOB) + (unsigned)(row * L * 4));
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, vo, 0, 0);
         s += v;
         qq = fmaf(v, v, qq);
@@ -402,23 +391,23 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
     // rows — no branches — and are fetched one group of four rows AHEAD of the group being finished: as a per-element
     // `if (valid) { load; use; store }` the epilogue was sixteen dependent round trips per wave (the data gradient ran at
     // 1.5x the forward's time; round 4).
-    const __amdgpu_buffer_rsrc_t rx1 = tg_rsrc(a.ex1 + obase, need_x ? M * L * 4 : 0);
-    const __amdgpu_buffer_rsrc_t rx2 = tg_rsrc((has2 ? a.ex2 : a.ex1) + obase, has2 ? M * L * 4 : 0);
-    const __amdgpu_buffer_rsrc_t ro1 = tg_rsrc(a.out + obase, M * L * 4);
-    const __amdgpu_buffer_rsrc_t ro2 = tg_rsrc((a.out2 ? a.out2 : a.out) + obase, a.out2 ? M * L * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rx1 = buf_rsrc(a.ex1 + obase, need_x ? M * L * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rx2 = buf_rsrc((has2 ? a.ex2 : a.ex1) + obase, has2 ? M * L * 4 : 0);
+    const __amdgpu_buffer_rsrc_t ro1 = buf_rsrc(a.out + obase, M * L * 4);
+    const __amdgpu_buffer_rsrc_t ro2 = buf_rsrc((a.out2 ? a.out2 : a.out) + obase, a.out2 ? M * L * 4 : 0);
     int ooff[NQW];
 #pragma unroll
-    for (int q = 0; q < NQW; ++q) ooff[q] = ovalid[q] ? opos[q] * 4 : TG_OOB;
+    for (int q = 0; q < NQW; ++q) ooff[q] = ovalid[q] ? opos[q] * 4 : BUF_OOB;
     float xa[2][4][NQW], xb[2][4][NQW];
     auto fetch = [&](int g, int slot) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        const int row = mBase0 + 32 * rt + tg_row32(4 * g + rr, half);
+        const int row = mBase0 + 32 * rt + mfma_row32(4 * g + rr, half);
 #pragma unroll
         for (int q = 0; q < NQW; ++q) {
-          const int vo = (int)((unsigned)(row < M ? ooff[q] : TG_OOB) + (unsigned)(row * L * 4));
-          xa[slot][rr][q] = tg_load(rx1, vo, 0);
-          xb[slot][rr][q] = tg_load(rx2, vo, 0);
+          const int vo = (int)((unsigned)(row < M ? ooff[q] : BUF_OOB) + (unsigned)(row * L * 4));
+          xa[slot][rr][q] = buf_load<1>(rx1, vo);
+          xb[slot][rr][q] = buf_load<1>(rx2, vo);
         }
       }
     };
@@ -432,7 +421,7 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int r = 4 * g + rr;
-        const int row32 = tg_row32(r, half), row = mBase0 + 32 * rt + row32;
+        const int row32 = mfma_row32(r, half), row = mBase0 + 32 * rt + row32;
         const bool rok = row < M;
         const float e1s = (rok && a.es1) ? a.es1[row] : 1.f, e1h = (rok && a.es1) ? a.eh1[row] : 0.f;
         const float e2s = (rok && a.es2) ? a.es2[row] : 1.f, e2h = (rok && a.es2) ? a.eh2[row] : 0.f;
@@ -444,7 +433,7 @@ __device__ __forceinline__ void tcg_body(const TcgArgs& a, float* lds) {
           float pre = fmaf(xav, e1s, e1h);
           if (has2) pre += fmaf(xbv, e2s, e2h);
           const float dv = (ok && (!a.erelu || pre > 0.f)) ? acc[q][r] : 0.f;
-          const int vo = (int)((unsigned)(rok ? ooff[q] : TG_OOB) + (unsigned)(row * L * 4));
+          const int vo = (int)((unsigned)(rok ? ooff[q] : BUF_OOB) + (unsigned)(row * L * 4));
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dv * e1s), ro1, vo, 0, 0);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dv * e2s), ro2, vo, 0, 0);   // zero-sized resource: no dx2
           u0 = fmaf(dv, xav, u0);
@@ -658,8 +647,8 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
     *reinterpret_cast<f32x4*>(XR + r * XP + ((xp + 4 * TW_RING) & (TW_RING - 1))) = f32x4{o[0], o[1], o[2], o[3]};
   };
   auto x_rsrc = [&](int ns, __amdgpu_buffer_rsrc_t& rx1, __amdgpu_buffer_rsrc_t& rx2) {
-    rx1 = tg_rsrc(a.x1 + (size_t)ns * Ci * Lx, Ci * Lx * 4);
-    rx2 = tg_rsrc((x2on ? a.x2 : a.x1) + (size_t)ns * Ci * Lx, x2on ? Ci * Lx * 4 : 0);
+    rx1 = buf_rsrc(a.x1 + (size_t)ns * Ci * Lx, Ci * Lx * 4);
+    rx2 = buf_rsrc((x2on ? a.x2 : a.x1) + (size_t)ns * Ci * Lx, x2on ? Ci * Lx * 4 : 0);
   };
   // aligned end of the span of the unit at p0
   auto span_hi = [&](int p0) { return (p0 + 32 + padV + 3) & ~3; };
@@ -670,9 +659,9 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
     x_rsrc(ns, rx1, rx2);
     const int r = tid >> 3, xp = span_hi(p0) - 32 + 4 * (tid & 7);
     // (quads are 4-aligned and the plane length is a multiple of 4: a quad is entirely inside or outside the plane)
-    const int vo = (ci0 + r < Ci && xp >= 0 && xp < Lx) ? ((ci0 + r) * Lx + xp) * 4 : TG_OOB;
-    xn = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx1, vo, 0, 0));
-    xn2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, vo, 0, 0));
+    const int vo = (ci0 + r < Ci && xp >= 0 && xp < Lx) ? ((ci0 + r) * Lx + xp) * 4 : BUF_OOB;
+    xn = buf_load<4>(rx1, vo);
+    xn2 = buf_load<4>(rx2, vo);
   };
   auto stageNew = [&](int u) {
     int ns, p0;
@@ -690,9 +679,9 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int q_ = q0 + TW_NT * i, r = q_ / nq, xp = lo4 + 4 * (q_ - r * nq);
-        const int vo = (q_ < TW_TN * nq && ci0 + r < Ci && xp >= 0 && xp < Lx) ? ((ci0 + r) * Lx + xp) * 4 : TG_OOB;
-        w1[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx1, vo, 0, 0));
-        w2[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, vo, 0, 0));
+        const int vo = (q_ < TW_TN * nq && ci0 + r < Ci && xp >= 0 && xp < Lx) ? ((ci0 + r) * Lx + xp) * 4 : BUF_OOB;
+        w1[i] = buf_load<4>(rx1, vo);
+        w2[i] = buf_load<4>(rx2, vo);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -729,14 +718,14 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
     const int p = p0 + 8 * apc;
     // buffer loads over the sample's planes: rows / quads outside get an out-of-range offset (zeros) — a conditional
     // load is a branch and a wait of its own (measured: 2 us to ISSUE a tap group's loads that way)
-    const __amdgpu_buffer_rsrc_t rg = tg_rsrc(a.gz + (size_t)ns * Co * L, Co * L * 4);
-    const __amdgpu_buffer_rsrc_t rz = tg_rsrc((dz2 ? a.z : a.gz) + (size_t)ns * Co * L, dz2 ? Co * L * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.gz + (size_t)ns * Co * L, Co * L * 4);
+    const __amdgpu_buffer_rsrc_t rz = buf_rsrc((dz2 ? a.z : a.gz) + (size_t)ns * Co * L, dz2 ? Co * L * 4 : 0);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const bool ok = aco < Co && p + 4 * h < L;          // (L % 4 == 0: a quad is inside or outside the plane)
-      const int vo = ok ? (aco * L + p + 4 * h) * 4 : TG_OOB;
-      ag[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, vo, 0, 0));
-      az[h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rz, vo, 0, 0));
+      const int vo = ok ? (aco * L + p + 4 * h) * 4 : BUF_OOB;
+      ag[h] = buf_load<4>(rg, vo);
+      az[h] = buf_load<4>(rz, vo);
     }
   };
   // x' position of dz position q for tap 0: (st*t' - pad)*V + v; a tap adds V.  -1: q outside the plane
@@ -754,8 +743,8 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
     int ns, p0;
     unit_base(u, ns, p0);
     if (grp == 0) xpos(p0);
-    const __amdgpu_buffer_rsrc_t rx1 = tg_rsrc(a.x1 + (size_t)ns * Ci * Lx, Ci * Lx * 4);
-    const __amdgpu_buffer_rsrc_t rx2 = tg_rsrc((x2on ? a.x2 : a.x1) + (size_t)ns * Ci * Lx, x2on ? Ci * Lx * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rx1 = buf_rsrc(a.x1 + (size_t)ns * Ci * Lx, Ci * Lx * 4);
+    const __amdgpu_buffer_rsrc_t rx2 = buf_rsrc((x2on ? a.x2 : a.x1) + (size_t)ns * Ci * Lx, x2on ? Ci * Lx * 4 : 0);
 #pragma unroll
     for (int tl = 0; tl < TW_G; ++tl) {
       const int tap = grp * TW_G + tl;
@@ -764,9 +753,9 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
         for (int e = 0; e < 4; ++e) {
           const int q = xq[e] + tap * V;
           const bool ok = bci < Ci && q >= 0 && q < Lx;
-          const int vo = ok ? (bci * Lx + q) * 4 : TG_OOB;
-          bx[tl][e] = tg_load(rx1, vo, 0);
-          bx2[tl][e] = tg_load(rx2, vo, 0);
+          const int vo = ok ? (bci * Lx + q) * 4 : BUF_OOB;
+          bx[tl][e] = buf_load<1>(rx1, vo);
+          bx2[tl][e] = buf_load<1>(rx2, vo);
         }
       }
     }
@@ -859,14 +848,10 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
       }
     }
   };
-  auto lds_barrier = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
   if constexpr (ST == 1) {
     // Units in order; `fresh` = the first unit of this workgroup or of a sample (the ring holds nothing of it yet).
     auto sample_of = [&](int u_) { return u_ / a.cpl; };
-    lds_barrier();                                 // the affine table of the window's channels is visible
+    block_lds_sync();                              // the affine table of the window's channels is visible
     if (u0 < u1) issueA(u0);
     for (int u = u0; u < u1; ++u) {
       const bool fresh = u == u0 || sample_of(u) != sample_of(u - 1);
@@ -880,11 +865,11 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
 #pragma unroll
       for (int grp = 0; grp < NG; ++grp) {           // (unrolled: the tap indices of the accumulators are compile-time)
         TCW_STAMP();
-        lds_barrier();                               // every wave is done with the previous step's products: images and dz image are free
+        block_lds_sync();                            // every wave is done with the previous step's products: images and dz image are free
         if (grp == 0) commitA(u, 0);
         buildB(u, grp);
         TCW_STAMP();
-        lds_barrier();                               // images (and the dz image) complete
+        block_lds_sync();                            // images (and the dz image) complete
         products(grp, 0, 0);
         TCW_STAMP();
         if (grp == 0) {
@@ -914,7 +899,7 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
       if (grp + 1 < NG) issueB(u, grp + 1);
       else if (u + 1 < u1) { issueA(u + 1); issueB(u + 1, 0); }
       TCW_STAMP();
-      lds_barrier();                               // this step's images complete; the other set is free (its readers passed the previous barrier)
+      block_lds_sync();                            // this step's images complete; the other set is free (its readers passed the previous barrier)
       TCW_STAMP();
       products(grp, abuf, gs & 1);
       TCW_STAMP();
@@ -933,7 +918,7 @@ __device__ __forceinline__ void tcw_body(const TcwArgs& a, float* lds) {
     if (owns(t % TW_G)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = co0 + 32 * rt + tg_row32(r, half);
+        const int co = co0 + 32 * rt + mfma_row32(r, half);
         if (co < Co && ci < Ci) dw[((size_t)co * Ci + ci) * KT + t] = acc[t][r];
       }
     }

@@ -175,14 +175,10 @@ __device__ __forceinline__ void tm_stage_w(const TmBranch& br, float* Wl, int CK
 // ---------------------------------------------------------------------------------------------------------------
 // software-pipelined staging: the global loads of the NEXT (unit, channel chunk) are issued into registers right after
 // the current one has been committed to LDS and land while the matrix product and the epilogue run.  Barriers are raw
-// s_barrier + lgkmcnt(0): a __syncthreads() would also drain vmcnt, i.e. wait for the epilogue's stores and the
+// s_barrier + lgkmcnt(0) (block_lds_sync, common.h): a __syncthreads() would also drain vmcnt, i.e. wait for the epilogue's stores and the
 // prefetch at every phase boundary (measured: the three phases of a unit then run strictly one after the other at
 // ~5 us each, none of them near a bound).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tm_bar() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
 
 constexpr int TM_NPF = 5;            // float4 prefetch slots per thread (16 channels x rows x V / 4 <= 2560)
 
@@ -363,9 +359,9 @@ __global__ __launch_bounds__(TM_NT, MTL >= 3 ? 3 : 4) void k_tms_fwd(TmArgs a) {
     const int rows = min(R, a.Tout - t0);                           // live output frames
     const int t_lo = t0 * s - TM_H;
     const int nq = (rows * V) >> 2;
-    tm_bar();                                                       // the previous item's readers are done
+    block_lds_sync();                                               // the previous item's readers are done
     if (!(dbg & 1)) tm_commit<0, false>(a, br, pf, Xl, XS, kc, t_lo, RIN, a.T, VL, AUG, tid);
-    tm_bar();
+    block_lds_sync();
     {                                                               // next item's loads
       int un = u, kn = kc + 1;
       if (kn == nchunk) { kn = 0; un += gridDim.x; }
@@ -417,7 +413,7 @@ __global__ __launch_bounds__(TM_NT, MTL >= 3 ? 3 : 4) void k_tms_fwd(TmArgs a) {
 #pragma unroll
         for (int m = 0; m < MTL; ++m) {
           if (16 * m >= bc) break;
-          tm_bar();
+          block_lds_sync();
 #pragma unroll
           for (int i = 0; i < TM_NTW; ++i) {
             const int P = 16 * (wave + 8 * i) + l15;
@@ -426,7 +422,7 @@ __global__ __launch_bounds__(TM_NT, MTL >= 3 ? 3 : 4) void k_tms_fwd(TmArgs a) {
               for (int r = 0; r < 4; ++r) Xl[(4 * kq + r) * DS + P] = acc[i][m][r];
             }
           }
-          tm_bar();
+          block_lds_sync();
           const int co = 16 * m + co_l;
           if (co < bc) {
             const float bias = br.b ? br.b[co] : 0.f;

@@ -32,11 +32,7 @@ namespace {
 
 constexpr int TS_NT = 256;
 constexpr int TS_MAXBR = 8;
-constexpr int TS_OOB = 0x7ffffff0;
 constexpr int TS_R = 4, TS_H = 4;                 // weight gradient: frames per unit, halo frames per side (max dilation)
-
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
 struct TSBranch {
   int type;            // 0 conv, 1 max (3,1), 2 pass-through
@@ -60,39 +56,12 @@ struct TSArgs {
   TSBranch br[TS_MAXBR];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ts_rsrc(const void* p, size_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ts_load4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x2s ts_load2(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  return __builtin_bit_cast(f32x2s, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
-}
 __device__ __forceinline__ void ts_store4(f32x4 v, __amdgpu_buffer_rsrc_t r, int voff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4s, v), r, voff, 0, 0);
-}
-__device__ __forceinline__ int ts_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-// vector offset of a per-row access (the row depends on the lane's half: it must not reach the scalar operand)
-__device__ __forceinline__ int ts_rowoff(bool ok, int base, int rowoff) {
-  return (int)((unsigned)(ok ? base : TS_OOB) + (unsigned)rowoff);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), r, voff, 0, 0);
 }
 __device__ __forceinline__ int ts_cp(int bc) { return (min(64, max(bc, 1)) + 7) & ~7; }
 
 __device__ __forceinline__ const TSBranch& ts_conv_window(const TSArgs& a, int w) { return a.br[a.cw[w]]; }
-
-// Sum of half of row l31 of a wave's [32][36] LDS tile (lane (half, l31); the caller adds the two halves).
-template <typename ACC>
-__device__ __forceinline__ ACC ts_rowread(const float* Tw, int half, int l31) {
-  const f32x4* rowp = reinterpret_cast<const f32x4*>(Tw + l31 * 36 + half * 16);
-  ACC s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x4 v = rowp[q];
-    s += ((ACC)v.x + (ACC)v.y) + ((ACC)v.z + (ACC)v.w);
-  }
-  return s;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // conv window, forward (FWD) or data gradient: four waves x 128 positions of the planes, all samples back to back; a lane
@@ -149,7 +118,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
   const int L = T * V, L4 = L * 4, Ls = Ts * V, Ls4 = Ls * 4;
   const int CP = ts_cp(bc), S = KT * CP + 1;
   float* Ws = lds;
-  f32x2s* SB = reinterpret_cast<f32x2s*>(lds + a.sboff);   // [64] (scale, shift): zero past the window
+  f32x2v* SB = reinterpret_cast<f32x2v*>(lds + a.sboff);   // [64] (scale, shift): zero past the window
   float* BI = lds + a.sboff + 128;                         // [64] bias
   float* HA = lds + a.sboff + 192;                         // [64][haw]: frames Gs .. Gs + haw of the block's channels
   const int HAW = a.haw;
@@ -164,7 +133,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
   const bool pok = wlive && n0 + ds < a.n;
   const float* srcp = FWD ? (AUG ? a.zaug : a.z) : (AUG ? a.doaug : a.ge);
   const int spad = (S2 && !FWD) ? FP : 0;
-  const __amdgpu_buffer_rsrc_t rs = ts_rsrc(srcp - spad, ((size_t)a.n * C * Ls + spad) * 4);
+  const __amdgpu_buffer_rsrc_t rs = buf_rsrc(srcp - spad, ((size_t)a.n * C * Ls + spad) * 4);
   const int rowbase = ((n0 + ds) * C + br.c0 + half) * Ls + spad;
   int t0 = 0, v0 = 0;                              // frame / joint of the lane's first position
   bool nx[4] = {false, false, false, false};       // element k lies in frame t0 + 1
@@ -191,7 +160,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
         const int qa = s ? q + 1 : (e ? q - 1 : q);
         fS[tap][j] = s;
         fE[tap][j] = e;
-        vP[tap][j] = (pok && (e0 || e1)) ? (rowbase + qa) * 4 : TS_OOB;
+        vP[tap][j] = (pok && (e0 || e1)) ? (rowbase + qa) * 4 : BUF_OOB;
         mk[tap][2 * j] = (pok && e0) ? 1.f : 0.f;
         mk[tap][2 * j + 1] = (pok && e1) ? 1.f : 0.f;
       }
@@ -215,14 +184,14 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
             ok = num >= 0 && !(num & 1) && src < Ts;
           }
           ok = ok && pok;
-          vP[tap][k] = ok ? (rowbase + src) * 4 : TS_OOB;
+          vP[tap][k] = ok ? (rowbase + src) * 4 : BUF_OOB;
           mk[tap][k] = ok ? 1.f : 0.f;
         }
       } else if (FWD) {
         const int fA = 2 * t0 + sft, fB = fA + 2;
         const bool okA = pok && fA >= 0 && fA < Ts, okB = pok && fB >= 0 && fB < Ts;
-        vP[tap][0] = okA ? (rowbase + fA * V + v0) * 4 : TS_OOB;
-        vP[tap][1] = okB ? (rowbase + fA * V + v0 + V) * 4 : TS_OOB;       // element k of frame t0 + 1: (fA + 2)*V + v0 + k - V
+        vP[tap][0] = okA ? (rowbase + fA * V + v0) * 4 : BUF_OOB;
+        vP[tap][1] = okB ? (rowbase + fA * V + v0 + V) * 4 : BUF_OOB;       // element k of frame t0 + 1: (fA + 2)*V + v0 + k - V
         vP[tap][2] = vP[tap][3] = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) mk[tap][k] = (nx[k] ? okB : okA) ? 1.f : 0.f;
@@ -233,7 +202,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
         const int fs = num >> 1;
         const bool ok = pok && num >= 0 && fs < Ts;
         // first-frame elements: source index fs*V + v0 + k;  second-frame elements: fs*V + v0 + k - V
-        vP[tap][0] = ok ? (rowbase + fs * V + v0 - (useA ? 0 : V)) * 4 : TS_OOB;
+        vP[tap][0] = ok ? (rowbase + fs * V + v0 - (useA ? 0 : V)) * 4 : BUF_OOB;
         vP[tap][1] = vP[tap][2] = vP[tap][3] = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) mk[tap][k] = (ok && (nx[k] != useA)) ? 1.f : 0.f;
@@ -244,19 +213,17 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
     const int soff = 2 * ks * Ls4;
     if constexpr (S2) {
       if constexpr (AUG)
-        return f32x4{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vP[tap][0], soff, 0)),
-                     __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vP[tap][1], soff, 0)),
-                     __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vP[tap][2], soff, 0)),
-                     __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vP[tap][3], soff, 0))};
+        return f32x4{buf_load<1>(rs, vP[tap][0], soff), buf_load<1>(rs, vP[tap][1], soff),
+                     buf_load<1>(rs, vP[tap][2], soff), buf_load<1>(rs, vP[tap][3], soff)};
       else
-        return ts_load4(rs, vP[tap][0], soff);
+        return buf_load<4>(rs, vP[tap][0], soff);
     } else {
-      if (tap == 1) return ts_load4(rs, vP[1][0], soff);
-      const f32x2s lo = ts_load2(rs, vP[tap][0], soff), hi = ts_load2(rs, vP[tap][1], soff);
+      if (tap == 1) return buf_load<4>(rs, vP[1][0], soff);
+      const f32x2v lo = buf_load<2>(rs, vP[tap][0], soff), hi = buf_load<2>(rs, vP[tap][1], soff);
       return f32x4{lo.x, lo.y, hi.x, hi.y};
     }
   };
-  auto loadB = [&](int tap, int ks) -> f32x4 { return ts_load4(rs, vP[tap][1], 2 * ks * Ls4); };   // forward, stride 2, V columns
+  auto loadB = [&](int tap, int ks) -> f32x4 { return buf_load<4>(rs, vP[tap][1], 2 * ks * Ls4); };   // forward, stride 2, V columns
   constexpr bool TWO = S2 && FWD && !AUG;
 
   // V columns, forward: add_coeff of the lane's four joints and the lane's frame inside the block's haug window
@@ -287,11 +254,11 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
       const int i = tid + q * TS_NT;
       wv[q] = i < wtotal ? br.w[i] : 0.f;
     }
-    f32x2s sb = {0.f, 0.f};
+    f32x2v sb = {0.f, 0.f};
     float bi = 0.f;
     if (tid < bc) {
       const int c = br.c0 + tid;
-      sb = f32x2s{a.scale ? a.scale[c] : 1.f, a.shift ? a.shift[c] : 0.f};
+      sb = f32x2v{a.scale ? a.scale[c] : 1.f, a.shift ? a.shift[c] : 0.f};
       if (br.b) bi = br.b[tid];
     }
     // haug: haw is a power of two (32 at V >= 23), thread = (frame tid % haw, channels tid / haw + k * 256 / haw): the
@@ -333,7 +300,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
     }
     if constexpr (FOLD) {
       auto put = [&](int ci, float x) {
-        const f32x2s e = SB[ci];
+        const f32x2v e = SB[ci];
         float y = fmaf(x, e.x, e.y);
         if (relu) y = fmaxf(y, 0.f);
         HA[ci * HAW + he] = (hok && ci < bc) ? y : 0.f;
@@ -373,12 +340,12 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
     return FWD ? Ws[(32 * m + l31) * S + tap * CP + kl] : Ws[kl * S + tap * CP + 32 * m + l31];
   };
   // haug of channel 2ks+half at the lane's frame shifted by the tap, and the frame after it
-  auto hfrag = [&](int tap, int ks) -> f32x2s {
+  auto hfrag = [&](int tap, int ks) -> f32x2v {
     const float* hp = HA + (2 * ks + half) * HAW + gl + (tap - 1) * br.dil;
-    return f32x2s{hp[0], hp[S2 ? 2 : 1]};          // (stride 2: the lane's second frame is two source frames on)
+    return f32x2v{hp[0], hp[S2 ? 2 : 1]};          // (stride 2: the lane's second frame is two source frames on)
   };
   float avb[2][MT];
-  f32x2s sbv[2], hab[2];
+  f32x2v sbv[2], hab[2];
 #pragma unroll
   for (int m = 0; m < MT; ++m) avb[0][m] = afrag(0, 0, m);
   sbv[0] = SB[half];
@@ -437,10 +404,10 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
   }
   TSC_STAMP();
   float* Tw = lds + wave * (32 * 36);               // one transpose tile per wave: the two sums of a row tile go through it in turn
-  const int ooff = pok ? (((n0 + ds) * C + br.c0) * L + p) * 4 : TS_OOB;
+  const int ooff = pok ? (((n0 + ds) * C + br.c0) * L + p) * 4 : BUF_OOB;
   if constexpr (FWD) {
     double* Ss = reinterpret_cast<double*>(lds + 4 * 32 * 36);       // [4][MT*32][2]
-    const __amdgpu_buffer_rsrc_t ro = ts_rsrc(AUG ? a.oaug : a.f, (size_t)a.n * C * L4);
+    const __amdgpu_buffer_rsrc_t ro = buf_rsrc(AUG ? a.oaug : a.f, (size_t)a.n * C * L4);
     const bool stats = !AUG && a.stats != nullptr && !(a.exp & 2);
     float bmul[4];
 #pragma unroll
@@ -451,7 +418,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
       float sq[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = ts_row32(r, half);
+        const int row = mfma_row32(r, half);
         const int ch = 32 * m + row;
         const float bias = BI[ch];
         f32x4 val;
@@ -462,7 +429,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
           s += val[k];
           qq = fmaf(val[k], val[k], qq);
         }
-        ts_store4(val, ro, ts_rowoff(ch < bc, ooff, ch * L4));
+        ts_store4(val, ro, buf_rowoff(ch < bc, ooff, ch * L4));
         if (stats) {
           const bool ok = ch < bc && pok;
           Tw[row * 36 + l31] = ok ? s : 0.f;
@@ -472,12 +439,12 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
       if (stats) {
         // (sums of a wave's 128 values of one row in fp32: 1e-7-class; everything across waves / blocks is fp64)
         wave_lds_sync();
-        float sf = ts_rowread<float>(Tw, half, l31);
+        float sf = tile36_rowsum<float>(Tw, half, l31);
         wave_lds_sync();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Tw[ts_row32(r, half) * 36 + l31] = sq[r];
+        for (int r = 0; r < 16; ++r) Tw[mfma_row32(r, half) * 36 + l31] = sq[r];
         wave_lds_sync();
-        float qf = ts_rowread<float>(Tw, half, l31);
+        float qf = tile36_rowsum<float>(Tw, half, l31);
         wave_lds_sync();
         sf += __shfl_xor(sf, 32, 64);
         qf += __shfl_xor(qf, 32, 64);
@@ -500,8 +467,8 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
     }
   } else {
     float* Ss = lds + 4 * 32 * 36;                                     // [4][MT*32][2]
-    const __amdgpu_buffer_rsrc_t rx = ts_rsrc(AUG ? a.zaug : a.z, (size_t)a.n * C * L4);
-    const __amdgpu_buffer_rsrc_t ro = ts_rsrc(AUG ? a.dzaug : a.dz, (size_t)a.n * C * L4);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(AUG ? a.zaug : a.z, (size_t)a.n * C * L4);
+    const __amdgpu_buffer_rsrc_t ro = buf_rsrc(AUG ? a.dzaug : a.dz, (size_t)a.n * C * L4);
     constexpr int G = MT * 4, PD = 4;
     f32x4 xa[PD][4];
     float su[16];
@@ -509,8 +476,8 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
       const int m = g >> 2, rb = (g & 3) * 4;
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        const int ch = 32 * m + ts_row32(rb + rr, half);
-        xa[slot][rr] = ts_load4(rx, ts_rowoff(ch < bc, ooff, ch * L4), 0);
+        const int ch = 32 * m + mfma_row32(rb + rr, half);
+        xa[slot][rr] = buf_load<4>(rx, buf_rowoff(ch < bc, ooff, ch * L4), 0);
       }
     };
 #pragma unroll
@@ -524,9 +491,9 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int r = rb + rr;
-        const int row = ts_row32(r, half);
+        const int row = mfma_row32(r, half);
         const int ch = 32 * m + row;
-        const f32x2s e = SB[ch];
+        const f32x2v e = SB[ch];
         float u0 = 0.f, u1 = 0.f;
         f32x4 d;
 #pragma unroll
@@ -538,7 +505,7 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
           u0 = fmaf(dv, x, u0);
           u1 += dv;
         }
-        ts_store4(d, ro, ts_rowoff(ch < bc, ooff, ch * L4));
+        ts_store4(d, ro, buf_rowoff(ch < bc, ooff, ch * L4));
         const bool ok = ch < bc && pok;
         Tw[row * 36 + l31] = ok ? u0 : 0.f;
         su[r] = ok ? u1 : 0.f;
@@ -550,12 +517,12 @@ __device__ __forceinline__ void ts_conv(const TSArgs& a, const TSBranch& br, boo
       }
       if ((g & 3) == 3) {
         wave_lds_sync();
-        float s0 = ts_rowread<float>(Tw, half, l31);
+        float s0 = tile36_rowsum<float>(Tw, half, l31);
         wave_lds_sync();
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Tw[ts_row32(r, half) * 36 + l31] = su[r];
+        for (int r = 0; r < 16; ++r) Tw[mfma_row32(r, half) * 36 + l31] = su[r];
         wave_lds_sync();
-        float s1 = ts_rowread<float>(Tw, half, l31);
+        float s1 = tile36_rowsum<float>(Tw, half, l31);
         wave_lds_sync();
         s0 += __shfl_xor(s0, 32, 64);
         s1 += __shfl_xor(s1, 32, 64);
@@ -1134,33 +1101,33 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
   const int LSd = tsw_ls(GM + TS_R), LSx = tsw_ls(XM + TS_R + 2 * TS_H);
   float* Ds = lds;                                                   // [CH][LSd]
   float* Xs = lds + CH * LSd;                                        // [CH][LSx]
-  f32x2s* SB = reinterpret_cast<f32x2s*>(Xs + CH * LSx);             // [CH] (scale, shift)
-  const f32x2s sb0 = (tid < CH && tid < bc) ? f32x2s{a.scale ? a.scale[br.c0 + tid] : 1.f, a.shift ? a.shift[br.c0 + tid] : 0.f}
-                                            : f32x2s{0.f, 0.f};
+  f32x2v* SB = reinterpret_cast<f32x2v*>(Xs + CH * LSx);             // [CH] (scale, shift)
+  const f32x2v sb0 = (tid < CH && tid < bc) ? f32x2v{a.scale ? a.scale[br.c0 + tid] : 1.f, a.shift ? a.shift[br.c0 + tid] : 0.f}
+                                            : f32x2v{0.f, 0.f};
   const int rel0 = br.c0;                          // ReLU on channels < n_act (per row: a group may straddle)
 
   const int units = a.n * (T / TS_R);
   const int per = (units + a.splits - 1) / a.splits;
   const int u0 = blockIdx.x * per, u1 = min(units, u0 + per);
 
-  const __amdgpu_buffer_rsrc_t rg = ts_rsrc(a.ge, (size_t)a.n * C * L * 4);
-  const __amdgpu_buffer_rsrc_t rz = ts_rsrc(a.z, (size_t)a.n * C * L * 4);
-  const __amdgpu_buffer_rsrc_t rga = ts_rsrc(a.doaug, (size_t)a.n * C * T * 4);
-  const __amdgpu_buffer_rsrc_t rza = ts_rsrc(a.zaug, (size_t)a.n * C * T * 4);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.ge, (size_t)a.n * C * L * 4);
+  const __amdgpu_buffer_rsrc_t rz = buf_rsrc(a.z, (size_t)a.n * C * L * 4);
+  const __amdgpu_buffer_rsrc_t rga = buf_rsrc(a.doaug, (size_t)a.n * C * T * 4);
+  const __amdgpu_buffer_rsrc_t rza = buf_rsrc(a.zaug, (size_t)a.n * C * T * 4);
   // staging slots: f = tid + 256*j -> (row, float4 column); fixed per thread
   int vD[JD], lD[JD], vX[JX], lX[JX];          // lX: LDS index | segment << 20 | row << 22 | valid << 28
 #pragma unroll
   for (int j = 0; j < JD; ++j) {
     const int f = tid + TS_NT * j, row = f / GS4, c4 = f - row * GS4;
     const bool ok = row < bc;
-    vD[j] = ok ? (row * L + 4 * c4) * 4 : TS_OOB;
+    vD[j] = ok ? (row * L + 4 * c4) * 4 : BUF_OOB;
     lD[j] = ok ? row * LSd + 4 * c4 : -1;
   }
 #pragma unroll
   for (int j = 0; j < JX; ++j) {
     const int f = tid + TS_NT * j, row = f / XS4, c4 = f - row * XS4;
     const bool ok = row < bc;
-    vX[j] = ok ? (row * L + 4 * c4) * 4 : TS_OOB;
+    vX[j] = ok ? (row * L + 4 * c4) * 4 : BUF_OOB;
     const int seg = c4 / SEG4;                  // 0 = halo before (needs bit 1 of `inval` clear), 1 = the unit, 2 = halo after (bit 2)
     lX[j] = (row * LSx + 4 * c4) | ((seg == 0 ? 1 : seg == 2 ? 2 : 0) << 20) | ((row & 63) << 22) | (ok ? 1 << 28 : 0);
   }
@@ -1179,18 +1146,18 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
     const int sx = ((n * C + br.c0) * L + (t0 - TS_H) * V) * 4;          // may be negative: only used with valid slots
     inval = (t0 >= TS_H ? 0 : 1) | (t0 + TS_R < T ? 0 : 2);
 #pragma unroll
-    for (int j = 0; j < JD; ++j) gr[j] = ts_load4(rg, vD[j], sg);
+    for (int j = 0; j < JD; ++j) gr[j] = buf_load<4>(rg, vD[j], sg);
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const bool ok = (((lX[j] >> 20) & 3) & inval) == 0;
-      xr[j] = ts_load4(rz, ok ? vX[j] + sx : TS_OOB, 0);
+      xr[j] = buf_load<4>(rz, ok ? vX[j] + sx : BUF_OOB);
     }
-    ga = ts_load4(rga, aokD ? ((n * C + br.c0 + tid) * T + t0) * 4 : TS_OOB, 0);
+    ga = buf_load<4>(rga, aokD ? ((n * C + br.c0 + tid) * T + t0) * 4 : BUF_OOB, 0);
     const bool oka = aokX & ((aneed & inval) == 0);
-    xa = ts_load4(rza, oka ? ((n * C + br.c0 + arow) * T + t0 + (aseg - 1) * TS_H) * 4 : TS_OOB, 0);
+    xa = buf_load<4>(rza, oka ? ((n * C + br.c0 + arow) * T + t0 + (aseg - 1) * TS_H) * 4 : BUF_OOB, 0);
   };
   const bool noact = a.exp & 128;
-  auto act = [&](float x, f32x2s sb, bool rl) -> float {
+  auto act = [&](float x, f32x2v sb, bool rl) -> float {
     if (noact) return x;
     const float y = fmaf(x, sb.x, sb.y);
     return rl ? fmaxf(y, 0.f) : y;
@@ -1199,9 +1166,9 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       if (lD[j] >= 0) {
-        f32x2s* d = reinterpret_cast<f32x2s*>(Ds + lD[j]);
-        d[0] = f32x2s{gr[j].x, gr[j].y};
-        d[1] = f32x2s{gr[j].z, gr[j].w};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Ds + lD[j]);
+        d[0] = f32x2v{gr[j].x, gr[j].y};
+        d[1] = f32x2v{gr[j].z, gr[j].w};
         dsum[j] += (gr[j].x + gr[j].y) + (gr[j].z + gr[j].w);
       }
     }
@@ -1210,26 +1177,26 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
       if (lX[j] & (1 << 28)) {
         const bool ok = (((lX[j] >> 20) & 3) & inval) == 0;
         const int row = (lX[j] >> 22) & 63;
-        const f32x2s sb = SB[row];
+        const f32x2v sb = SB[row];
         const bool rl = rel0 + row < a.n_act;
-        f32x2s* d = reinterpret_cast<f32x2s*>(Xs + (lX[j] & 0xfffff));
-        d[0] = ok ? f32x2s{act(xr[j].x, sb, rl), act(xr[j].y, sb, rl)} : f32x2s{0.f, 0.f};
-        d[1] = ok ? f32x2s{act(xr[j].z, sb, rl), act(xr[j].w, sb, rl)} : f32x2s{0.f, 0.f};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Xs + (lX[j] & 0xfffff));
+        d[0] = ok ? f32x2v{act(xr[j].x, sb, rl), act(xr[j].y, sb, rl)} : f32x2v{0.f, 0.f};
+        d[1] = ok ? f32x2v{act(xr[j].z, sb, rl), act(xr[j].w, sb, rl)} : f32x2v{0.f, 0.f};
       }
     }
     if (aokD) {
-      f32x2s* d = reinterpret_cast<f32x2s*>(Ds + tid * LSd + GM);
-      d[0] = f32x2s{ga.x, ga.y};
-      d[1] = f32x2s{ga.z, ga.w};
+      f32x2v* d = reinterpret_cast<f32x2v*>(Ds + tid * LSd + GM);
+      d[0] = f32x2v{ga.x, ga.y};
+      d[1] = f32x2v{ga.z, ga.w};
       dsa += (ga.x + ga.y) + (ga.z + ga.w);
     }
     if (aokX) {
       const bool ok = (aneed & inval) == 0;
-      const f32x2s sb = SB[arow];
+      const f32x2v sb = SB[arow];
       const bool rl = rel0 + arow < a.n_act;
-      f32x2s* d = reinterpret_cast<f32x2s*>(Xs + arow * LSx + XM + aseg * TS_H);
-      d[0] = ok ? f32x2s{act(xa.x, sb, rl), act(xa.y, sb, rl)} : f32x2s{0.f, 0.f};
-      d[1] = ok ? f32x2s{act(xa.z, sb, rl), act(xa.w, sb, rl)} : f32x2s{0.f, 0.f};
+      f32x2v* d = reinterpret_cast<f32x2v*>(Xs + arow * LSx + XM + aseg * TS_H);
+      d[0] = ok ? f32x2v{act(xa.x, sb, rl), act(xa.y, sb, rl)} : f32x2v{0.f, 0.f};
+      d[1] = ok ? f32x2v{act(xa.z, sb, rl), act(xa.w, sb, rl)} : f32x2v{0.f, 0.f};
     }
   };
 
@@ -1249,7 +1216,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
   const float* Bp = Xs + (32 * nt + l31) * LSx + TS_H * V + 2 * half;
   const float* Aq = Ds + (32 * mt + l31) * LSd + GM + 2 * half;
   const float* Bq = Xs + (32 * nt + l31) * LSx + XM + TS_H + 2 * half;
-  auto mm = [&](f32x2s av, f32x2s b0, f32x2s b1, f32x2s b2) {
+  auto mm = [&](f32x2v av, f32x2v b0, f32x2v b1, f32x2v b2) {
     acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc[0], 0, 0, 0);
     acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc[1], 0, 0, 0);
     acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b2.x, acc[2], 0, 0, 0);
@@ -1268,39 +1235,37 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
   TSW_STAMP();
   for (int u = u0; u < u1; ++u) {
     commit();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     TSW_STAMP();
     if (u + 1 < u1) issue(u + 1);
     TSW_STAMP();
     if (oddsh) {
 #pragma unroll 2
       for (int g = g0; g < g1; ++g) {
-        const f32x2s av = *reinterpret_cast<const f32x2s*>(Ap + 4 * g);
-        const f32x2s b1 = *reinterpret_cast<const f32x2s*>(Bp + 4 * g);
-        const f32x2s b0 = {Bp[4 * g - sh], Bp[4 * g - sh + 1]};
-        const f32x2s b2 = {Bp[4 * g + sh], Bp[4 * g + sh + 1]};
+        const f32x2v av = *reinterpret_cast<const f32x2v*>(Ap + 4 * g);
+        const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g);
+        const f32x2v b0 = {Bp[4 * g - sh], Bp[4 * g - sh + 1]};
+        const f32x2v b2 = {Bp[4 * g + sh], Bp[4 * g + sh + 1]};
         mm(av, b0, b1, b2);
       }
     } else {
 #pragma unroll 2
       for (int g = g0; g < g1; ++g) {
-        const f32x2s av = *reinterpret_cast<const f32x2s*>(Ap + 4 * g);
-        const f32x2s b0 = *reinterpret_cast<const f32x2s*>(Bp + 4 * g - sh);
-        const f32x2s b1 = *reinterpret_cast<const f32x2s*>(Bp + 4 * g);
-        const f32x2s b2 = *reinterpret_cast<const f32x2s*>(Bp + 4 * g + sh);
+        const f32x2v av = *reinterpret_cast<const f32x2v*>(Ap + 4 * g);
+        const f32x2v b0 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g - sh);
+        const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g);
+        const f32x2v b2 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g + sh);
         mm(av, b0, b1, b2);
       }
     }
     if (augw) {
-      const f32x2s av = *reinterpret_cast<const f32x2s*>(Aq);
-      const f32x2s b1 = *reinterpret_cast<const f32x2s*>(Bq);
-      const f32x2s b0 = {Bq[-ldil], Bq[1 - ldil]};
-      const f32x2s b2 = {Bq[ldil], Bq[1 + ldil]};
+      const f32x2v av = *reinterpret_cast<const f32x2v*>(Aq);
+      const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bq);
+      const f32x2v b0 = {Bq[-ldil], Bq[1 - ldil]};
+      const f32x2v b2 = {Bq[ldil], Bq[1 + ldil]};
       mm(av, b0, b1, b2);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                   // raw barrier: the next unit's loads stay in flight
+    block_lds_sync();                   // raw barrier: the next unit's loads stay in flight
     TSW_STAMP();
   }
 
@@ -1309,7 +1274,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
 #pragma unroll
     for (int k = 0; k < KT; ++k)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + ts_row32(r, half)) * 33 + l31] = acc[k][r];
+      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + mfma_row32(r, half)) * 33 + l31] = acc[k][r];
     __syncthreads();
     for (int w = 0, r0 = 0; w < gcnt; ++w) {         // the diagonal block of every window of the group
       const TSBranch& bw = ts_conv_window(a, gw0 + w);
@@ -1331,7 +1296,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw(TSArgs a, BnCo
     if (ci < bc) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = 32 * mt + ts_row32(r, half);
+        const int co = 32 * mt + mfma_row32(r, half);
         if (co < bc) {
 #pragma unroll
           for (int k = 0; k < KT; ++k) dw[((size_t)co * bc + ci) * KT + k] = acc[k][r];
@@ -1403,23 +1368,23 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
   const int LSd = tsw_ls(GM + TS_R);
   float* Ds = lds;                                                   // [CH][LSd]
   float* Xs = lds + CH * LSd;                                        // [3][CH][LSd]
-  f32x2s* SB = reinterpret_cast<f32x2s*>(Xs + 3 * CH * LSd);         // [CH] (scale, shift)
-  const f32x2s sb0 = (tid < CH && tid < bc) ? f32x2s{a.scale ? a.scale[br.c0 + tid] : 1.f, a.shift ? a.shift[br.c0 + tid] : 0.f}
-                                            : f32x2s{0.f, 0.f};
+  f32x2v* SB = reinterpret_cast<f32x2v*>(Xs + 3 * CH * LSd);         // [CH] (scale, shift)
+  const f32x2v sb0 = (tid < CH && tid < bc) ? f32x2v{a.scale ? a.scale[br.c0 + tid] : 1.f, a.shift ? a.shift[br.c0 + tid] : 0.f}
+                                            : f32x2v{0.f, 0.f};
   const int rel0 = br.c0;
   const int units = a.n * (To / TS_R);
   const int per = (units + a.splits - 1) / a.splits;
   const int u0 = blockIdx.x * per, u1 = min(units, u0 + per);
-  const __amdgpu_buffer_rsrc_t rg = ts_rsrc(a.ge, (size_t)a.n * C * Lo * 4);
-  const __amdgpu_buffer_rsrc_t rz = ts_rsrc(a.z, (size_t)a.n * C * Li * 4);
-  const __amdgpu_buffer_rsrc_t rga = ts_rsrc(a.doaug, (size_t)a.n * C * To * 4);
-  const __amdgpu_buffer_rsrc_t rza = ts_rsrc(a.zaug, (size_t)a.n * C * Ti * 4);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(a.ge, (size_t)a.n * C * Lo * 4);
+  const __amdgpu_buffer_rsrc_t rz = buf_rsrc(a.z, (size_t)a.n * C * Li * 4);
+  const __amdgpu_buffer_rsrc_t rga = buf_rsrc(a.doaug, (size_t)a.n * C * To * 4);
+  const __amdgpu_buffer_rsrc_t rza = buf_rsrc(a.zaug, (size_t)a.n * C * Ti * 4);
   int vD[JD], lD[JD];
 #pragma unroll
   for (int j = 0; j < JD; ++j) {
     const int f = tid + TS_NT * j, row = f / GS4, c4 = f - row * GS4;
     const bool ok = row < bc;
-    vD[j] = ok ? (row * Lo + 4 * c4) * 4 : TS_OOB;
+    vD[j] = ok ? (row * Lo + 4 * c4) * 4 : BUF_OOB;
     lD[j] = ok ? row * LSd + 4 * c4 : -1;
   }
   // h slots: f = tid + 256*j -> (row, tap, frame of the unit, 16-byte piece of the frame row)
@@ -1431,7 +1396,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
     const bool ok = row < bc;
     const int fo = 2 * fr + (tap - 1) * row_dil(row);               // source frame minus 2 * (first output frame of the unit)
     fX[j] = fo;
-    vX[j] = ok ? (row * Li + fo * V + 4 * q) * 4 : TS_OOB;
+    vX[j] = ok ? (row * Li + fo * V + 4 * q) * 4 : BUF_OOB;
     lX[j] = ((tap * CH + row) * LSd + fr * V + 4 * q) | (min(4, V - 4 * q) << 20) | ((row & 63) << 23) | (ok ? 1 << 29 : 0);
   }
   // the one-column operands: thread < CH: doaug of row tid (4 frames); slots tid + 256*j < CH*12: (row, tap, frame) of zaug
@@ -1443,7 +1408,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
     const bool ok = f < CH * 12 && row < bc;
     const int fo = 2 * fr + (tap - 1) * row_dil(row);
     fA[j] = fo;
-    vA[j] = ok ? (row * Ti + fo) * 4 : TS_OOB;
+    vA[j] = ok ? (row * Ti + fo) * 4 : BUF_OOB;
     lA[j] = ((tap * CH + row) * LSd + GM + fr) | ((row & 63) << 23) | (ok ? 1 << 29 : 0);
   }
   f32x4 gr[JD], xr[JX], ga;
@@ -1459,22 +1424,22 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
     const int sx = ((n * C + br.c0) * Li + t2 * V) * 4;
     const int sa = ((n * C + br.c0) * Ti + t2) * 4;
 #pragma unroll
-    for (int j = 0; j < JD; ++j) gr[j] = ts_load4(rg, vD[j], sg);
+    for (int j = 0; j < JD; ++j) gr[j] = buf_load<4>(rg, vD[j], sg);
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const int fr = t2 + fX[j];
       const bool ok = fr >= 0 && fr < Ti;
-      xr[j] = ts_load4(rz, ok ? vX[j] + sx : TS_OOB, 0);
+      xr[j] = buf_load<4>(rz, ok ? vX[j] + sx : BUF_OOB);
     }
-    ga = ts_load4(rga, aokD ? ((n * C + br.c0 + tid) * To + tp0) * 4 : TS_OOB, 0);
+    ga = buf_load<4>(rga, aokD ? ((n * C + br.c0 + tid) * To + tp0) * 4 : BUF_OOB, 0);
 #pragma unroll
     for (int j = 0; j < JA; ++j) {
       const int fr = t2 + fA[j];
       const bool ok = fr >= 0 && fr < Ti;
-      xa[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rza, ok ? vA[j] + sa : TS_OOB, 0, 0));
+      xa[j] = buf_load<1>(rza, ok ? vA[j] + sa : BUF_OOB);
     }
   };
-  auto act = [&](float x, f32x2s sb, bool rl) -> float {
+  auto act = [&](float x, f32x2v sb, bool rl) -> float {
     const float y = fmaf(x, sb.x, sb.y);
     return rl ? fmaxf(y, 0.f) : y;
   };
@@ -1482,9 +1447,9 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       if (lD[j] >= 0) {
-        f32x2s* d = reinterpret_cast<f32x2s*>(Ds + lD[j]);
-        d[0] = f32x2s{gr[j].x, gr[j].y};
-        d[1] = f32x2s{gr[j].z, gr[j].w};
+        f32x2v* d = reinterpret_cast<f32x2v*>(Ds + lD[j]);
+        d[0] = f32x2v{gr[j].x, gr[j].y};
+        d[1] = f32x2v{gr[j].z, gr[j].w};
         dsum[j] += (gr[j].x + gr[j].y) + (gr[j].z + gr[j].w);
       }
     }
@@ -1494,7 +1459,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
         const int fr = t2 + fX[j];
         const bool ok = fr >= 0 && fr < Ti;
         const int row = (lX[j] >> 23) & 63, cnt = (lX[j] >> 20) & 7;
-        const f32x2s sb = SB[row];
+        const f32x2v sb = SB[row];
         const bool rl = rel0 + row < a.n_act;
         float* d = Xs + (lX[j] & 0xfffff);
 #pragma unroll
@@ -1503,9 +1468,9 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
       }
     }
     if (aokD) {
-      f32x2s* d = reinterpret_cast<f32x2s*>(Ds + tid * LSd + GM);
-      d[0] = f32x2s{ga.x, ga.y};
-      d[1] = f32x2s{ga.z, ga.w};
+      f32x2v* d = reinterpret_cast<f32x2v*>(Ds + tid * LSd + GM);
+      d[0] = f32x2v{ga.x, ga.y};
+      d[1] = f32x2v{ga.z, ga.w};
       dsa += (ga.x + ga.y) + (ga.z + ga.w);
     }
 #pragma unroll
@@ -1537,15 +1502,14 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
   __syncthreads();
   for (int u = u0; u < u1; ++u) {
     commit();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     if (u + 1 < u1) issue(u + 1);
 #pragma unroll 2
     for (int g = g0; g < g1; ++g) {
-      const f32x2s av = *reinterpret_cast<const f32x2s*>(Ap + 4 * g);
-      const f32x2s b0 = *reinterpret_cast<const f32x2s*>(Bp + 4 * g);
-      const f32x2s b1 = *reinterpret_cast<const f32x2s*>(Bp + CH * LSd + 4 * g);
-      const f32x2s b2 = *reinterpret_cast<const f32x2s*>(Bp + 2 * CH * LSd + 4 * g);
+      const f32x2v av = *reinterpret_cast<const f32x2v*>(Ap + 4 * g);
+      const f32x2v b0 = *reinterpret_cast<const f32x2v*>(Bp + 4 * g);
+      const f32x2v b1 = *reinterpret_cast<const f32x2v*>(Bp + CH * LSd + 4 * g);
+      const f32x2v b2 = *reinterpret_cast<const f32x2v*>(Bp + 2 * CH * LSd + 4 * g);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b2.x, acc[2], 0, 0, 0);
@@ -1553,15 +1517,14 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc[1], 0, 0, 0);
       acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b2.y, acc[2], 0, 0, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
   }
   if (CH == 32) {
     float* Rs = lds;                                 // [wave][tap][co][33]
 #pragma unroll
     for (int k = 0; k < KT; ++k)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + ts_row32(r, half)) * 33 + l31] = acc[k][r];
+      for (int r = 0; r < 16; ++r) Rs[((wave * KT + k) * 32 + mfma_row32(r, half)) * 33 + l31] = acc[k][r];
     __syncthreads();
     for (int w = 0, r0 = 0; w < gcnt; ++w) {
       const TSBranch& bw = ts_conv_window(a, gw0 + w);
@@ -1583,7 +1546,7 @@ __global__ __launch_bounds__(TS_NT, CH == 32 ? 2 : 1) void k_tspw2(TSArgs a, BnC
     if (ci < bc) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = 32 * mt + ts_row32(r, half);
+        const int co = 32 * mt + mfma_row32(r, half);
         if (co < bc) {
 #pragma unroll
           for (int k = 0; k < KT; ++k) dw[((size_t)co * bc + ci) * KT + k] = acc[k][r];

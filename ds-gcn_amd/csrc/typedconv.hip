@@ -30,8 +30,6 @@ constexpr int TC_XS = TC_NS * TC_TILE + 32;    // LDS row of the gathered column
 constexpr int TC_WS = TC_KC + 2;               // LDS row of the weights: 34 l mod 64 is distinct and even for l < 32
 constexpr int TC_OFF = 17;                     // tile_off entries in front of tile_type (P <= 16)
 
-__device__ __forceinline__ int tc_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 // x (n, K, TV), W (P, M, K) [TRANS: (P, K, M)], b (P, M) or NULL -> y (n, M, TV)
 template <int TRANS>
 __global__ __launch_bounds__(256) void k_typedconv(const float* __restrict__ x, const float* __restrict__ W,
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(256) void k_typedconv(const float* __restrict__ x, 
   float bias[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = m0 + 32 * wave + tc_row32(r, half);
+    const int m = m0 + 32 * wave + mfma_row32(r, half);
     bias[r] = (b && m < M) ? b[(size_t)p * M + m] : 0.f;
   }
 #pragma unroll
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(256) void k_typedconv(const float* __restrict__ x, 
     float* __restrict__ ycol = y + ((size_t)(n0 + s) * M) * TV + base + op;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * wave + tc_row32(r, half);
+      const int m = m0 + 32 * wave + mfma_row32(r, half);
       if (m < M) ycol[(size_t)m * TV] = acc[s][r] + bias[r];
     }
   }
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(256) void k_typedconv_wgrad(const float* __restrict
   float* __restrict__ row = part + (size_t)blockIdx.z * pstride;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int co = co0 + 32 * wm + tc_row32(r, half);
+    const int co = co0 + 32 * wm + mfma_row32(r, half);
     if (co >= Co) continue;
     if (ci < Ci) row[((size_t)p * Co + co) * Ci + ci] = acc[r];
     else row[(size_t)P * Co * Ci + (size_t)p * Co + co] = acc[r];

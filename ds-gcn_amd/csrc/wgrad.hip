@@ -15,7 +15,6 @@
 namespace {
 
 constexpr int WG_NT = 256;
-constexpr int WG_OOB = 0x7ffffff0;
 
 struct Wg2Args {
   const float* x1; const float* s1; const float* h1;
@@ -30,16 +29,6 @@ struct Wg2Args {
   int ngroup;
   struct Grp { const float* x1; const float* s1; const float* h1; const float* gz; float* dwp; float* dbp; } g[3];
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 wg_load(__amdgpu_buffer_rsrc_t r, int voff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-__device__ __forceinline__ int wg_row32(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // What every weight-gradient kernel does before its body, on the kernel's OWN argument (the job table and the group
 // records are indexed at run time: read straight from the kernel-argument segment here, they never become a private copy):
@@ -75,7 +64,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
   constexpr int TF = B3 ? 3 * (TM + TN) * RB / 4 : (TM + TN) * LS;   // floats of tile storage
   char* Db = reinterpret_cast<char*>(lds);        // B3: [3][TM][RB] dz_eff terms
   char* Xb = Db + 3 * TM * RB;                    // B3: [3][TN][RB] virtual-input terms
-  f32x2* Cs = reinterpret_cast<f32x2*>(lds + TF);          // [TM] (A0, B0)
+  f32x2v* Cs = reinterpret_cast<f32x2v*>(lds + TF);          // [TM] (A0, B0)
   f32x4* Ps = reinterpret_cast<f32x4*>(lds + TF + 2 * TM);  // [TN] (s1, h1, s2, h2)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,7 +89,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
 
   for (int i = tid; i < TM; i += WG_NT) {
     const int co = coBase + i;
-    Cs[i] = (HASC && co < Co) ? f32x2{a.A0[co], a.B0[co]} : f32x2{0.f, 0.f};
+    Cs[i] = (HASC && co < Co) ? f32x2v{a.A0[co], a.B0[co]} : f32x2v{0.f, 0.f};
   }
   for (int i = tid; i < TN; i += WG_NT) {
     const int ci = ciBase + i;
@@ -123,23 +112,23 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
     const int n = ch / a.cpn;
     const int c0 = (ch - n * a.cpn) * KC;
     const bool pv = c0 + col < L;
-    const __amdgpu_buffer_rsrc_t rg = wg_rsrc((a.gz ? a.gz : a.x1) + (size_t)(a.gz ? n : 0) * Co * L, a.gz ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rz = wg_rsrc((HASC ? a.z : a.x1) + (size_t)(HASC ? n : 0) * Co * L, HASC ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rx = wg_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
-    const __amdgpu_buffer_rsrc_t ry = wg_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc((a.gz ? a.gz : a.x1) + (size_t)(a.gz ? n : 0) * Co * L, a.gz ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rz = buf_rsrc((HASC ? a.z : a.x1) + (size_t)(HASC ? n : 0) * Co * L, HASC ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, Ci * L4);
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       const int co = coBase + rowD0 + RSTEP * j;
-      const int voff = (pv && co < Co) ? (co * L + c0 + col) * 4 : WG_OOB;
-      gr[j] = wg_load(rg, voff);
-      if constexpr (HASC) zr[j] = wg_load(rz, voff);
+      const int voff = (pv && co < Co) ? (co * L + c0 + col) * 4 : BUF_OOB;
+      gr[j] = buf_load<4>(rg, voff);
+      if constexpr (HASC) zr[j] = buf_load<4>(rz, voff);
     }
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const int ci = ciBase + rowX0 + RSTEP * j;
-      const int voff = (pv && ci < Ci) ? (ci * L + c0 + col) * 4 : WG_OOB;
-      xr[j] = wg_load(rx, voff);
-      if constexpr (HAS2) yr[j] = wg_load(ry, voff);
+      const int voff = (pv && ci < Ci) ? (ci * L + c0 + col) * 4 : BUF_OOB;
+      xr[j] = buf_load<4>(rx, voff);
+      if constexpr (HAS2) yr[j] = buf_load<4>(ry, voff);
     }
   };
 
@@ -158,7 +147,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
       const bool ok = pv && coBase + row < Co;
       f32x4 d = gr[j];
       if constexpr (HASC) {
-        const f32x2 c = Cs[row];
+        const f32x2v c = Cs[row];
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] += fmaf(c.y, zr[j][e], c.x);
       }
@@ -175,9 +164,9 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
         *reinterpret_cast<u32x2v*>(dst + TM * RB) = u32x2v{p1, q1};
         if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(dst + 2 * TM * RB) = u32x2v{p2, q2};
       } else {
-        f32x2* dst = reinterpret_cast<f32x2*>(Ds + row * LS + col);
-        dst[0] = f32x2{d.x, d.y};
-        dst[1] = f32x2{d.z, d.w};
+        f32x2v* dst = reinterpret_cast<f32x2v*>(Ds + row * LS + col);
+        dst[0] = f32x2v{d.x, d.y};
+        dst[1] = f32x2v{d.z, d.w};
       }
     }
 #pragma unroll
@@ -201,9 +190,9 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
         *reinterpret_cast<u32x2v*>(dst + TN * RB) = u32x2v{p1, q1};
         if constexpr (NT == 3) *reinterpret_cast<u32x2v*>(dst + 2 * TN * RB) = u32x2v{p2, q2};
       } else {
-        f32x2* dst = reinterpret_cast<f32x2*>(Xs + row * LS + col);
-        dst[0] = f32x2{v.x, v.y};
-        dst[1] = f32x2{v.z, v.w};
+        f32x2v* dst = reinterpret_cast<f32x2v*>(Xs + row * LS + col);
+        dst[0] = f32x2v{v.x, v.y};
+        dst[1] = f32x2v{v.z, v.w};
       }
     }
   };
@@ -224,8 +213,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
   issue(ch0);
   for (int ch = ch0; ch < ch1; ++ch) {
     commit(ch);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    block_lds_sync();
     if (ch + 1 < ch1) issue(ch + 1);
     if constexpr (B3) {
       const char* Ab = Db + (m0 + l31) * RB + 16 * half;
@@ -250,11 +238,11 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
     } else {
 #pragma unroll
     for (int w = 0; w < Q; ++w) {
-      f32x2 av[MI], bv[NI];
+      f32x2v av[MI], bv[NI];
 #pragma unroll
-      for (int mi = 0; mi < MI; ++mi) av[mi] = *reinterpret_cast<const f32x2*>(Ap + 32 * mi * LS + 4 * w);
+      for (int mi = 0; mi < MI; ++mi) av[mi] = *reinterpret_cast<const f32x2v*>(Ap + 32 * mi * LS + 4 * w);
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) bv[ni] = *reinterpret_cast<const f32x2*>(Bp + 32 * ni * LS + 4 * w);
+      for (int ni = 0; ni < NI; ++ni) bv[ni] = *reinterpret_cast<const f32x2v*>(Bp + 32 * ni * LS + 4 * w);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -264,8 +252,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
         }
     }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                 // raw barrier: the next chunk's loads stay in flight
+    block_lds_sync();                 // raw barrier: the next chunk's loads stay in flight
   }
 
   // D[i = co][j = ci] -> partial dW of this split
@@ -277,7 +264,7 @@ __device__ __forceinline__ void wg2_body(const Wg2Args& a, float* lds) {
       const int ci = ciBase + n0 + 32 * ni + l31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = coBase + m0 + 32 * mi + wg_row32(r, half);
+        const int co = coBase + m0 + 32 * mi + mfma_row32(r, half);
         if (co < Co && ci < Ci) dw[(size_t)co * Ci + ci] = acc[mi][ni][r];
       }
     }
@@ -327,7 +314,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
   constexpr int DEPTH = (HAS2 && HASC && TM == 256 && TN == 256) ? 1 : 2;
   char* B0p = reinterpret_cast<char*>(lds);                        // buffer: [3][TM][RB] dz_eff terms, [3][TN][RB] input terms
   char* B1p = B0p + BUF;
-  f32x2* Cs = reinterpret_cast<f32x2*>(B1p + BUF);                 // [TM] (A0, B0)
+  f32x2v* Cs = reinterpret_cast<f32x2v*>(B1p + BUF);                 // [TM] (A0, B0)
   f32x4* Ps = reinterpret_cast<f32x4*>(Cs + TM);                   // [TN] (s1, h1, s2, h2)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -350,7 +337,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
   const int L4 = L * 4;
   for (int i = tid; i < TM; i += W3_NT) {
     const int co = coBase + i;
-    Cs[i] = (HASC && co < Co) ? f32x2{a.A0[co], a.B0[co]} : f32x2{0.f, 0.f};
+    Cs[i] = (HASC && co < Co) ? f32x2v{a.A0[co], a.B0[co]} : f32x2v{0.f, 0.f};
   }
   for (int i = tid; i < TN; i += W3_NT) {
     const int ci = ciBase + i;
@@ -371,25 +358,25 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
     const int n = ch / a.cpn;
     const int c0 = (ch - n * a.cpn) * W3_KC;
     const bool pv = (ch < ch1) & (c0 + col < L);
-    const __amdgpu_buffer_rsrc_t rg = wg_rsrc((a.gz ? a.gz : a.x1) + (size_t)(a.gz ? n : 0) * Co * L, a.gz ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rz = wg_rsrc((HASC ? a.z : a.x1) + (size_t)(HASC ? n : 0) * Co * L, HASC ? Co * L4 : 0);
-    const __amdgpu_buffer_rsrc_t rx = wg_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
-    const __amdgpu_buffer_rsrc_t ry = wg_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc((a.gz ? a.gz : a.x1) + (size_t)(a.gz ? n : 0) * Co * L, a.gz ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rz = buf_rsrc((HASC ? a.z : a.x1) + (size_t)(HASC ? n : 0) * Co * L, HASC ? Co * L4 : 0);
+    const __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x1 + (size_t)n * Ci * L, Ci * L4);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc((HAS2 ? a.x2 : a.x1) + (size_t)n * Ci * L, Ci * L4);
 #pragma unroll
     for (int j = 0; j < JD; ++j) {
       const int co = coBase + row0 + 128 * j;
       const bool ok = pv & (co < Co);              // (bitwise: a short-circuit turns the load into a branch + vmcnt(0))
-      const int voff = ok ? (co * L + c0 + col) * 4 : WG_OOB;
-      r.g[j] = wg_load(rg, voff);
-      if constexpr (HASC) r.z[j] = wg_load(rz, voff);
+      const int voff = ok ? (co * L + c0 + col) * 4 : BUF_OOB;
+      r.g[j] = buf_load<4>(rg, voff);
+      if constexpr (HASC) r.z[j] = buf_load<4>(rz, voff);
     }
 #pragma unroll
     for (int j = 0; j < JX; ++j) {
       const int ci = ciBase + row0 + 128 * j;
       const bool ok = pv & (ci < Ci);
-      const int voff = ok ? (ci * L + c0 + col) * 4 : WG_OOB;
-      r.x[j] = wg_load(rx, voff);
-      if constexpr (HAS2) r.y[j] = wg_load(ry, voff);
+      const int voff = ok ? (ci * L + c0 + col) * 4 : BUF_OOB;
+      r.x[j] = buf_load<4>(rx, voff);
+      if constexpr (HAS2) r.y[j] = buf_load<4>(ry, voff);
     }
   };
   float dsum[JD];
@@ -410,7 +397,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
       const bool ok = pv & (coBase + row < Co);
       f32x4 d = r.g[j];
       if constexpr (HASC) {
-        const f32x2 c = Cs[row];
+        const f32x2v c = Cs[row];
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] += fmaf(c.y, r.z[j][e], c.x);
       }
@@ -465,8 +452,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
   __builtin_amdgcn_sched_barrier(0);
   issue(ch0 + DEPTH, RA);
   __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  block_lds_sync();
 
   // one chunk: its 16 positions' products on `cur` with chunk ch+1's split (register set r) written to `nxt` in between
   auto step = [&](int ch, const char* cur, char* nxt, Regs& r) {
@@ -499,8 +485,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
     __builtin_amdgcn_sched_barrier(0);
     issue(ch + 1 + DEPTH, r);                      // this set is free again
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                  // raw barrier: the loads in flight stay in flight
+    block_lds_sync();                  // raw barrier: the loads in flight stay in flight
   };
   if constexpr (DEPTH == 2) {
     // (pairs in the loop, an odd last chunk outside it: a conditional second call would make the compiler allow a
@@ -529,7 +514,7 @@ __device__ __forceinline__ void wg3_body(const Wg2Args& a, float* lds) {
       const int ci = ciBase + n0 + 32 * ni + l31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = coBase + m0 + 32 * mi + wg_row32(r, half);
+        const int co = coBase + m0 + 32 * mi + mfma_row32(r, half);
         if (co < Co && ci < Ci) dw[(size_t)co * Ci + ci] = acc[mi][ni][r];
       }
     }
