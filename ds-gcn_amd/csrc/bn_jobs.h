@@ -1,5 +1,5 @@
 // Train-mode BatchNorm's two micro-reductions as JOBS: a job is what one k_bn_finalize / k_bn_coef_rows launch did
-// (pwconv.hip, same arithmetic, same fixed summation order: results are bit-identical to the single launches); a launch
+// (reduce.hip, same arithmetic, same fixed summation order: results are bit-identical to the single launches); a launch
 // takes a small table of them in its kernel arguments.  Two uses (round 6):
 //   * k_bn_finalize_multi / k_bn_coef_rows_multi: the jobs of INDEPENDENT producers in one launch (`post` + `down`;
 //     transform + block-residual conv — gcn.py:2142-2167,2215, tcn.py:389-404: the reference's nn.BatchNorm2d calls);
@@ -172,7 +172,7 @@ inline int bnj_total_blocks(const TABLE& t) {
   return nb;
 }
 
-// host-side argument checks shared by the entry points (pwconv.hip, dynadj.hip)
+// host-side argument checks shared by the entry points (reduce.hip, pwconv.hip, dynadj.hip)
 inline bool bnj_fin_ok(const BnFinTable& t) {
   if (t.n < 0 || t.n > BNJ_MAX) return false;
   for (int i = 0; i < t.n; ++i) {
@@ -191,3 +191,7 @@ inline bool bnj_coef_ok(const BnCoefTable& t) {
   }
   return true;
 }
+
+// reduce.hip: the jobs of a table as a launch of their own (k_bn_coef_rows_multi) — for a caller in another file whose own
+// launch cannot host them (dsgcn_pwconv_wgrad_jobs on a first-generation kernel).  0, or the launch's hipError_t.
+__attribute__((visibility("hidden"))) int bnj_coef_launch(const BnCoefTable& t, hipStream_t st);

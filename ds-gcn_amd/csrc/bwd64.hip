@@ -592,33 +592,29 @@ bool bf_plan(int n, int Ci, int Co, int L, BfPlan* p) {
 
 }  // namespace
 
-// Internal (hidden): partial rows of the fused backward for this shape, 0 = not eligible.
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_splits(int n, int Ci, int Co, int L) {
+// Internal (hidden, kc.h): partial rows of the fused backward for this shape, 0 = not eligible.
+int dsgcn_bwd64_splits(int n, int Ci, int Co, int L) {
   BfPlan p;
   return bf_plan(n, Ci, Co, L, &p) ? p.splits : 0;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const float* s1, const float* h1, const float* x2,
-                                                       const float* s2, const float* h2, int relu, const float* w,
-                                                       const float* z, const float* gz, const float* A0, const float* B0,
-                                                       float* dx, float* dx2, float* dwp, float* dbp, int pstride,
-                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                       const dsgcn_guest_conv* guest, int* hosted) {
+int dsgcn_bwd64(const KcIn& in, const float* w, const KcDz& d, float* dx, float* dx2, float* dwp, float* dbp, int pstride,
+                float* ipart, int n, int Ci, int Co, int L, hipStream_t st, const dsgcn_guest_conv* guest, int* hosted) {
   BfPlan p;
   if (hosted) *hosted = 0;
   if (!bf_plan(n, Ci, Co, L, &p)) return 0;
   BfArgs a = {};
-  a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu; a.w = w; a.z = z; a.gz = gz;
-  a.A0 = A0; a.B0 = B0; a.dx = dx; a.dx2 = dx2; a.dwp = dwp; a.dbp = dbp; a.ipart = ipart; a.pstride = pstride;
+  a.x1 = in.x1; a.s1 = in.s1; a.h1 = in.h1; a.x2 = in.x2; a.s2 = in.s2; a.h2 = in.h2; a.relu = in.relu; a.w = w;
+  a.z = d.z; a.gz = d.gz; a.A0 = d.A0; a.B0 = d.B0; a.dx = dx; a.dx2 = dx2; a.dwp = dwp; a.dbp = dbp; a.ipart = ipart; a.pstride = pstride;
   a.n = n; a.Ci = Ci; a.Co = Co; a.L = L; a.cpn = p.cpn; a.total_chunks = p.chunks; a.cps = p.cps;
-  const bool b3 = g_bf_b3 && x2 == nullptr && Ci >= 16;
+  const bool b3 = g_bf_b3 && in.x2 == nullptr && Ci >= 16;
   if (b3) {                                           // 32-position units over the same splits (a split with none writes zero rows)
     a.cpn = (L + 31) / 32;
     a.total_chunks = n * a.cpn;
     a.cps = (a.total_chunks + p.splits - 1) / p.splits;
   }
   const size_t lds = b3 ? (size_t)BB_LDS : (size_t)(192 * BF_LS + 64 * 65 + 2 * 64 + 4 * 64) * sizeof(float);
-  const bool hasc = A0 != nullptr, has2 = x2 != nullptr, aff = s1 != nullptr || s2 != nullptr || relu != 0 || has2;
+  const bool hasc = d.A0 != nullptr, has2 = in.x2 != nullptr, aff = in.s1 != nullptr || in.s2 != nullptr || in.relu != 0 || has2;
   // a guest (the projections' data gradient) rides in the leading workgroups of the two hosting instantiations; its body
   // needs less LDS than either form of this pass
   P4Hosted hg;
@@ -683,17 +679,17 @@ __attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const flo
 }
 
 // 1 = the one-pass backward of a plain-input (Ci -> Co) conv with batch-statistics terms hosts `guest`
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_hosts(int n, int Ci, int Co, int L, const dsgcn_guest_conv* guest) {
+int dsgcn_bwd64_hosts(int n, int Ci, int Co, int L, const dsgcn_guest_conv* guest) {
   BfPlan p;
   P4Hosted hg;
   return (guest && bf_plan(n, Ci, Co, L, &p) && dsgcn_p4_guest_plan(guest, 1, &hg)) ? 1 : 0;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_tuning(int value) { g_bf_b3 = value; return 0; }
+int dsgcn_bwd64_tuning(int value) { g_bf_b3 = value; return 0; }
 
 // bf16 products per fp32 product of the one-pass backward of a single-stream conv of this shape: k_bwd64b stays on six
 // terms at every matmul precision level (it runs at the copy rate: nothing to buy); 0 = its fp32 MFMA form
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_terms(int n, int Ci, int Co, int L) {
+int dsgcn_bwd64_terms(int n, int Ci, int Co, int L) {
   BfPlan p;
   return (bf_plan(n, Ci, Co, L, &p) && g_bf_b3 && Ci >= 16) ? 6 : 0;
 }

@@ -841,13 +841,13 @@ bool p4_hosts_guest(const P4Plan& p, int epi, int mode, int M, bool have_ws) {
 
 }  // namespace
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_guest_plan(const dsgcn_guest_conv* g, int epi, P4Hosted* h) {
+int dsgcn_p4_guest_plan(const dsgcn_guest_conv* g, int epi, P4Hosted* h) {
   return (g && p4_guest_plan(*g, epi, h)) ? 1 : 0;
 }
 
-// Internal (not part of the C ABI): called by dsgcn_pwconv_fwd / dsgcn_pwconv_dgrad when the shape qualifies
+// Internal (not part of the C ABI; declared hidden in kc.h): called by pwconv.hip's dispatch when the shape qualifies
 // (stride 1, even plane size).  Return 1 = launched, 0 = not eligible, <0 / >0 = error codes as everywhere.
-__attribute__((visibility("hidden"))) int dsgcn_p4_tuning(int key, int value) {
+int dsgcn_p4_tuning(int key, int value) {
   if (key == 0) g_p4_nq = value;
   else if (key == 1) g_p4_mt = value;
   else if (key == 2) g_p4_pd = value;
@@ -865,32 +865,29 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_tuning(int key, int value) {
 // bf16 products per fp32 product of the forward (epi 0: K = Ci, M = Co) / data gradient (epi 1: K = Co, M = Ci) launch of
 // this shape under the current precision level, the weight image supplied wherever dsgcn_p4_ws_bytes asks for one:
 // 6 / 3 = k_pwg3 / k_pwg3h (k_pwg without the fragment-order image: always 6), 0 = an fp32 MFMA form
-__attribute__((visibility("hidden"))) int dsgcn_p4_terms(int n, int K, int M, int L, int epi) {
+int dsgcn_p4_terms(int n, int K, int M, int L, int epi) {
   P4Plan p;
   if (!p4_plan(n, K, M, L, &p, epi) || !p.gemm) return 0;
   return (g_p4_ws == 2 && dsgcn_precision_level() == 1) ? 3 : 6;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_groups(int n, int K, int M, int L, int epi) {
+int dsgcn_p4_groups(int n, int K, int M, int L, int epi) {
   P4Plan p;
   return p4_plan(n, K, M, L, &p, epi) ? p.ngrp : 0;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const float* s1, const float* h1,
-                                                        const float* x2, const float* s2, const float* h2, int relu,
-                                                        const float* w, const float* bias, float* z, float* partial,
-                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws,
-                                                        const dsgcn_guest_conv* guest, int* hosted) {
+int dsgcn_p4_fwd(const KcIn& in, const float* w, const float* bias, float* z, float* partial, int n, int Ci, int Co, int L,
+                 hipStream_t st, const void* ws, const dsgcn_guest_conv* guest, int* hosted) {
   P4Plan p;
   if (hosted) *hosted = 0;
   if (!p4_plan(n, Ci, Co, L, &p)) return 0;
   const WsDims wd = ws_dims(Ci, Co);
   const unsigned short* wsp = static_cast<const unsigned short*>(ws);
   Pw4Args a = {};
-  a.b1 = x1; a.b2 = x2; a.ps1 = s1; a.ph1 = h1; a.ps2 = s2; a.ph2 = h2; a.relu = relu;
+  a.b1 = in.x1; a.b2 = in.x2; a.ps1 = in.s1; a.ph1 = in.h1; a.ps2 = in.s2; a.ph2 = in.h2; a.relu = in.relu;
   a.w = w; a.w_ldm = Ci; a.w_ldk = 1; a.bias = bias; a.out = z; a.partial = partial;
   a.n = n; a.K = Ci; a.M = Co; a.L = L; a.span = p.span; a.WT = p.WT; a.cc = p.cc; a.Kpad = p.Kpad; a.Lq = p.Lq;
-  const int mode = x2 ? 2 : ((s1 || relu) ? 1 : 0);
+  const int mode = in.x2 ? 2 : ((in.s1 || in.relu) ? 1 : 0);
   if (p.ksp && !p.gemm && mode == 0 && !partial) {
     hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 0, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a, P4NoGuest{});
     DSGCN_LAUNCH_CHECK();
@@ -912,8 +909,7 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const fl
 
 // 1 = the forward of a plain-operand (Ci -> Co) conv over n planes of L positions hosts `guest` (have_ws: the caller passes
 // the pre-split weight image the shape asks for)
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_hosts(int n, int Ci, int Co, int L, int have_ws,
-                                                              const dsgcn_guest_conv* guest) {
+int dsgcn_p4_fwd_hosts(int n, int Ci, int Co, int L, int have_ws, const dsgcn_guest_conv* guest) {
   P4Plan p;
   P4Hosted hg;
   if (!guest || !p4_plan(n, Ci, Co, L, &p)) return 0;
@@ -921,25 +917,21 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_fwd_hosts(int n, int Ci, int 
   return (p4_hosts_guest(p, 0, 0, Co, have_ws != 0) && p4_guest_plan(*guest, 0, &hg)) ? 1 : 0;
 }
 
-// dz_eff = gz + A0 + B0*z (either part may be absent);  x1/x2/s*/h*/relu describe the forward's virtual input.
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const float* s1, const float* h1,
-                                                          const float* x2, const float* s2, const float* h2, int relu,
-                                                          const float* w, const float* z, const float* gz,
-                                                          const float* A0, const float* B0, float* dx1, float* dx2,
-                                                          float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                          const void* ws, const dsgcn_guest_conv* guest, int* hosted) {
+// d: dz_eff = gz + A0 + B0*z (either part may be absent);  in: the forward's virtual input.
+int dsgcn_p4_dgrad(const KcIn& in, const float* w, const KcDz& d, float* dx1, float* dx2, float* ipart, int n, int Ci, int Co,
+                   int L, hipStream_t st, const void* ws, const dsgcn_guest_conv* guest, int* hosted) {
   P4Plan p;
   if (hosted) *hosted = 0;
-  if (!gz) return 0;                               // (a conv whose output has no direct gradient: not on the fast path)
+  if (!d.gz) return 0;                             // (a conv whose output has no direct gradient: not on the fast path)
   if (!p4_plan(n, Co, Ci, L, &p, 1)) return 0;
   Pw4Args a = {};
-  a.b1 = gz; a.b2 = A0 ? z : nullptr;
-  a.ps1 = nullptr; a.ph1 = A0; a.ps2 = B0; a.ph2 = nullptr; a.relu = 0;
+  a.b1 = d.gz; a.b2 = d.A0 ? d.z : nullptr;
+  a.ps1 = nullptr; a.ph1 = d.A0; a.ps2 = d.B0; a.ph2 = nullptr; a.relu = 0;
   a.w = w; a.w_ldm = 1; a.w_ldk = Ci; a.bias = nullptr; a.out = dx1; a.partial = nullptr;
-  a.ex1 = x1; a.ex2 = x2; a.es1 = s1; a.eh1 = h1; a.es2 = s2; a.eh2 = h2; a.erelu = relu;
+  a.ex1 = in.x1; a.ex2 = in.x2; a.es1 = in.s1; a.eh1 = in.h1; a.es2 = in.s2; a.eh2 = in.h2; a.erelu = in.relu;
   a.out2 = dx2; a.ipart = ipart;
   a.n = n; a.K = Co; a.M = Ci; a.L = L; a.span = p.span; a.WT = p.WT; a.cc = p.cc; a.Kpad = p.Kpad; a.Lq = p.Lq;
-  const int mode = A0 ? 2 : 0;
+  const int mode = d.A0 ? 2 : 0;
   if (p.ksp && !p.gemm && mode == 0 && !ipart) {
     hipLaunchKernelGGL((k_pw4<1, 2, 0, 16, 1, true>), dim3((unsigned)((p.WT + 7) / 8 * 8 * p.cc)), dim3(P4_NT), p.lds, st, a, P4NoGuest{});
     DSGCN_LAUNCH_CHECK();
@@ -961,8 +953,7 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const 
 }
 
 // 1 = the data gradient of a (Ci -> Co) conv with batch-statistics terms (A0 / B0) hosts `guest`
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_hosts(int n, int Ci, int Co, int L, int have_ws,
-                                                                const dsgcn_guest_conv* guest) {
+int dsgcn_p4_dgrad_hosts(int n, int Ci, int Co, int L, int have_ws, const dsgcn_guest_conv* guest) {
   P4Plan p;
   P4Hosted hg;
   if (!guest || !p4_plan(n, Co, Ci, L, &p, 1)) return 0;
@@ -971,15 +962,13 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_hosts(int n, int Ci, in
 
 // Up to three convs of one shape in ONE launch (k_pw4 only: plain / affine operand, no second stream, no statistics).
 // Return 1 = launched, 0 = not eligible (the caller launches them one by one).
-__attribute__((visibility("hidden"))) int dsgcn_p4_group_ok(int n, int Ci, int Co, int L) {
+int dsgcn_p4_group_ok(int n, int Ci, int Co, int L) {
   P4Plan pf, pb;
   return (p4_plan(n, Ci, Co, L, &pf, 0) && !pf.gemm && p4_plan(n, Co, Ci, L, &pb, 1) && !pb.gemm) ? 1 : 0;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_group(const float* const* x1, const float* const* s1,
-                                                              const float* const* h1, int relu, const float* const* w,
-                                                              float* const* z, int ng, int n, int Ci, int Co, int L,
-                                                              hipStream_t st) {
+int dsgcn_p4_fwd_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
+                       const float* const* w, float* const* z, int ng, int n, int Ci, int Co, int L, hipStream_t st) {
   P4Plan p;
   if (ng < 1 || ng > 3 || !p4_plan(n, Ci, Co, L, &p) || p.gemm) return 0;
   Pw4Args a = {};
@@ -998,10 +987,9 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_fwd_group(const float* const*
   return 1;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_group(const float* const* x1, const float* const* s1,
-                                                                const float* const* h1, int relu, const float* const* w,
-                                                                const float* const* gz, float* const* dx1, float* const* ipart,
-                                                                int ng, int n, int Ci, int Co, int L, hipStream_t st) {
+int dsgcn_p4_dgrad_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
+                         const float* const* w, const float* const* gz, float* const* dx1, float* const* ipart, int ng, int n,
+                         int Ci, int Co, int L, hipStream_t st) {
   P4Plan p;
   if (ng < 1 || ng > 3 || !p4_plan(n, Co, Ci, L, &p, 1) || p.gemm) return 0;
   Pw4Args a = {};
@@ -1022,14 +1010,14 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_group(const float* cons
 
 // Bytes of the pre-split weight image a (Ci -> Co) conv over planes of L positions wants (0: neither its forward nor its
 // data gradient takes the GEMM form), and the launch that fills it.
-__attribute__((visibility("hidden"))) size_t dsgcn_p4_ws_bytes(int n, int Ci, int Co, int L) {
+size_t dsgcn_p4_ws_bytes(int n, int Ci, int Co, int L) {
   P4Plan pf, pb;
   const bool f = p4_plan(n, Ci, Co, L, &pf, 0) && pf.gemm, b = p4_plan(n, Co, Ci, L, &pb, 1) && pb.gemm;
   if (!g_p4_ws || !(f || b)) return 0;
   return ws_dims(Ci, Co).bytes;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_wsplit(const float* w, int Ci, int Co, void* out, hipStream_t st) {
+int dsgcn_p4_wsplit(const float* w, int Ci, int Co, void* out, hipStream_t st) {
   const WsDims d = ws_dims(Ci, Co);
   const long total = (long)d.MpN * (d.KpN >> 2) + (long)d.MpT * (d.KpT >> 2);
   hipLaunchKernelGGL(k_wsplit, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w, Ci, Co,
@@ -1038,8 +1026,7 @@ __attribute__((visibility("hidden"))) int dsgcn_p4_wsplit(const float* w, int Ci
   return 0;
 }
 
-__attribute__((visibility("hidden"))) int dsgcn_p4_wsplit_multi(const float* const* w, void* const* out, const int* Ci,
-                                                                const int* Co, int njobs, hipStream_t st) {
+int dsgcn_p4_wsplit_multi(const float* const* w, void* const* out, const int* Ci, const int* Co, int njobs, hipStream_t st) {
   for (int j0 = 0; j0 < njobs; j0 += WS_MAXJOBS) {
     WsJobs jb;
     jb.njobs = njobs - j0 < WS_MAXJOBS ? njobs - j0 : WS_MAXJOBS;

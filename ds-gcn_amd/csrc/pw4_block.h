@@ -2,8 +2,7 @@
 // the kernels that run it: k_pw4 itself, and the launches that HOST a small conv in their leading workgroups (the guest
 // blocks below: k_pw4 / k_pwg3 in pw4.hip, the one-pass narrow backward in bwd64.hip).
 #pragma once
-#include "common.h"
-#include "dsgcn_jobs.h"
+#include "kc.h"
 #include <type_traits>
 
 struct Pw4Args {
@@ -31,11 +30,10 @@ struct Pw4Args {
 struct P4Guest { Pw4Args a; int nblk; };
 struct P4NoGuest {};
 template <bool HOST> using P4GuestArg = std::conditional_t<HOST, P4Guest, P4NoGuest>;
-// ... with the dynamic LDS its body needs (host side)
+// ... with the dynamic LDS its body needs (host side).  dsgcn_p4_guest_plan (kc.h, defined in pw4.hip): a guest record ->
+// P4Hosted (epi 0: forward, in = x, out = z; 1: data gradient, in = gz, out = dx); 0 unless it is the <1, 2, 0, 16, epi>
+// shape of the dynamic-adjacency projections (plain operand, tiny planes)
 struct P4Hosted { P4Guest g; size_t lds; };
-// pw4.hip: a guest record -> P4Hosted (epi 0: forward, in = x, out = z; 1: data gradient, in = gz, out = dx); 0 unless it is
-// the <1, 2, 0, 16, epi> shape of the dynamic-adjacency projections (plain operand, tiny planes)
-__attribute__((visibility("hidden"))) int dsgcn_p4_guest_plan(const dsgcn_guest_conv* g, int epi, P4Hosted* h);
 
 namespace {
 

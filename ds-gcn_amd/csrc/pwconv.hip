@@ -13,10 +13,14 @@
 // Work decomposition (k_pwconv_fwd2 / _dgrad2, below): wave-independent — each wave owns one 32-position tile of one
 // sample and <= 64 output channels; the B operand comes straight from HBM in MFMA fragment shape (raw buffer loads), only
 // the weights pass through LDS; per-channel sums leave through an LDS transpose, one partial row per block
-// (deterministic two-stage BN statistics, finalised in fp64 by k_bn_finalize).  wgrad stages both operands in LDS.
-// Bound: HBM for Ci,Co <= 64 (16 FLOP/B), f32 MFMA above (32-64 FLOP/B vs ridge ~20).
-#include "common.h"
-#include "bn_jobs.h"
+// (deterministic two-stage BN statistics, finalised in fp64 by k_bn_finalize: reduce.hip).  wgrad stages both operands in
+// LDS.  Bound: HBM for Ci,Co <= 64 (16 FLOP/B), f32 MFMA above (32-64 FLOP/B vs ridge ~20).
+//
+// This file, top to bottom: the first-generation kernels with the conv's own epilogue / prologue kernels (k_rowmean_stats,
+// k_dz_eff_aug); the dispatch functions that choose between them and the family's later forms (pw4.hip, wgrad.hip,
+// bwd64.hip, reached through kc.h); the C entry points of include/dsgcn.h, each of which fills the operand structs of kc.h
+// once and hands them down.  The column sums and the BatchNorm reductions the conv's partial rows feed are in reduce.hip.
+#include "kc.h"
 
 namespace {
 
@@ -202,10 +206,6 @@ __device__ __forceinline__ void fwd2_roll(const PwArgs& a, f32x16 (&acc)[MT][1],
     }
   }
 }
-
-int g_pw_roll = 13;        // bit 0: rolling prefetch in the forward (on), bit 1: in the data gradient (off: 64 more VGPRs halve
-                           // the occupancy, measured -4 % on the step: round-1 A/B), bit 2: dgrad epilogue operands
-                           // fetched before the K loop (on: +0.5 %), bit 3: XCD-aware block order in wgrad (on: +0.5 %)
 
 template <int MT, int NW, bool ROLL>
 __global__ __launch_bounds__(PW_NT) void k_pwconv_fwd2(PwArgs a) {
@@ -471,162 +471,6 @@ __global__ __launch_bounds__(64) void k_dz_eff_aug4(const float* __restrict__ gz
       po[i] = f32x4{r[0], r[1], r[2], r[3]};
     }
   }
-}
-
-// Batch statistics -> BN affine.  partial [nblk][C][2] (fp32 block sums) reduced in fp64: one 256-thread workgroup
-// per 32 channels (8 row-slices x 32 channels, coalesced 256-B rows), then a cross-slice LDS reduction.
-//   mean, var (biased) saved for backward; scale = gamma*rsqrt(var+eps); shift = beta - mean*scale.
-// gamma/beta NULL -> identity affine parameters; channels >= c_affine get the identity affine (1, 0).
-__global__ __launch_bounds__(1024) void k_bn_finalize(const float* __restrict__ partial, int nblk, int C, double count,
-                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                     float eps, float* __restrict__ mean_out,
-                                                     float* __restrict__ var_out, float* __restrict__ scale_out,
-                                                     float* __restrict__ shift_out, int c_affine) {
-  // 8 channels x 128 row slices per block: the kernel is a latency chain over the partial rows (up to ~1800 of them),
-  // so the rows are spread over many threads and C/8 blocks rather than walked by 32 slices in C/32 blocks (bn_jobs.h)
-  __shared__ double red[16][8][2];
-  const BnFinJob J = {partial, gamma, beta, mean_out, var_out, scale_out, shift_out, count, eps, nblk, C, c_affine};
-  bn_finalize_block(J, blockIdx.x, red);
-}
-
-// several finalize / coefficient jobs in one launch (bn_jobs.h): blocks = the jobs' blocks back to back
-__global__ __launch_bounds__(1024) void k_bn_finalize_multi(BnFinTable t) {
-  __shared__ double red[16][8][2];
-  bnj_dispatch(t, blockIdx.x, [&](const BnFinJob& J, int b) { bn_finalize_block(J, b, red); });
-}
-
-__global__ __launch_bounds__(1024) void k_bn_coef_rows_multi(BnCoefTable t) {
-  __shared__ double red[16][8][2];
-  bnj_dispatch(t, blockIdx.x, [&](const BnCoefJob& J, int b) { bn_coef_rows_block(J, b, red); });
-}
-
-// Column sums of a row-major (R, C) fp32 matrix -> out (C), accumulated in fp64 (partial-buffer reductions).
-struct ColJob { const float* src; float* out; int R, C, inner, nblk; };
-
-// 16-byte form: a thread owns 4 consecutive columns, a block 128 columns x 32 row slices, so every row visit of a wave is
-// two 512-B segments instead of two 128-B ones (the big inputs are the weight-gradient partials: 10-30 MB each, ~0.8 GB
-// per DS-STGCN step — these sums are bandwidth-bound, not launch-bound).  C % 4 == 0, rows 16-byte aligned, inner == 1.
-__host__ __device__ inline bool colsum_wide(int C, int inner, const float* src) {
-  return (C & 3) == 0 && inner == 1 && C >= 128 && ((size_t)src & 15) == 0;
-}
-__host__ __device__ inline int colsum_blocks(int C, int inner, const float* src) {
-  return colsum_wide(C, inner, src) ? (C + 127) / 128 : (C + 31) / 32;
-}
-
-__device__ __forceinline__ void colsum_body4(const ColJob& j, int bid, double (*red)[32]) {
-  const int cl = threadIdx.x & 31, slice = threadIdx.x >> 5;
-  const int c = bid * 128 + 4 * cl;
-  const int R = j.R, C = j.C;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  if (c < C) {
-    for (int r0 = slice; r0 < R; r0 += 32 * 4) {
-      f32x4 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = r0 + 32 * q;
-        v[q] = r < R ? *reinterpret_cast<const f32x4*>(j.src + (size_t)r * C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { s0 += (double)v[q].x; s1 += (double)v[q].y; s2 += (double)v[q].z; s3 += (double)v[q].w; }
-    }
-  }
-  // four passes through the [32][32] staging array, one per column of the quad
-  double acc[4] = {s0, s1, s2, s3};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    __syncthreads();
-    red[slice][cl] = acc[e];
-    __syncthreads();
-    if (slice == 0 && c < C) {
-      double t = 0.0;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) t += red[i][cl];
-      j.out[c + e] = (float)t;
-    }
-  }
-}
-
-__device__ __forceinline__ void colsum_body(const ColJob& j, int bid) {
-  __shared__ double red[32][32];
-  if (colsum_wide(j.C, j.inner, j.src)) { colsum_body4(j, bid, red); return; }
-  const int cl = threadIdx.x & 31, slice = threadIdx.x >> 5;
-  const int c = bid * 32 + cl;
-  const int R = j.R, C = j.C;
-  double s = 0.0;
-  if (c < C) {
-    for (int r0 = slice; r0 < R; r0 += 32 * 8) {
-      float v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int r = r0 + 32 * q;
-        v[q] = r < R ? j.src[(size_t)r * C + c] : 0.f;
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += (double)v[q];
-    }
-  }
-  red[slice][cl] = s;
-  __syncthreads();
-  if (slice == 0 && c < C) {
-#pragma unroll
-    for (int i = 1; i < 32; ++i) s += red[i][cl];
-    // inner > 1: columns are (C/inner, inner) pairs and leave transposed, out (inner, C/inner), so that each of the
-    // `inner` reductions is a contiguous vector for its consumer
-    j.out[j.inner > 1 ? (c % j.inner) * (C / j.inner) + c / j.inner : c] = (float)s;
-  }
-}
-
-// up to two independent reductions in one launch (the weight-gradient and the input-affine partials of one conv)
-__global__ __launch_bounds__(1024) void k_colsum(ColJob a, ColJob b) {
-  if ((int)blockIdx.x < a.nblk) colsum_body(a, blockIdx.x);
-  else colsum_body(b, blockIdx.x - a.nblk);
-}
-
-// any number of independent reductions in one launch: the partial rows of parameter gradients (weights, biases, A,
-// alpha / beta, add_coeff) feed nothing but the optimizer, so their ~55 column sums per DS-STGCN step are queued during
-// the backward and finished by ONE launch before the gradients are packed.  table: njobs x {src, out, (R, C) packed,
-// first block} as 64-bit words (device memory), blocks of a job are contiguous in the grid.
-__global__ __launch_bounds__(1024) void k_colsum_multi(const long* __restrict__ table, int njobs) {
-  // binary search of the job that owns this block (first-block column is ascending)
-  int lo = 0, hi = njobs - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((int)table[4 * mid + 3] <= b) lo = mid; else hi = mid - 1;
-  }
-  ColJob j;
-  j.src = reinterpret_cast<const float*>(table[4 * lo]);
-  j.out = reinterpret_cast<float*>(table[4 * lo + 1]);
-  j.R = (int)(table[4 * lo + 2] >> 32);
-  j.C = (int)(table[4 * lo + 2] & 0xffffffffL);
-  j.inner = 1;
-  j.nblk = 0;
-  colsum_body(j, b - (int)table[4 * lo + 3]);
-}
-
-// the same with the table in the kernel arguments (<= CM_MAXJOBS jobs per launch): no table upload in front of the launch,
-// the job lookup runs on scalar loads
-constexpr int CM_MAXJOBS = 112;
-struct ColTable {
-  long w[4 * CM_MAXJOBS];
-  int njobs;
-};
-
-__global__ __launch_bounds__(1024) void k_colsum_multi_arg(ColTable t) {
-  int lo = 0, hi = t.njobs - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((int)t.w[4 * mid + 3] <= b) lo = mid; else hi = mid - 1;
-  }
-  ColJob j;
-  j.src = reinterpret_cast<const float*>(t.w[4 * lo]);
-  j.out = reinterpret_cast<float*>(t.w[4 * lo + 1]);
-  j.R = (int)(t.w[4 * lo + 2] >> 32);
-  j.C = (int)(t.w[4 * lo + 2] & 0xffffffffL);
-  j.inner = 1;
-  j.nblk = 0;
-  colsum_body(j, b - (int)t.w[4 * lo + 3]);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1115,111 +959,18 @@ __global__ __launch_bounds__(PW_NT) void k_pwconv_wgrad(PwBwdArgs a) {
   if (byy == 0 && quarter == 0 && co < Co) a.dbp[(size_t)split * a.pstride + co] = dbacc;
 }
 
-// BN backward coefficients of a conv whose batch statistics feed a deferred affine (scale, shift):
-//   d gamma = r (g_scale - mean g_shift), d beta = g_shift, A0 = dmean/M - 2 dvar mean/M, B0 = 2 dvar/M
-//   with dmean = -g_shift*gamma*r, dvar = -0.5 r^3 gamma (g_scale - mean g_shift).
-__global__ __launch_bounds__(64) void k_bn_bwd_coef(const float* __restrict__ g_scale,
-                                                    const float* __restrict__ g_shift,
-                                                    const float* __restrict__ mean, const float* __restrict__ var,
-                                                    const float* __restrict__ gamma, float eps, double count, int C,
-                                                    int c_affine, float* __restrict__ dgamma,
-                                                    float* __restrict__ dbeta, float* __restrict__ A0,
-                                                    float* __restrict__ B0) {
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (c >= C) return;
-  if (c >= c_affine) { dgamma[c] = 0.f; dbeta[c] = 0.f; A0[c] = 0.f; B0[c] = 0.f; return; }
-  const double gs = g_scale ? (double)g_scale[c] : 0.0, gh = g_shift ? (double)g_shift[c] : 0.0;
-  const double mu = mean[c], r = 1.0 / sqrt((double)var[c] + (double)eps);
-  const double g = gamma ? (double)gamma[c] : 1.0;
-  const double t = gs - mu * gh;
-  dgamma[c] = (float)(r * t);
-  dbeta[c] = (float)gh;
-  const double dmean = -gh * g * r;
-  const double dvar = -0.5 * r * r * r * g * t;
-  A0[c] = (float)((dmean - 2.0 * dvar * mu) / count);
-  B0[c] = (float)(2.0 * dvar / count);
-}
-
-// The same coefficients straight from a consumer's partial rows: g_scale[c] = sum_r part[r][c][i_ds], g_shift[c] = sum_r
-// part[r][c][i_dh] (fp64, rows in order), optionally ADDED to what another consumer of the same BatchNorm already wrote —
-// the coefficients are linear in (g_scale, g_shift).  One launch instead of a column sum + k_bn_bwd_coef per consumer.
-// Block = 8 channels x 128 row slices (as k_bn_finalize: the launch is a latency chain over up to ~1600 partial rows, so the
-// rows are spread over many threads and C / 8 blocks: 6.6 -> 4.x us per launch, 55 launches per DS-STGCN step).
-__global__ __launch_bounds__(1024) void k_bn_coef_rows(const float* __restrict__ part, int R, int C, int k, int ids, int idh,
-                                                       const float* __restrict__ mean, const float* __restrict__ var,
-                                                       const float* __restrict__ gamma, float eps, double count,
-                                                       int c_affine, float* __restrict__ coef, int accumulate) {
-  __shared__ double red[16][8][2];
-  const BnCoefJob J = {part, mean, var, gamma, coef, count, eps, R, C, k, ids, idh, c_affine, accumulate};
-  bn_coef_rows_block(J, blockIdx.x, red);
-}
-
-}  // namespace
-
-int g_pw_maxmt = 2;      // measured (round-1 ablation): small per-wave tiles + more resident waves win
-int g_pw4 = 15;           // bit 0: wide-load forward (pw4.hip), bit 1: wide-load data gradient, bit 2: blocked wgrad (wgrad.hip)
-
-// pw4.hip (internal linkage across the library's objects, not exported)
-__attribute__((visibility("hidden"))) int dsgcn_p4_tuning(int key, int value);
-__attribute__((visibility("hidden"))) int dsgcn_p4_groups(int n, int K, int M, int L, int epi);
-__attribute__((visibility("hidden"))) int dsgcn_p4_terms(int n, int K, int M, int L, int epi);
-__attribute__((visibility("hidden"))) int dsgcn_wg2_terms(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_terms(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_wg2_tuning(int key, int value);
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd(const float* x1, const float* s1, const float* h1,
-                                                        const float* x2, const float* s2, const float* h2, int relu,
-                                                        const float* w, const float* bias, float* z, float* partial,
-                                                        int n, int Ci, int Co, int L, hipStream_t st, const void* ws,
-                                                        const dsgcn_guest_conv* guest, int* hosted);
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_hosts(int n, int Ci, int Co, int L, int have_ws,
-                                                              const dsgcn_guest_conv* guest);
-__attribute__((visibility("hidden"))) size_t dsgcn_p4_ws_bytes(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_tuning(int value);
-__attribute__((visibility("hidden"))) int dsgcn_p4_wsplit(const float* w, int Ci, int Co, void* out, hipStream_t st);
-__attribute__((visibility("hidden"))) int dsgcn_p4_wsplit_multi(const float* const* w, void* const* out, const int* Ci,
-                                                                const int* Co, int njobs, hipStream_t st);
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad(const float* x1, const float* s1, const float* h1,
-                                                          const float* x2, const float* s2, const float* h2, int relu,
-                                                          const float* w, const float* z, const float* gz,
-                                                          const float* A0, const float* B0, float* dx1, float* dx2,
-                                                          float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                          const void* ws, const dsgcn_guest_conv* guest, int* hosted);
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_hosts(int n, int Ci, int Co, int L, int have_ws,
-                                                                const dsgcn_guest_conv* guest);
-
-__attribute__((visibility("hidden"))) int dsgcn_p4_group_ok(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_p4_fwd_group(const float* const* x1, const float* const* s1,
-                                                              const float* const* h1, int relu, const float* const* w,
-                                                              float* const* z, int ng, int n, int Ci, int Co, int L,
-                                                              hipStream_t st);
-__attribute__((visibility("hidden"))) int dsgcn_p4_dgrad_group(const float* const* x1, const float* const* s1,
-                                                                const float* const* h1, int relu, const float* const* w,
-                                                                const float* const* gz, float* const* dx1, float* const* ipart,
-                                                                int ng, int n, int Ci, int Co, int L, hipStream_t st);
-
-// bwd64.hip
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_splits(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_bwd64(const float* x1, const float* s1, const float* h1, const float* x2,
-                                                       const float* s2, const float* h2, int relu, const float* w,
-                                                       const float* z, const float* gz, const float* A0, const float* B0,
-                                                       float* dx, float* dx2, float* dwp, float* dbp, int pstride,
-                                                       float* ipart, int n, int Ci, int Co, int L, hipStream_t st,
-                                                       const dsgcn_guest_conv* guest, int* hosted);
-__attribute__((visibility("hidden"))) int dsgcn_bwd64_hosts(int n, int Ci, int Co, int L, const dsgcn_guest_conv* guest);
-
-// wgrad.hip
-__attribute__((visibility("hidden"))) int dsgcn_wg2_splits(int n, int Ci, int Co, int L);
-__attribute__((visibility("hidden"))) int dsgcn_wg2(const float* x1, const float* s1, const float* h1, const float* x2,
-                                                     const float* s2, const float* h2, int relu, const float* z,
-                                                     const float* gz, const float* A0, const float* B0, float* dwp,
-                                                     float* dbp, int pstride, int n, int Ci, int Co, int L,
-                                                     hipStream_t st, const BnCoefTable* jobs, int ngroup = 0,
-                                                     const float* const* gx1 = nullptr, const float* const* gs1 = nullptr,
-                                                     const float* const* gh1 = nullptr, const float* const* ggz = nullptr,
-                                                     float* const* gdwp = nullptr, float* const* gdbp = nullptr);
+// ------------------------------------------------------------------------------------------------------------
+// Dispatch.  Knobs first (lab: dsgcn_pwconv_tuning keys 1-3; the values are the product's).
+// ------------------------------------------------------------------------------------------------------------
+int g_pw_maxmt = 2;        // measured (round-1 ablation): small per-wave tiles + more resident waves win
+int g_pw_roll = 13;        // bit 0: rolling prefetch in the forward (on), bit 1: in the data gradient (off: 64 more VGPRs halve
+                           // the occupancy, measured -4 % on the step: round-1 A/B), bit 2: dgrad epilogue operands
+                           // fetched before the K loop (on: +0.5 %), bit 3: XCD-aware block order in wgrad (on: +0.5 %)
+int g_pw4 = 15;            // bit 0: wide-load forward (pw4.hip), bit 1: wide-load data gradient, bit 2: blocked wgrad (wgrad.hip),
+                           // bit 3: one-pass narrow backward (bwd64.hip)
 
 // workgroup rows of the statistics / input-affine partial buffers for a (K -> M) mix over n planes of L positions
-static int pw_conv_rows(int n, int K, int M, int T, int V, int stride, int which) {
+int pw_conv_rows(int n, int K, int M, int T, int V, int stride, int which) {
   const int Tout = (T + stride - 1) / stride;
   const int L = Tout * V;
   if (stride == 1 && (g_pw4 & which)) {
@@ -1229,12 +980,219 @@ static int pw_conv_rows(int n, int K, int M, int T, int V, int stride, int which
   return n * ((L + 4 * 32 - 1) / (4 * 32));
 }
 
-// the forward behind dsgcn_pwconv_fwd_ws / _guest.  guest: a conv for the launch to carry (hosted: set to 1 when it did)
-static int pw_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
-                  int relu, const float* w, const float* bias, float* z, float* zaug, float* partial, int n, int Ci,
-                  int Co, int T, int V, int stride, int aug, int stats, const void* ws, const dsgcn_guest_conv* guest,
-                  int* hosted, void* stream);
+// the first-generation kernels address the whole tensor with 32-bit byte offsets (the wide-load kernels carry the sample
+// base in the buffer resource): what they cannot address is refused instead of wrapping silently
+bool pw_gen1_addressable(int n, int Ci, int Co, int T, int V) {
+  return (long)n * Ci * T * V * 4 < (1L << 31) - 64 && (long)n * Co * T * V * 4 < (1L << 31) - 64;
+}
 
+bool pw_guest_ok(const dsgcn_guest_conv* g) {
+  return !g || (g->in && g->w && g->out && g->n > 0 && g->Ci > 0 && g->Co > 0 && g->L > 0);
+}
+
+// The forward.  guest: a conv for the launch to carry (*hosted: set to 1 when it did).
+int pw_fwd(const KcIn& in, const float* w, const float* bias, float* z, float* zaug, float* partial, int n, int Ci, int Co,
+           int T, int V, int stride, int aug, int stats, const void* ws, const dsgcn_guest_conv* guest, int* hosted,
+           void* stream) {
+  if (!in.x1 || !w || !z || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
+  if ((aug && !zaug) || (stats && !partial) || (in.s1 && !in.h1) || (in.s2 && !in.h2)) return DSGCN_EINVAL;
+  const int Tout = (T + stride - 1) / stride;
+  hipStream_t st = (hipStream_t)stream;
+  const int L = Tout * V;
+  const int conv_rows = pw_conv_rows(n, Ci, Co, T, V, stride, 1);
+  int fast = 0;
+  if (stride == 1 && (g_pw4 & 1)) {
+    fast = dsgcn_p4_fwd(in, w, bias, z, stats ? partial : nullptr, n, Ci, Co, L, st, ws, guest, hosted);
+    if (fast != 0 && fast != 1) return fast;
+  }
+  if (!fast) {
+    if (!pw_gen1_addressable(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
+    PwArgs a = {};
+    a.x1 = in.x1; a.s1 = in.s1; a.h1 = in.h1; a.x2 = in.x2; a.s2 = in.s2; a.h2 = in.h2; a.relu = in.relu;
+    a.w = w; a.bias = bias; a.z = z; a.zaug = zaug; a.partial = partial;
+    a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug;
+    a.stats = stats;
+    a.roll = ((g_pw_roll & 1) && Ci % KW == 0) ? 1 : 0;
+    const int mtiles = (Co + 31) / 32;
+    const int MT = mtiles >= g_pw_maxmt ? g_pw_maxmt : mtiles;
+    const int NW = 1;
+    const int nbx = (L + 4 * NW * 32 - 1) / (4 * NW * 32);
+    a.nbx = nbx;
+    a.cc = (mtiles + MT - 1) / MT;
+    dim3 grid((unsigned)(((long)nbx * n + 7) / 8 * 8 * a.cc));
+    size_t ldsf = (size_t)32 * MT * KWS + 4 + (size_t)4 * Ci;
+    if (ldsf < (size_t)4 * 32 * 36 + 512) ldsf = (size_t)4 * 32 * 36 + 512;
+    const size_t lds = ldsf * sizeof(float);
+#define PW_FWD2(MTV)                                                                                  \
+  if (a.roll) hipLaunchKernelGGL((k_pwconv_fwd2<MTV, 1, true>), grid, dim3(PW_NT), lds, st, a);       \
+  else hipLaunchKernelGGL((k_pwconv_fwd2<MTV, 1, false>), grid, dim3(PW_NT), lds, st, a)
+    switch (MT) {
+      case 1: PW_FWD2(1); break;
+      case 2: PW_FWD2(2); break;
+      case 3: PW_FWD2(3); break;
+      default: PW_FWD2(4); break;
+    }
+#undef PW_FWD2
+    DSGCN_LAUNCH_CHECK();
+  }
+  if (aug) {
+    const size_t l2 = (size_t)Tout * V * sizeof(float);
+    if (l2 > 64 * 1024) return DSGCN_EUNSUPPORTED;
+    hipLaunchKernelGGL(k_rowmean_stats, dim3((unsigned)((long)n * Co)), dim3(64), l2, st, z, zaug,
+                       stats ? partial + (size_t)conv_rows * Co * 2 : (float*)nullptr, Co, Tout, V);
+    DSGCN_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The data gradient (guest, hosted: as pw_fwd).  zaug / gzaug: the global-joint column's share of d (aug).
+int pw_dgrad(const KcIn& in, const float* w, const KcDz& d, const float* zaug, const float* gzaug, float* dx1, float* dx2,
+             float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, const void* ws,
+             const dsgcn_guest_conv* guest, int* hosted, void* stream) {
+  if (!in.x1 || !w || !dx1 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
+  if ((d.A0 && (!d.B0 || !d.z)) || (aug && d.A0 && !zaug) || (in.x2 && !dx2)) return DSGCN_EINVAL;
+  // dsgcn_pwconv_ipart_rows sizes `ipart` for the wide-load plan, which needs gz: a NULL gz would drop to the scalar
+  // kernels and their (larger) row count — refuse instead of writing past the caller's buffer
+  if (!d.gz && ipart) return DSGCN_EINVAL;
+  const int Tout = (T + stride - 1) / stride;
+  hipStream_t st = (hipStream_t)stream;
+  if (stride > 1) {
+    hipError_t e = hipMemsetAsync(dx1, 0, (size_t)n * Ci * T * V * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    if (dx2) {
+      e = hipMemsetAsync(dx2, 0, (size_t)n * Ci * T * V * sizeof(float), st);
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  const int L = Tout * V;
+  if (stride == 1 && !aug && (g_pw4 & 2)) {
+    const int fast = dsgcn_p4_dgrad(in, w, d, dx1, dx2, ipart, n, Ci, Co, L, st, ws, guest, hosted);
+    if (fast == 1) return 0;
+    if (fast != 0) return fast;
+  }
+  if (!pw_gen1_addressable(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
+  PwBwdArgs a = {};
+  a.x1 = in.x1; a.s1 = in.s1; a.h1 = in.h1; a.x2 = in.x2; a.s2 = in.s2; a.h2 = in.h2; a.relu = in.relu; a.w = w;
+  a.z = d.z; a.zaug = zaug; a.gz = d.gz; a.gzaug = gzaug; a.A0 = d.A0; a.B0 = d.B0;
+  a.dx1 = dx1; a.dx2 = dx2; a.ipart = ipart;
+  a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug;
+  a.roll = ((g_pw_roll & 2) && Co % KW == 0 && (Ci & 3) == 0) ? 1 : 0;
+  const int mtiles = (Ci + 31) / 32;
+  const int MT = mtiles >= g_pw_maxmt ? g_pw_maxmt : mtiles;
+  const int NW = 1;
+  const int nbx = (L + 4 * NW * 32 - 1) / (4 * NW * 32);
+  a.nbx = nbx;
+  a.cc = (mtiles + MT - 1) / MT;
+  dim3 grid((unsigned)(((long)nbx * n + 7) / 8 * 8 * a.cc));
+  size_t ldsf = (size_t)KW * (32 * MT + 1) + 4 + (size_t)2 * Co;
+  if (ldsf < (size_t)4 * 32 * 36 + 4 * 32 * 3) ldsf = (size_t)4 * 32 * 36 + 4 * 32 * 3;
+  const size_t lds = ldsf * sizeof(float);
+#define DSGCN_DGRAD(MTv, NWv)                                                                        \
+  do {                                                                                               \
+    if (aug) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, true, false, false>), grid, dim3(PW_NT), lds, st, a);   \
+    else if (a.roll) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, true, false>), grid, dim3(PW_NT), lds, st, a);   \
+    else if (g_pw_roll & 4) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, false, (NWv == 1)>), grid, dim3(PW_NT), lds, st, a);      \
+    else hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, false, false>), grid, dim3(PW_NT), lds, st, a);      \
+  } while (0)
+  switch (MT) {
+    case 1: DSGCN_DGRAD(1, 1); break;
+    case 2: DSGCN_DGRAD(2, 1); break;
+    case 3: DSGCN_DGRAD(3, 1); break;
+    default: DSGCN_DGRAD(4, 1); break;
+  }
+#undef DSGCN_DGRAD
+  DSGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+// A guest record (dsgcn_jobs.h) launched on its own, when the host's launch did not carry it.  Forward: in = x, out = z.
+int pw_guest_fwd(const dsgcn_guest_conv* g, void* stream) {
+  return pw_fwd(KcIn{g->in}, g->w, g->bias, g->out, nullptr, nullptr, g->n, g->Ci, g->Co, 1, g->L, 1, 0, 0, nullptr, nullptr,
+                nullptr, stream);
+}
+// Backward: the data gradient of a small plain conv — in = gz (n, Co, L), out = dx (n, Ci, L), bias unused.
+// (x1 only has to be non-NULL: a plain conv — no ReLU, no input affine, no second stream — never reads its forward input
+// in the data gradient, so the record carries none and dx stands in for it)
+int pw_guest_dgrad(const dsgcn_guest_conv* g, void* stream) {
+  return pw_dgrad(KcIn{g->out}, g->w, KcDz{nullptr, g->in}, nullptr, nullptr, g->out, nullptr, nullptr, g->n, g->Ci, g->Co, 1,
+                  g->L, 1, 0, nullptr, nullptr, nullptr, stream);
+}
+
+// k-split plan of the weight gradient: the number of splits (size of dim 0 of dwp / dbp)
+int pw_wgrad_splits(int n, int Ci, int Co, int T, int V, int stride) {
+  const int Tout = (T + stride - 1) / stride;
+  if (stride == 1 && (g_pw4 & 4)) {
+    const int s = dsgcn_wg2_splits(n, Ci, Co, T * V);
+    if (s > 0) return s;
+  }
+  const int TR = Tout >= WG_TR ? WG_TR : Tout;
+  const int chunks = n * ((Tout + TR - 1) / TR);
+  const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
+  int splits = 512 / tiles;
+  if (splits < 1) splits = 1;
+  if (splits > chunks) splits = chunks;
+  const int per = (chunks + splits - 1) / splits;
+  return (chunks + per - 1) / per;
+}
+
+// The weight gradient with the BatchNorm coefficient jobs `jt` (checked by the caller; jt.n may be 0): the jobs ride in
+// the blocked kernel's launch as extra workgroups, or go out as one launch ahead of the first-generation kernel.
+int pw_wgrad(const KcIn& in, const KcDz& d, const float* zaug, const float* gzaug, float* dwp, float* dbp, int pstride, int n,
+             int Ci, int Co, int T, int V, int stride, int aug, const BnCoefTable& jt, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (stride == 1 && !aug && (g_pw4 & 4)) {
+    if (pstride < Co * Ci) return DSGCN_EINVAL;
+    const int fast = dsgcn_wg2(in, d, dwp, dbp, pstride, n, Ci, Co, T * V, st, &jt);
+    if (fast == 1) return 0;
+    if (fast != 0) return fast;
+  }
+  if (jt.n) {                                      // not hosted: one launch for the jobs, then the weight gradient
+    const int rc = bnj_coef_launch(jt, st);
+    if (rc != 0) return rc;
+  }
+  if (!pw_gen1_addressable(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
+  const int Tout = (T + stride - 1) / stride;
+  const int TR = Tout >= WG_TR ? WG_TR : Tout;
+  if (TR * V > 16 * WG_J) return DSGCN_EUNSUPPORTED;
+  if (pstride < Co * Ci) return DSGCN_EINVAL;
+  PwBwdArgs a = {};
+  a.x1 = in.x1; a.s1 = in.s1; a.h1 = in.h1; a.x2 = in.x2; a.s2 = in.s2; a.h2 = in.h2; a.relu = in.relu;
+  a.z = d.z; a.zaug = zaug; a.gz = d.gz; a.gzaug = gzaug; a.A0 = d.A0; a.B0 = d.B0; a.dwp = dwp; a.dbp = dbp;
+  a.pstride = pstride;
+  a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug; a.TR = TR;
+  a.nb_per_sample = (Tout + TR - 1) / TR;
+  a.total_chunks = n * a.nb_per_sample;
+  a.vec = (stride == 1 && (T * V) % 4 == 0 && (Tout * V) % 4 == 0 && (TR * V) % 4 == 0 &&
+           ((Tout % TR) * V) % 4 == 0) ? 1 : 0;
+  const int splits = pw_wgrad_splits(n, Ci, Co, T, V, stride);
+  a.chunks_per_split = (a.total_chunks + splits - 1) / splits;
+  const int KP = (TR * V + 1) & ~1;
+  const int LS = KP | 1;
+  const size_t lds = (size_t)2 * 64 * LS * sizeof(float);
+  dim3 grid((unsigned)((Co + 63) / 64), (unsigned)((Ci + 63) / 64), (unsigned)splits);
+  a.nbx = a.cc = 0;
+  if (grid.x * grid.y > 1 && splits % 8 == 0 && (g_pw_roll & 8)) {
+    a.nbx = (int)grid.x; a.cc = (int)grid.y;
+    grid = dim3(grid.x * grid.y * (unsigned)splits);
+  }
+  if (a.vec && in.x2) hipLaunchKernelGGL((k_pwconv_wgrad<true, true>), grid, dim3(PW_NT), lds, st, a);
+  else if (a.vec) hipLaunchKernelGGL((k_pwconv_wgrad<true, false>), grid, dim3(PW_NT), lds, st, a);
+  else if (in.x2) hipLaunchKernelGGL((k_pwconv_wgrad<false, true>), grid, dim3(PW_NT), lds, st, a);
+  else hipLaunchKernelGGL((k_pwconv_wgrad<false, false>), grid, dim3(PW_NT), lds, st, a);
+  DSGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+// the sizes the three grouped entry points accept
+bool pw_group_dims_ok(int ngroup, int n, int Ci, int Co, int T, int V) {
+  return ngroup >= 1 && ngroup <= 3 && n > 0 && Ci > 0 && Co > 0 && T > 0 && V > 0;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------
+// The C ABI (include/dsgcn.h).  An entry point that is another one with a NULL stands right under it.
+// ------------------------------------------------------------------------------------------------------------
 extern "C" {
 
 #ifdef DSGCN_LAB
@@ -1268,7 +1226,8 @@ int dsgcn_pwconv_plan(int Tout, int V, int aug, int* TR, int* NPpad, int* nblk_p
   return 0;
 }
 
-// Forward.  x2/s1/h1/s2/h2/bias/zaug/partial may be NULL as allowed by the flags.  partial: (n*nblk_per_sample, Co, 2).
+// ---- forward ----
+
 // Rows of the `partial` buffer the forward writes for a given shape (conv blocks [+ global-joint rows when aug]).
 int dsgcn_pwconv_partial_rows(int n, int Ci, int Co, int T, int V, int stride, int aug) {
   int rows = pw_conv_rows(n, Ci, Co, T, V, stride, 1);
@@ -1280,33 +1239,36 @@ int dsgcn_pwconv_partial_rows(int n, int Ci, int Co, int T, int V, int stride, i
 // partial: (dsgcn_pwconv_partial_rows(...), Co, 2).
 // ws: NULL, or the pre-split weight image of dsgcn_pwconv_wsplit (same w): the GEMM-form launches then skip the split of
 // the weight tile (csrc/pw4.hip, k_pwg2).
-int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                        const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
-                        float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
-                        const void* ws, void* stream) {
-  return pw_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats, ws, nullptr,
-                nullptr, stream);
-}
-
-// The same launch with a GUEST conv in its leading workgroups (csrc/pw4.hip: P4Guest).  guest NULL: exactly
-// dsgcn_pwconv_fwd_ws.  A pair that is not hosted (the host falls to a first-generation kernel or takes another form than
-// the `pre` conv's, the guest is not a tiny-plane plain conv, LDS) launches the guest on its own from this call: it is
-// never dropped.  *hosted (may be NULL) = 1 when the host's launch carried it, 0 when it went out alone.
+// guest: NULL, or a GUEST conv for the launch's leading workgroups (csrc/pw4.hip: P4Guest).  A pair that is not hosted (the
+// host falls to a first-generation kernel or takes another form than the `pre` conv's, the guest is not a tiny-plane plain
+// conv, LDS) launches the guest on its own from this call: it is never dropped.  *hosted (may be NULL) = 1 when the host's
+// launch carried it, 0 when it went out alone.
 int dsgcn_pwconv_fwd_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                               const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
                               float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
                               const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
   if (hosted) *hosted = 0;
-  if (guest && (!guest->in || !guest->w || !guest->out || guest->n <= 0 || guest->Ci <= 0 || guest->Co <= 0 || guest->L <= 0))
-    return DSGCN_EINVAL;
+  if (!pw_guest_ok(guest)) return DSGCN_EINVAL;
   int took = 0;
-  const int rc = pw_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats, ws,
-                        guest, &took, stream);
+  const int rc = pw_fwd(KcIn{x1, s1, h1, x2, s2, h2, relu}, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats,
+                        ws, guest, &took, stream);
   if (rc != 0 || !guest) return rc;
   if (hosted) *hosted = took;
-  if (took) return 0;
-  return pw_fwd(guest->in, nullptr, nullptr, nullptr, nullptr, nullptr, 0, guest->w, guest->bias, guest->out, nullptr,
-                nullptr, guest->n, guest->Ci, guest->Co, 1, guest->L, 1, 0, 0, nullptr, nullptr, nullptr, stream);
+  return took ? 0 : pw_guest_fwd(guest, stream);
+}
+int dsgcn_pwconv_fwd_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                        const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
+                        float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
+                        const void* ws, void* stream) {
+  return dsgcn_pwconv_fwd_ws_guest(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug,
+                                   stats, ws, nullptr, nullptr, stream);
+}
+int dsgcn_pwconv_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                     const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
+                     float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
+                     void* stream) {
+  return dsgcn_pwconv_fwd_ws(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats,
+                             nullptr, stream);
 }
 
 // 1 = the (Ci -> Co) conv of this shape hosts `guest` (with the weight image passed whenever dsgcn_pwconv_wsplit_bytes asks
@@ -1321,81 +1283,11 @@ int dsgcn_pwconv_guest_hosted(int dir, int n, int Ci, int Co, int T, int V, int 
   return (g_pw4 & 2) ? dsgcn_p4_dgrad_hosts(n, Ci, Co, T * V, have_ws, guest) : 0;
 }
 
-}  // extern "C"
-
-static int pw_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
-                  int relu, const float* w, const float* bias, float* z, float* zaug, float* partial, int n, int Ci,
-                  int Co, int T, int V, int stride, int aug, int stats, const void* ws, const dsgcn_guest_conv* guest,
-                  int* hosted, void* stream) {
-  if (!x1 || !w || !z || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
-  if ((aug && !zaug) || (stats && !partial) || (s1 && !h1) || (s2 && !h2)) return DSGCN_EINVAL;
-  const int Tout = (T + stride - 1) / stride;
-  PwArgs a = {};
-  a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu;
-  a.w = w; a.bias = bias; a.z = z; a.zaug = zaug; a.partial = partial;
-  a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug;
-  a.stats = stats;
-  a.roll = ((g_pw_roll & 1) && Ci % KW == 0) ? 1 : 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int L = Tout * V;
-  const int conv_rows = pw_conv_rows(n, Ci, Co, T, V, stride, 1);
-  int fast = 0;
-  if (stride == 1 && (g_pw4 & 1)) {
-    fast = dsgcn_p4_fwd(x1, s1, h1, x2, s2, h2, relu, w, bias, z, stats ? partial : nullptr, n, Ci, Co, L, st, ws, guest,
-                        hosted);
-    if (fast != 0 && fast != 1) return fast;
-  }
-  if (!fast) {
-  // the first-generation kernels address the whole tensor with 32-bit byte offsets (the wide-load kernels above carry
-  // the sample base in the buffer resource): refuse what they cannot address instead of wrapping silently
-  if ((long)n * Ci * T * V * 4 >= (1L << 31) - 64 || (long)n * Co * T * V * 4 >= (1L << 31) - 64) return DSGCN_EUNSUPPORTED;
-  const int mtiles = (Co + 31) / 32;
-  const int MT = mtiles >= g_pw_maxmt ? g_pw_maxmt : mtiles;
-  const int NW = 1;
-  const int nbx = (L + 4 * NW * 32 - 1) / (4 * NW * 32);
-  a.nbx = nbx;
-  a.cc = (mtiles + MT - 1) / MT;
-  dim3 grid((unsigned)(((long)nbx * n + 7) / 8 * 8 * a.cc));
-  size_t ldsf = (size_t)32 * MT * KWS + 4 + (size_t)4 * Ci;
-  if (ldsf < (size_t)4 * 32 * 36 + 512) ldsf = (size_t)4 * 32 * 36 + 512;
-  const size_t lds = ldsf * sizeof(float);
-#define PW_FWD2(MTV)                                                                                  \
-  if (a.roll) hipLaunchKernelGGL((k_pwconv_fwd2<MTV, 1, true>), grid, dim3(PW_NT), lds, st, a);       \
-  else hipLaunchKernelGGL((k_pwconv_fwd2<MTV, 1, false>), grid, dim3(PW_NT), lds, st, a)
-  switch (MT) {
-    case 1: PW_FWD2(1); break;
-    case 2: PW_FWD2(2); break;
-    case 3: PW_FWD2(3); break;
-    default: PW_FWD2(4); break;
-  }
-#undef PW_FWD2
-  DSGCN_LAUNCH_CHECK();
-  }
-  if (aug) {
-    const size_t l2 = (size_t)Tout * V * sizeof(float);
-    if (l2 > 64 * 1024) return DSGCN_EUNSUPPORTED;
-    hipLaunchKernelGGL(k_rowmean_stats, dim3((unsigned)((long)n * Co)), dim3(64), l2, st, z, zaug,
-                       stats ? partial + (size_t)conv_rows * Co * 2 : (float*)nullptr, Co, Tout, V);
-    DSGCN_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-extern "C" {
-
-int dsgcn_pwconv_fwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                     const float* h2, int relu, const float* w, const float* bias, float* z, float* zaug,
-                     float* partial, int n, int Ci, int Co, int T, int V, int stride, int aug, int stats,
-                     void* stream) {
-  return dsgcn_pwconv_fwd_ws(x1, s1, h1, x2, s2, h2, relu, w, bias, z, zaug, partial, n, Ci, Co, T, V, stride, aug, stats,
-                             nullptr, stream);
-}
-
 // bf16 products per fp32 product of the launch this shape takes under the CURRENT matmul precision level (dir: 0 forward,
 // 1 data gradient, 2 weight gradient): 6 (highest) or 3 (high), 0 = the shape runs an fp32 MFMA form.  Mirrors the
-// dispatch of pw_fwd / pw_dgrad / dsgcn_pwconv_wgrad_jobs and the one-pass backward (dsgcn_pwconv_bwd_rows != 0: six
-// terms at both levels), for a plain conv (no global-joint column) with the weight image passed wherever
-// dsgcn_pwconv_wsplit_bytes asks for one.
+// dispatch of pw_fwd / pw_dgrad / pw_wgrad and the one-pass backward (dsgcn_pwconv_bwd_rows != 0: six terms at both
+// levels), for a plain conv (no global-joint column) with the weight image passed wherever dsgcn_pwconv_wsplit_bytes asks
+// for one.
 int dsgcn_pwconv_terms(int dir, int n, int Ci, int Co, int T, int V, int stride) {
   if (dir < 0 || dir > 2 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride != 1) return 0;
   const int L = T * V;
@@ -1425,213 +1317,18 @@ int dsgcn_pwconv_wsplit_multi(const float* const* w, void* const* ws, const int*
   return dsgcn_p4_wsplit_multi(w, ws, Ci, Co, njobs, (hipStream_t)stream);
 }
 
-int dsgcn_bn_finalize(const float* partial, int nblk, int C, double count, const float* gamma, const float* beta,
-                      float eps, float* mean_out, float* var_out, float* scale_out, float* shift_out, int c_affine,
-                      void* stream) {
-  if (!partial || !mean_out || !var_out || !scale_out || !shift_out || nblk <= 0 || C <= 0) return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_bn_finalize, dim3((unsigned)((C + 7) / 8)), dim3(1024), 0, (hipStream_t)stream, partial, nblk,
-                     C, count, gamma, beta, eps, mean_out, var_out, scale_out, shift_out, c_affine);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
+// ---- backward, data path ----
 
-// Up to three 1x1 convs of ONE shape in one launch each way (host arrays of ngroup device pointers): z_g = W_g . (x1_g * s1_g +
-// h1_g), no bias / second stream / statistics, stride 1 — CTR-GCN's three conv4's per unit (gcn.py:655-657, one per subset),
-// each of which alone leaves the chip under-filled.  dsgcn_pwconv_group_ok: 1 when the shape takes the grouped form (else
-// the caller launches the convs one by one); the data gradient writes dx1_g and the input-scale rows ipart_g
-// (dsgcn_pwconv_ipart_rows, or NULL for all).  The weight gradients stay per conv (dsgcn_pwconv_wgrad).
-int dsgcn_pwconv_group_ok(int n, int Ci, int Co, int T, int V) {
-  if (n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return 0;
-  return ((g_pw4 & 3) == 3) ? dsgcn_p4_group_ok(n, Ci, Co, T * V) : 0;
-}
-
-int dsgcn_pwconv_fwd_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
-                           const float* const* w, float* const* z, int ngroup, int n, int Ci, int Co, int T, int V,
-                           void* stream) {
-  if (!x1 || !s1 || !h1 || !w || !z || ngroup < 1 || ngroup > 3 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
-  for (int g = 0; g < ngroup; ++g)
-    if (!x1[g] || !w[g] || !z[g] || ((s1[g] == nullptr) != (h1[g] == nullptr))) return DSGCN_EINVAL;
-  if (!dsgcn_pwconv_group_ok(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
-  const int rc = dsgcn_p4_fwd_group(x1, s1, h1, relu, w, z, ngroup, n, Ci, Co, T * V, (hipStream_t)stream);
-  return rc == 1 ? 0 : (rc == 0 ? DSGCN_EUNSUPPORTED : rc);
-}
-
-int dsgcn_pwconv_dgrad_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
-                             const float* const* w, const float* const* gz, float* const* dx1, float* const* ipart,
-                             int ngroup, int n, int Ci, int Co, int T, int V, void* stream) {
-  if (!x1 || !s1 || !h1 || !w || !gz || !dx1 || !ipart || ngroup < 1 || ngroup > 3 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 ||
-      V <= 0)
-    return DSGCN_EINVAL;
-  for (int g = 0; g < ngroup; ++g)
-    if (!x1[g] || !w[g] || !gz[g] || !dx1[g] || ((s1[g] == nullptr) != (h1[g] == nullptr))) return DSGCN_EINVAL;
-  if (!dsgcn_pwconv_group_ok(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
-  const int rc = dsgcn_p4_dgrad_group(x1, s1, h1, relu, w, gz, dx1, ipart, ngroup, n, Ci, Co, T * V, (hipStream_t)stream);
-  return rc == 1 ? 0 : (rc == 0 ? DSGCN_EUNSUPPORTED : rc);
-}
-
-// the weight gradients of the same group (dwp_g / dbp_g: partial rows as dsgcn_pwconv_wgrad, dsgcn_pwconv_wgrad_splits rows each)
-int dsgcn_pwconv_wgrad_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
-                             const float* const* gz, float* const* dwp, float* const* dbp, int pstride, int ngroup, int n,
-                             int Ci, int Co, int T, int V, void* stream) {
-  if (!x1 || !s1 || !h1 || !gz || !dwp || !dbp || ngroup < 1 || ngroup > 3 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0)
-    return DSGCN_EINVAL;
-  for (int g = 0; g < ngroup; ++g)
-    if (!x1[g] || !gz[g] || !dwp[g] || !dbp[g] || ((s1[g] == nullptr) != (h1[g] == nullptr)) ||
-        ((s1[g] == nullptr) != (s1[0] == nullptr)))
-      return DSGCN_EINVAL;
-  if (pstride < Co * Ci || !(g_pw4 & 4)) return pstride < Co * Ci ? DSGCN_EINVAL : DSGCN_EUNSUPPORTED;
-  BnCoefTable none = {};
-  const int fast = dsgcn_wg2(x1[0], s1[0], h1[0], nullptr, nullptr, nullptr, relu, nullptr, gz[0], nullptr, nullptr, dwp[0],
-                             dbp[0], pstride, n, Ci, Co, T * V, (hipStream_t)stream, &none, ngroup, x1, s1, h1, gz, dwp, dbp);
-  return fast == 1 ? 0 : (fast == 0 ? DSGCN_EUNSUPPORTED : fast);
-}
-
-// njobs <= 4 finalize jobs (include/dsgcn.h: dsgcn_bn_fin_job, the arguments of dsgcn_bn_finalize as a struct) in ONE
-// launch — BatchNorms whose producers are independent of one another and both done (gcn.py:2165-2169 `post` + `down`).
-int dsgcn_bn_finalize_multi(const dsgcn_bn_fin_job* jobs, int njobs, void* stream) {
-  if (!jobs || njobs <= 0 || njobs > BNJ_MAX) return DSGCN_EINVAL;
-  BnFinTable t = {};
-  t.n = njobs;
-  for (int i = 0; i < njobs; ++i) {
-    const dsgcn_bn_fin_job& q = jobs[i];
-    t.j[i] = BnFinJob{q.partial, q.gamma, q.beta, q.mean, q.var, q.scale, q.shift, q.count, q.eps, q.nblk, q.C, q.c_affine};
-  }
-  if (!bnj_fin_ok(t)) return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_bn_finalize_multi, dim3((unsigned)bnj_total_blocks(t)), dim3(BNJ_NT), 0, (hipStream_t)stream, t);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// njobs <= 4 coefficient jobs (dsgcn_bn_coef_job = the arguments of dsgcn_bn_coef_rows) in one launch.
-int dsgcn_bn_coef_rows_multi(const dsgcn_bn_coef_job* jobs, int njobs, void* stream) {
-  if (!jobs || njobs <= 0 || njobs > BNJ_MAX) return DSGCN_EINVAL;
-  BnCoefTable t = {};
-  t.n = njobs;
-  for (int i = 0; i < njobs; ++i) {
-    const dsgcn_bn_coef_job& q = jobs[i];
-    t.j[i] = BnCoefJob{q.part, q.mean, q.var, q.gamma, q.coef, q.count, q.eps, q.R, q.C, q.k, q.i_ds, q.i_dh, q.c_affine,
-                       q.accumulate};
-  }
-  if (!bnj_coef_ok(t)) return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_bn_coef_rows_multi, dim3((unsigned)bnj_total_blocks(t)), dim3(BNJ_NT), 0, (hipStream_t)stream, t);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// out[c] = sum_r src[r, c]  (fp64 accumulation).
-int dsgcn_colsum(const float* src, int R, int C, float* out, void* stream) {
-  if (!src || !out || R <= 0 || C <= 0) return DSGCN_EINVAL;
-  ColJob a{src, out, R, C, 1, colsum_blocks(C, 1, src)}, b{nullptr, nullptr, 0, 0, 1, 0};
-  hipLaunchKernelGGL(k_colsum, dim3((unsigned)a.nblk), dim3(1024), 0, (hipStream_t)stream, a, b);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// Same, with the result transposed: src (R, C/inner, inner) -> out (inner, C/inner).
-int dsgcn_colsum_t(const float* src, int R, int C, int inner, float* out, void* stream) {
-  if (!src || !out || R <= 0 || C <= 0 || inner <= 0 || C % inner) return DSGCN_EINVAL;
-  ColJob a{src, out, R, C, inner, (C + 31) / 32}, b{nullptr, nullptr, 0, 0, 1, 0};
-  hipLaunchKernelGGL(k_colsum, dim3((unsigned)a.nblk), dim3(1024), 0, (hipStream_t)stream, a, b);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// Two reductions (as dsgcn_colsum_t each; inner = 1 for the plain form) in one launch.
-int dsgcn_colsum2(const float* src_a, int Ra, int Ca, int inner_a, float* out_a, const float* src_b, int Rb, int Cb,
-                  int inner_b, float* out_b, void* stream) {
-  if (!src_a || !out_a || !src_b || !out_b || Ra <= 0 || Ca <= 0 || Rb <= 0 || Cb <= 0 || inner_a <= 0 ||
-      inner_b <= 0 || Ca % inner_a || Cb % inner_b)
-    return DSGCN_EINVAL;
-  ColJob a{src_a, out_a, Ra, Ca, inner_a, colsum_blocks(Ca, inner_a, src_a)}, b{src_b, out_b, Rb, Cb, inner_b, colsum_blocks(Cb, inner_b, src_b)};
-  hipLaunchKernelGGL(k_colsum, dim3((unsigned)(a.nblk + b.nblk)), dim3(1024), 0, (hipStream_t)stream, a, b);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// blocks a job of C columns takes in dsgcn_colsum_multi's grid (the caller lays the jobs' first blocks out with it)
-int dsgcn_colsum_blocks(const float* src, int C) { return colsum_blocks(C, 1, src); }
-
-// table (device, njobs x 4 int64): {src pointer, out pointer, (R << 32) | C, first block}; nblocks = sum of dsgcn_colsum_blocks.
-int dsgcn_colsum_multi(const long* table, int njobs, int nblocks, void* stream) {
-  if (!table || njobs <= 0 || nblocks <= 0) return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_colsum_multi, dim3((unsigned)nblocks), dim3(1024), 0, (hipStream_t)stream, table, njobs);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// The same from a HOST table (njobs x 4 int64, layout as above): the jobs ride in the kernel arguments, CM_MAXJOBS per
-// launch (first-block columns are rebased per launch).
-int dsgcn_colsum_multi_host(const long* table, int njobs, void* stream) {
-  if (!table || njobs <= 0) return DSGCN_EINVAL;
-  for (int j0 = 0; j0 < njobs; j0 += CM_MAXJOBS) {
-    ColTable t;
-    t.njobs = njobs - j0 < CM_MAXJOBS ? njobs - j0 : CM_MAXJOBS;
-    const long base = table[4 * j0 + 3];
-    for (int j = 0; j < t.njobs; ++j) {
-      for (int q = 0; q < 3; ++q) t.w[4 * j + q] = table[4 * (j0 + j) + q];
-      t.w[4 * j + 3] = table[4 * (j0 + j) + 3] - base;
-    }
-    const int jl = j0 + t.njobs - 1;
-    const float* lsrc = reinterpret_cast<const float*>(table[4 * jl]);
-    const long end = table[4 * jl + 3] + colsum_blocks((int)(table[4 * jl + 2] & 0xffffffffL), 1, lsrc);
-    hipLaunchKernelGGL(k_colsum_multi_arg, dim3((unsigned)(end - base)), dim3(1024), 0, (hipStream_t)stream, t);
-    DSGCN_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-// Backward, data path.  gz/gzaug/A0/B0/x2/s*/h*/dx2/ipart may be NULL as in the forward.  dx1 (and dx2) are fully
-// written (zero rows where stride skips frames).  ipart: (n*nblk_per_sample, Ci, 3) = [sum dv*x1, sum dv, sum dv*x2].
+// Rows of the `ipart` buffer the data gradient writes for a given shape.
 int dsgcn_pwconv_ipart_rows(int n, int Ci, int Co, int T, int V, int stride) {
   return pw_conv_rows(n, Co, Ci, T, V, stride, 2);
 }
 
-int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                          const float* h2, int relu, const float* w, const float* z, const float* zaug,
-                          const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
-                          float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, const void* ws,
-                          void* stream);
-
-int dsgcn_pwconv_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                       const float* h2, int relu, const float* w, const float* z, const float* zaug,
-                       const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
-                       float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, void* stream) {
-  return dsgcn_pwconv_dgrad_ws(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T,
-                               V, stride, aug, nullptr, stream);
-}
-
-}  // extern "C"
-
-// the data gradient behind dsgcn_pwconv_dgrad_ws / _guest (guest, hosted: as pw_fwd)
-static int pw_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
-                    int relu, const float* w, const float* z, const float* zaug, const float* gz, const float* gzaug,
-                    const float* A0, const float* B0, float* dx1, float* dx2, float* ipart, int n, int Ci, int Co, int T,
-                    int V, int stride, int aug, const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream);
-
-extern "C" {
-
-int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
-                          const float* h2, int relu, const float* w, const float* z, const float* zaug,
-                          const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
-                          float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, const void* ws,
-                          void* stream) {
-  return pw_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T, V, stride, aug,
-                  ws, nullptr, nullptr, stream);
-}
-
-// The guest of a backward launch: the data gradient of a small plain conv — guest->in = gz (n, Co, L), guest->out = dx
-// (n, Ci, L), guest->bias unused.  Launched on its own from the same call when the pair is not hosted.
-static int pw_guest_dgrad(const dsgcn_guest_conv* g, void* stream) {
-  // (x1 only has to be non-NULL: a plain conv — no ReLU, no input affine, no second stream — never reads its forward input
-  // in the data gradient, so the record carries none and dx stands in for it)
-  return pw_dgrad(g->out, nullptr, nullptr, nullptr, nullptr, nullptr, 0, g->w, nullptr, nullptr, g->in, nullptr, nullptr,
-                  nullptr, g->out, nullptr, nullptr, g->n, g->Ci, g->Co, 1, g->L, 1, 0, nullptr, nullptr, nullptr, stream);
-}
-static bool pw_guest_ok(const dsgcn_guest_conv* g) {
-  return !g || (g->in && g->w && g->out && g->n > 0 && g->Ci > 0 && g->Co > 0 && g->L > 0);
-}
-
-// dsgcn_pwconv_dgrad_ws with a guest data gradient in its leading workgroups (see dsgcn_pwconv_fwd_ws_guest)
+// Backward, data path.  gz/gzaug/A0/B0/x2/s*/h*/dx2/ipart may be NULL as in the forward.  dx1 (and dx2) are fully
+// written (zero rows where stride skips frames).  ipart: (dsgcn_pwconv_ipart_rows(...), Ci, 3) = [sum dv*x1, sum dv,
+// sum dv*x2].  ws: as in the forward.  guest: NULL, or a guest data gradient for the launch's leading workgroups (see
+// dsgcn_pwconv_fwd_ws_guest) — guest->in = gz (n, Co, L), guest->out = dx (n, Ci, L), guest->bias unused; launched on its
+// own from the same call when the pair is not hosted.
 int dsgcn_pwconv_dgrad_ws_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                                 const float* h2, int relu, const float* w, const float* z, const float* zaug,
                                 const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1,
@@ -1640,95 +1337,49 @@ int dsgcn_pwconv_dgrad_ws_guest(const float* x1, const float* s1, const float* h
   if (hosted) *hosted = 0;
   if (!pw_guest_ok(guest)) return DSGCN_EINVAL;
   int took = 0;
-  const int rc = pw_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T, V,
-                          stride, aug, ws, guest, &took, stream);
+  const int rc = pw_dgrad(KcIn{x1, s1, h1, x2, s2, h2, relu}, w, KcDz{z, gz, A0, B0}, zaug, gzaug, dx1, dx2, ipart, n, Ci, Co,
+                          T, V, stride, aug, ws, guest, &took, stream);
   if (rc != 0 || !guest) return rc;
   if (hosted) *hosted = took;
   return took ? 0 : pw_guest_dgrad(guest, stream);
 }
+int dsgcn_pwconv_dgrad_ws(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                          const float* h2, int relu, const float* w, const float* z, const float* zaug,
+                          const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
+                          float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, const void* ws,
+                          void* stream) {
+  return dsgcn_pwconv_dgrad_ws_guest(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co,
+                                     T, V, stride, aug, ws, nullptr, nullptr, stream);
+}
+int dsgcn_pwconv_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
+                       const float* h2, int relu, const float* w, const float* z, const float* zaug,
+                       const float* gz, const float* gzaug, const float* A0, const float* B0, float* dx1, float* dx2,
+                       float* ipart, int n, int Ci, int Co, int T, int V, int stride, int aug, void* stream) {
+  return dsgcn_pwconv_dgrad_ws(x1, s1, h1, x2, s2, h2, relu, w, z, zaug, gz, gzaug, A0, B0, dx1, dx2, ipart, n, Ci, Co, T,
+                               V, stride, aug, nullptr, stream);
+}
 
-}  // extern "C"
-
-static int pw_dgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
-                    int relu, const float* w, const float* z, const float* zaug, const float* gz, const float* gzaug,
-                    const float* A0, const float* B0, float* dx1, float* dx2, float* ipart, int n, int Ci, int Co, int T,
-                    int V, int stride, int aug, const void* ws, const dsgcn_guest_conv* guest, int* hosted, void* stream) {
-  if (!x1 || !w || !dx1 || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0 || stride <= 0) return DSGCN_EINVAL;
-  if ((A0 && (!B0 || !z)) || (aug && A0 && !zaug) || (x2 && !dx2)) return DSGCN_EINVAL;
-  // dsgcn_pwconv_ipart_rows sizes `ipart` for the wide-load plan, which needs gz: a NULL gz would drop to the scalar
-  // kernels and their (larger) row count — refuse instead of writing past the caller's buffer
-  if (!gz && ipart) return DSGCN_EINVAL;
-  const int Tout = (T + stride - 1) / stride;
-  hipStream_t st = (hipStream_t)stream;
-  if (stride > 1) {
-    hipError_t e = hipMemsetAsync(dx1, 0, (size_t)n * Ci * T * V * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-    if (dx2) {
-      e = hipMemsetAsync(dx2, 0, (size_t)n * Ci * T * V * sizeof(float), st);
-      if (e != hipSuccess) return (int)e;
-    }
+// out (n,Co,T,V) = gz + A0 + B0*z + (gzaug + A0 + B0*zaug)/V   (gz, gzaug, A0/B0 may be NULL = zero)
+int dsgcn_dz_eff_aug(const float* gz, const float* z, const float* gzaug, const float* zaug, const float* A0,
+                     const float* B0, float* out, int n, int C, int T, int V, void* stream) {
+  if (!z || !zaug || !out || n <= 0 || C <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
+  if ((T * V) % 4 == 0 && T <= 8192) {
+    hipLaunchKernelGGL(k_dz_eff_aug4, dim3((unsigned)((long)n * C)), dim3(64), (size_t)T * 4, (hipStream_t)stream, gz, z,
+                       gzaug, zaug, A0, B0, out, C, T, V);
+    DSGCN_LAUNCH_CHECK();
+    return 0;
   }
-  PwBwdArgs a = {};
-  a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu; a.w = w;
-  a.z = z; a.zaug = zaug; a.gz = gz; a.gzaug = gzaug; a.A0 = A0; a.B0 = B0;
-  a.dx1 = dx1; a.dx2 = dx2; a.ipart = ipart;
-  a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug;
-  a.roll = ((g_pw_roll & 2) && Co % KW == 0 && (Ci & 3) == 0) ? 1 : 0;
-  const int L = Tout * V;
-  if (stride == 1 && !aug && (g_pw4 & 2)) {
-    const int fast = dsgcn_p4_dgrad(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, ipart, n, Ci, Co, L, st, ws,
-                                    guest, hosted);
-    if (fast == 1) return 0;
-    if (fast != 0) return fast;
-  }
-  // the first-generation kernels address the whole tensor with 32-bit byte offsets (the wide-load kernels above carry
-  // the sample base in the buffer resource): refuse what they cannot address instead of wrapping silently
-  if ((long)n * Ci * T * V * 4 >= (1L << 31) - 64 || (long)n * Co * T * V * 4 >= (1L << 31) - 64) return DSGCN_EUNSUPPORTED;
-  const int mtiles = (Ci + 31) / 32;
-  const int MT = mtiles >= g_pw_maxmt ? g_pw_maxmt : mtiles;
-  const int NW = 1;
-  const int nbx = (L + 4 * NW * 32 - 1) / (4 * NW * 32);
-  a.nbx = nbx;
-  a.cc = (mtiles + MT - 1) / MT;
-  dim3 grid((unsigned)(((long)nbx * n + 7) / 8 * 8 * a.cc));
-  size_t ldsf = (size_t)KW * (32 * MT + 1) + 4 + (size_t)2 * Co;
-  if (ldsf < (size_t)4 * 32 * 36 + 4 * 32 * 3) ldsf = (size_t)4 * 32 * 36 + 4 * 32 * 3;
-  const size_t lds = ldsf * sizeof(float);
-#define DSGCN_DGRAD(MTv, NWv)                                                                        \
-  do {                                                                                               \
-    if (aug) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, true, false, false>), grid, dim3(PW_NT), lds, st, a);   \
-    else if (a.roll) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, true, false>), grid, dim3(PW_NT), lds, st, a);   \
-    else if (g_pw_roll & 4) hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, false, (NWv == 1)>), grid, dim3(PW_NT), lds, st, a);      \
-    else hipLaunchKernelGGL((k_pwconv_dgrad2<MTv, NWv, false, false, false>), grid, dim3(PW_NT), lds, st, a);      \
-  } while (0)
-  switch (MT) {
-    case 1: DSGCN_DGRAD(1, 1); break;
-    case 2: DSGCN_DGRAD(2, 1); break;
-    case 3: DSGCN_DGRAD(3, 1); break;
-    default: DSGCN_DGRAD(4, 1); break;
-  }
-#undef DSGCN_DGRAD
+  hipLaunchKernelGGL(k_dz_eff_aug, dim3((unsigned)((long)n * C)), dim3(64), 0, (hipStream_t)stream, gz, z, gzaug, zaug,
+                     A0, B0, out, C, T, V);
   DSGCN_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" {
+// ---- backward, weight path ----
 
 // k-split plan of the weight gradient: returns the number of splits (size of dim 0 of dwp / dbp).
 int dsgcn_pwconv_wgrad_splits(int n, int Ci, int Co, int T, int V, int stride) {
-  const int Tout = (T + stride - 1) / stride;
-  if (stride == 1 && (g_pw4 & 4)) {
-    const int s = dsgcn_wg2_splits(n, Ci, Co, T * V);
-    if (s > 0) return s;
-  }
-  const int TR = Tout >= WG_TR ? WG_TR : Tout;
-  const int chunks = n * ((Tout + TR - 1) / TR);
-  const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
-  int splits = 512 / tiles;
-  if (splits < 1) splits = 1;
-  if (splits > chunks) splits = chunks;
-  const int per = (chunks + splits - 1) / splits;
-  return (chunks + per - 1) / per;
+  return pw_wgrad_splits(n, Ci, Co, T, V, stride);
 }
 
 // Backward, weight path.  Partial sums per k-split: split s writes dW at dwp + s*pstride (Co*Ci floats) and db at
@@ -1753,53 +1404,9 @@ int dsgcn_pwconv_wgrad_jobs(const float* x1, const float* s1, const float* h1, c
                         q.accumulate};
   }
   if (!bnj_coef_ok(jt)) return DSGCN_EINVAL;
-  if (stride == 1 && !aug && (g_pw4 & 4)) {
-    if (pstride < Co * Ci) return DSGCN_EINVAL;
-    const int fast = dsgcn_wg2(x1, s1, h1, x2, s2, h2, relu, z, gz, A0, B0, dwp, dbp, pstride, n, Ci, Co, T * V,
-                               (hipStream_t)stream, &jt);
-    if (fast == 1) return 0;
-    if (fast != 0) return fast;
-  }
-  if (njobs) {                                     // not hosted: one launch for the jobs, then the weight gradient
-    hipLaunchKernelGGL(k_bn_coef_rows_multi, dim3((unsigned)bnj_total_blocks(jt)), dim3(BNJ_NT), 0, (hipStream_t)stream, jt);
-    DSGCN_LAUNCH_CHECK();
-  }
-  // the first-generation kernels address the whole tensor with 32-bit byte offsets (the wide-load kernels above carry
-  // the sample base in the buffer resource): refuse what they cannot address instead of wrapping silently
-  if ((long)n * Ci * T * V * 4 >= (1L << 31) - 64 || (long)n * Co * T * V * 4 >= (1L << 31) - 64) return DSGCN_EUNSUPPORTED;
-  const int Tout = (T + stride - 1) / stride;
-  const int TR = Tout >= WG_TR ? WG_TR : Tout;
-  if (TR * V > 16 * WG_J) return DSGCN_EUNSUPPORTED;
-  PwBwdArgs a = {};
-  a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu;
-  a.z = z; a.zaug = zaug; a.gz = gz; a.gzaug = gzaug; a.A0 = A0; a.B0 = B0; a.dwp = dwp; a.dbp = dbp;
-  a.pstride = pstride;
-  if (pstride < Co * Ci) return DSGCN_EINVAL;
-  a.n = n; a.Ci = Ci; a.Co = Co; a.T = T; a.V = V; a.Tout = Tout; a.stride = stride; a.aug = aug; a.TR = TR;
-  a.nb_per_sample = (Tout + TR - 1) / TR;
-  a.total_chunks = n * a.nb_per_sample;
-  a.vec = (stride == 1 && (T * V) % 4 == 0 && (Tout * V) % 4 == 0 && (TR * V) % 4 == 0 &&
-           ((Tout % TR) * V) % 4 == 0) ? 1 : 0;
-  const int splits = dsgcn_pwconv_wgrad_splits(n, Ci, Co, T, V, stride);
-  a.chunks_per_split = (a.total_chunks + splits - 1) / splits;
-  const int KP = (TR * V + 1) & ~1;
-  const int LS = KP | 1;
-  const size_t lds = (size_t)2 * 64 * LS * sizeof(float);
-  dim3 grid((unsigned)((Co + 63) / 64), (unsigned)((Ci + 63) / 64), (unsigned)splits);
-  a.nbx = a.cc = 0;
-  if (grid.x * grid.y > 1 && splits % 8 == 0 && (g_pw_roll & 8)) {
-    a.nbx = (int)grid.x; a.cc = (int)grid.y;
-    grid = dim3(grid.x * grid.y * (unsigned)splits);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  if (a.vec && x2) hipLaunchKernelGGL((k_pwconv_wgrad<true, true>), grid, dim3(PW_NT), lds, st, a);
-  else if (a.vec) hipLaunchKernelGGL((k_pwconv_wgrad<true, false>), grid, dim3(PW_NT), lds, st, a);
-  else if (x2) hipLaunchKernelGGL((k_pwconv_wgrad<false, true>), grid, dim3(PW_NT), lds, st, a);
-  else hipLaunchKernelGGL((k_pwconv_wgrad<false, false>), grid, dim3(PW_NT), lds, st, a);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
+  return pw_wgrad(KcIn{x1, s1, h1, x2, s2, h2, relu}, KcDz{z, gz, A0, B0}, zaug, gzaug, dwp, dbp, pstride, n, Ci, Co, T, V,
+                  stride, aug, jt, stream);
 }
-
 int dsgcn_pwconv_wgrad(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                        const float* h2, int relu, const float* z, const float* zaug, const float* gz,
                        const float* gzaug, const float* A0, const float* B0, float* dwp, float* dbp, int pstride, int n,
@@ -1808,50 +1415,7 @@ int dsgcn_pwconv_wgrad(const float* x1, const float* s1, const float* h1, const 
                                  stride, aug, nullptr, 0, stream);
 }
 
-// out (n,Co,T,V) = gz + A0 + B0*z + (gzaug + A0 + B0*zaug)/V   (gz, gzaug, A0/B0 may be NULL = zero)
-int dsgcn_dz_eff_aug(const float* gz, const float* z, const float* gzaug, const float* zaug, const float* A0,
-                     const float* B0, float* out, int n, int C, int T, int V, void* stream) {
-  if (!z || !zaug || !out || n <= 0 || C <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
-  if ((T * V) % 4 == 0 && T <= 8192) {
-    hipLaunchKernelGGL(k_dz_eff_aug4, dim3((unsigned)((long)n * C)), dim3(64), (size_t)T * 4, (hipStream_t)stream, gz, z,
-                       gzaug, zaug, A0, B0, out, C, T, V);
-    DSGCN_LAUNCH_CHECK();
-    return 0;
-  }
-  hipLaunchKernelGGL(k_dz_eff_aug, dim3((unsigned)((long)n * C)), dim3(64), 0, (hipStream_t)stream, gz, z, gzaug, zaug,
-                     A0, B0, out, C, T, V);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-int dsgcn_bn_bwd_coef(const float* g_scale, const float* g_shift, const float* mean, const float* var,
-                      const float* gamma, float eps, double count, int C, int c_affine, float* dgamma, float* dbeta,
-                      float* A0, float* B0, void* stream) {
-  if (!mean || !var || !dgamma || !dbeta || !A0 || !B0 || C <= 0) return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_bn_bwd_coef, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, g_scale,
-                     g_shift, mean, var, gamma, eps, count, C, c_affine, dgamma, dbeta, A0, B0);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-// coef (4, C) = [d gamma | d beta | A0 | B0] from partial rows part (R, C, k): column i_ds holds a consumer's partial
-// sums of d scale, column i_dh of d shift.  accumulate != 0: added to the coefficients already in coef (a second consumer
-// of the same deferred BatchNorm).
-int dsgcn_bn_coef_rows(const float* part, int R, int C, int k, int i_ds, int i_dh, const float* mean, const float* var,
-                       const float* gamma, float eps, double count, int c_affine, float* coef, int accumulate,
-                       void* stream) {
-  if (!part || !mean || !var || !coef || R <= 0 || C <= 0 || k <= 0 || i_ds < 0 || i_ds >= k || i_dh < 0 || i_dh >= k)
-    return DSGCN_EINVAL;
-  hipLaunchKernelGGL(k_bn_coef_rows, dim3((unsigned)((C + 7) / 8)), dim3(1024), 0, (hipStream_t)stream, part, R, C, k, i_ds,
-                     i_dh, mean, var, gamma, eps, count, c_affine, coef, accumulate);
-  DSGCN_LAUNCH_CHECK();
-  return 0;
-}
-
-}  // extern "C"
-
-
-extern "C" {
+// ---- one-pass backward ----
 
 // Fused backward (data gradient + weight gradient + input-affine partial sums in one pass over gz, z and the input) for
 // narrow convs: stride 1, no global-joint column, Ci and Co <= 64, T*V % 4 == 0 (one or two input streams).
@@ -1862,19 +1426,7 @@ int dsgcn_pwconv_bwd_rows(int n, int Ci, int Co, int T, int V, int stride) {
   return dsgcn_bwd64_splits(n, Ci, Co, T * V);
 }
 
-int dsgcn_pwconv_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
-                     int relu, const float* w, const float* z, const float* gz, const float* A0, const float* B0,
-                     float* dx1, float* dx2, float* ipart, float* dwp, float* dbp, int pstride, int n, int Ci, int Co,
-                     int T, int V, void* stream) {
-  if (!x1 || !w || !gz || !dx1 || !dwp || !dbp || n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return DSGCN_EINVAL;
-  if ((A0 && (!B0 || !z)) || (s1 && !h1) || (s2 && !h2) || (x2 && !dx2) || pstride < Co * Ci) return DSGCN_EINVAL;
-  const int rc = dsgcn_bwd64(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, dwp, dbp, pstride, ipart, n, Ci, Co,
-                             T * V, (hipStream_t)stream, nullptr, nullptr);
-  if (rc == 1) return 0;
-  return rc == 0 ? DSGCN_EUNSUPPORTED : rc;
-}
-
-// dsgcn_pwconv_bwd with a guest data gradient in its leading workgroups (see dsgcn_pwconv_dgrad_ws_guest)
+// guest: NULL, or a guest data gradient for the launch's leading workgroups (see dsgcn_pwconv_dgrad_ws_guest)
 int dsgcn_pwconv_bwd_guest(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2,
                            const float* h2, int relu, const float* w, const float* z, const float* gz, const float* A0,
                            const float* B0, float* dx1, float* dx2, float* ipart, float* dwp, float* dbp, int pstride, int n,
@@ -1884,12 +1436,69 @@ int dsgcn_pwconv_bwd_guest(const float* x1, const float* s1, const float* h1, co
   if ((A0 && (!B0 || !z)) || (s1 && !h1) || (s2 && !h2) || (x2 && !dx2) || pstride < Co * Ci) return DSGCN_EINVAL;
   if (!pw_guest_ok(guest)) return DSGCN_EINVAL;
   int took = 0;
-  const int rc = dsgcn_bwd64(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, dwp, dbp, pstride, ipart, n, Ci, Co,
-                             T * V, (hipStream_t)stream, guest, &took);
+  const int rc = dsgcn_bwd64(KcIn{x1, s1, h1, x2, s2, h2, relu}, w, KcDz{z, gz, A0, B0}, dx1, dx2, dwp, dbp, pstride, ipart, n,
+                             Ci, Co, T * V, (hipStream_t)stream, guest, &took);
   if (rc != 1) return rc == 0 ? DSGCN_EUNSUPPORTED : rc;
   if (!guest) return 0;
   if (hosted) *hosted = took;
   return took ? 0 : pw_guest_dgrad(guest, stream);
+}
+int dsgcn_pwconv_bwd(const float* x1, const float* s1, const float* h1, const float* x2, const float* s2, const float* h2,
+                     int relu, const float* w, const float* z, const float* gz, const float* A0, const float* B0,
+                     float* dx1, float* dx2, float* ipart, float* dwp, float* dbp, int pstride, int n, int Ci, int Co,
+                     int T, int V, void* stream) {
+  return dsgcn_pwconv_bwd_guest(x1, s1, h1, x2, s2, h2, relu, w, z, gz, A0, B0, dx1, dx2, ipart, dwp, dbp, pstride, n, Ci, Co,
+                                T, V, nullptr, nullptr, stream);
+}
+
+// ---- grouped convs ----
+
+// Up to three 1x1 convs of ONE shape in one launch each way (host arrays of ngroup device pointers): z_g = W_g . (x1_g * s1_g +
+// h1_g), no bias / second stream / statistics, stride 1 — CTR-GCN's three conv4's per unit (gcn.py:655-657, one per subset),
+// each of which alone leaves the chip under-filled.  dsgcn_pwconv_group_ok: 1 when the shape takes the grouped form (else
+// the caller launches the convs one by one); the data gradient writes dx1_g and the input-scale rows ipart_g
+// (dsgcn_pwconv_ipart_rows, or NULL for all).
+int dsgcn_pwconv_group_ok(int n, int Ci, int Co, int T, int V) {
+  if (n <= 0 || Ci <= 0 || Co <= 0 || T <= 0 || V <= 0) return 0;
+  return ((g_pw4 & 3) == 3) ? dsgcn_p4_group_ok(n, Ci, Co, T * V) : 0;
+}
+
+int dsgcn_pwconv_fwd_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
+                           const float* const* w, float* const* z, int ngroup, int n, int Ci, int Co, int T, int V,
+                           void* stream) {
+  if (!x1 || !s1 || !h1 || !w || !z || !pw_group_dims_ok(ngroup, n, Ci, Co, T, V)) return DSGCN_EINVAL;
+  for (int g = 0; g < ngroup; ++g)
+    if (!x1[g] || !w[g] || !z[g] || ((s1[g] == nullptr) != (h1[g] == nullptr))) return DSGCN_EINVAL;
+  if (!dsgcn_pwconv_group_ok(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
+  const int rc = dsgcn_p4_fwd_group(x1, s1, h1, relu, w, z, ngroup, n, Ci, Co, T * V, (hipStream_t)stream);
+  return rc == 1 ? 0 : (rc == 0 ? DSGCN_EUNSUPPORTED : rc);
+}
+
+int dsgcn_pwconv_dgrad_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
+                             const float* const* w, const float* const* gz, float* const* dx1, float* const* ipart,
+                             int ngroup, int n, int Ci, int Co, int T, int V, void* stream) {
+  if (!x1 || !s1 || !h1 || !w || !gz || !dx1 || !ipart || !pw_group_dims_ok(ngroup, n, Ci, Co, T, V)) return DSGCN_EINVAL;
+  for (int g = 0; g < ngroup; ++g)
+    if (!x1[g] || !w[g] || !gz[g] || !dx1[g] || ((s1[g] == nullptr) != (h1[g] == nullptr))) return DSGCN_EINVAL;
+  if (!dsgcn_pwconv_group_ok(n, Ci, Co, T, V)) return DSGCN_EUNSUPPORTED;
+  const int rc = dsgcn_p4_dgrad_group(x1, s1, h1, relu, w, gz, dx1, ipart, ngroup, n, Ci, Co, T * V, (hipStream_t)stream);
+  return rc == 1 ? 0 : (rc == 0 ? DSGCN_EUNSUPPORTED : rc);
+}
+
+// the weight gradients of the same group (dwp_g / dbp_g: partial rows as dsgcn_pwconv_wgrad, dsgcn_pwconv_wgrad_splits rows each)
+int dsgcn_pwconv_wgrad_group(const float* const* x1, const float* const* s1, const float* const* h1, int relu,
+                             const float* const* gz, float* const* dwp, float* const* dbp, int pstride, int ngroup, int n,
+                             int Ci, int Co, int T, int V, void* stream) {
+  if (!x1 || !s1 || !h1 || !gz || !dwp || !dbp || !pw_group_dims_ok(ngroup, n, Ci, Co, T, V)) return DSGCN_EINVAL;
+  for (int g = 0; g < ngroup; ++g)
+    if (!x1[g] || !gz[g] || !dwp[g] || !dbp[g] || ((s1[g] == nullptr) != (h1[g] == nullptr)) ||
+        ((s1[g] == nullptr) != (s1[0] == nullptr)))
+      return DSGCN_EINVAL;
+  if (pstride < Co * Ci || !(g_pw4 & 4)) return pstride < Co * Ci ? DSGCN_EINVAL : DSGCN_EUNSUPPORTED;
+  BnCoefTable none = {};
+  const int fast = dsgcn_wg2(KcIn{x1[0], s1[0], h1[0], nullptr, nullptr, nullptr, relu}, KcDz{nullptr, gz[0]}, dwp[0], dbp[0],
+                             pstride, n, Ci, Co, T * V, (hipStream_t)stream, &none, ngroup, x1, s1, h1, gz, dwp, dbp);
+  return fast == 1 ? 0 : (fast == 0 ? DSGCN_EUNSUPPORTED : fast);
 }
 
 }  // extern "C"

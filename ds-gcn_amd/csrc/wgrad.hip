@@ -9,8 +9,7 @@
 // (TM/2)x(TN/2) block of the workgroup's TMxTN output tile (up to 2x2 MFMA tiles: one LDS read per MFMA instead of the
 // two of the first version, and a 128x128 tile reads each operand row once for 128 output columns instead of 64).
 // K (positions) is split over workgroups; each split writes its partial dW / db (deterministic: summed by dsgcn_colsum).
-#include "common.h"
-#include "bn_jobs.h"
+#include "kc.h"
 
 namespace {
 
@@ -647,7 +646,7 @@ void wg3_launch(const Wg2Args& a, bool has2, bool hasc, dim3 grid, size_t lds, h
 
 }  // namespace
 
-__attribute__((visibility("hidden"))) int dsgcn_wg2_tuning(int key, int value) {
+int dsgcn_wg2_tuning(int key, int value) {
   if (key == 0) g_wg2_target4 = value;
   else if (key == 1) g_wg2_kc128 = value;
   else if (key == 2) g_wg2_target1 = value;
@@ -659,46 +658,41 @@ __attribute__((visibility("hidden"))) int dsgcn_wg2_tuning(int key, int value) {
   return 0;
 }
 
-// Internal (not exported): K-split count of the fast weight gradient for this shape, 0 = not eligible.
-__attribute__((visibility("hidden"))) int dsgcn_wg2_splits(int n, int Ci, int Co, int L) {
+// Internal (hidden, kc.h): K-split count of the fast weight gradient for this shape, 0 = not eligible.
+int dsgcn_wg2_splits(int n, int Ci, int Co, int L) {
   Wg2Plan p;
   return wg2_plan(n, Ci, Co, L, &p) ? p.splits : 0;
 }
 
 // bf16 products per fp32 product of the fast weight gradient of this shape under the current precision level: 6 / 3 = the
 // B3 tile of k_wg2 or k_wg3 (k_wg2h / k_wg3h), 0 = an fp32 MFMA tile or not eligible
-__attribute__((visibility("hidden"))) int dsgcn_wg2_terms(int n, int Ci, int Co, int L) {
+int dsgcn_wg2_terms(int n, int Ci, int Co, int L) {
   Wg2Plan p;
   if (!wg2_plan(n, Ci, Co, L, &p) || !p.b3) return 0;
   return dsgcn_precision_level() == 1 ? 3 : 6;
 }
 
 // Returns 1 = launched, 0 = not eligible (caller falls back), other = error.
-__attribute__((visibility("hidden"))) int dsgcn_wg2(const float* x1, const float* s1, const float* h1, const float* x2,
-                                                     const float* s2, const float* h2, int relu, const float* z,
-                                                     const float* gz, const float* A0, const float* B0, float* dwp,
-                                                     float* dbp, int pstride, int n, int Ci, int Co, int L,
-                                                     hipStream_t st, const BnCoefTable* jobs, int ngroup,
-                                                     const float* const* gx1, const float* const* gs1,
-                                                     const float* const* gh1, const float* const* ggz, float* const* gdwp,
-                                                     float* const* gdbp) {
+int dsgcn_wg2(const KcIn& in, const KcDz& d, float* dwp, float* dbp, int pstride, int n, int Ci, int Co, int L, hipStream_t st,
+              const BnCoefTable* jobs, int ngroup, const float* const* gx1, const float* const* gs1, const float* const* gh1,
+              const float* const* ggz, float* const* gdwp, float* const* gdbp) {
   Wg2Plan p;
   if (!wg2_plan(n, Ci, Co, L, &p)) return 0;
   Wg2Args a = {};
   if (jobs) a.jobs = *jobs;
   if (ngroup > 1) {
-    if (ngroup > 3 || x2 || A0) return 0;
+    if (ngroup > 3 || in.x2 || d.A0) return 0;
     a.ngroup = ngroup;
     for (int g = 0; g < ngroup; ++g) a.g[g] = Wg2Args::Grp{gx1[g], gs1[g], gh1[g], ggz[g], gdwp[g], gdbp[g]};
   }
-  a.x1 = x1; a.s1 = s1; a.h1 = h1; a.x2 = x2; a.s2 = s2; a.h2 = h2; a.relu = relu;
-  a.z = z; a.gz = gz; a.A0 = A0; a.B0 = B0; a.dwp = dwp; a.dbp = dbp; a.pstride = pstride;
+  a.x1 = in.x1; a.s1 = in.s1; a.h1 = in.h1; a.x2 = in.x2; a.s2 = in.s2; a.h2 = in.h2; a.relu = in.relu;
+  a.z = d.z; a.gz = d.gz; a.A0 = d.A0; a.B0 = d.B0; a.dwp = dwp; a.dbp = dbp; a.pstride = pstride;
   a.n = n; a.Ci = Ci; a.Co = Co; a.L = L; a.cpn = p.cpn; a.total_chunks = p.chunks; a.cps = p.cps;
   a.tm_tiles = p.tm_tiles; a.tn_tiles = p.tn_tiles;
   const int tiles = p.tm_tiles * p.tn_tiles;
   a.main_blocks = tiles > 1 ? (p.splits + 7) / 8 * 8 * tiles : p.splits;
   const dim3 grid((unsigned)(a.main_blocks + bnj_total_blocks(a.jobs)), ngroup > 1 ? (unsigned)ngroup : 1u);
-  const bool has2 = x2 != nullptr, hasc = A0 != nullptr;
+  const bool has2 = in.x2 != nullptr, hasc = d.A0 != nullptr;
   const bool high = dsgcn_precision_level() == 1;  // (read here, on the host: a captured launch keeps its kernel)
   if (p.v3) {
 #ifdef DSGCN_LAB                                   // the full 256 x 256 tile (key 17 = 256) measured slower in the step: lab builds only

@@ -116,7 +116,8 @@ def digest(lib=DEFAULT_LIB):
         for i, path in enumerate(paths):
             ks = notes(path)
             for sym, lines in symbols(path).items():
-                text = '\n'.join(re.sub(r'// [0-9A-F]+:', '//', line) for line in lines)
+                # ('...' = the zero padding up to the next symbol, which the last symbol of a code object lacks: no instruction)
+                text = '\n'.join(re.sub(r'// [0-9A-F]+:', '//', line) for line in lines if line.strip() != '...')
                 figures = ' '.join(f"{k}={ks.get(sym, {}).get(k, '-')}" for k in DIGEST_FIELDS)
                 out.append(f'{i:02d} {sym} {hashlib.sha256(text.encode()).hexdigest()} {figures}')
     return out
