@@ -9,7 +9,7 @@ from .config import Config, ConfigDict
 from .graph import Graph
 from .builder import (MODELS, BACKBONES, HEADS, LOSSES, NECKS, RECOGNIZERS, build_backbone, build_head, build_loss,
                       build_model, build_recognizer)
-from .evaluation import top_k_accuracy, mean_class_accuracy, confusion_matrix
+from .evaluation import top_k_accuracy, mean_class_accuracy, confusion_matrix, class_mean_graphs
 from .losses import CrossEntropyLoss
 from .heads import GCNHead, SimpleHead
 from .gcn_units import dggcn, dghgcn, dgphgcn1, unit_aagcn, unit_gcn, unit_ctrgcn, unit_ctrhgcn, CTRGC, CTRHGC, Deferred

@@ -540,7 +540,8 @@ class EvalLoop:
     def predict(self, model, rank, world):
         """This rank's share of the val scores, in its sampler order.  Under ``test_cfg['feat_ext']`` / ``['score_ext']``:
         one float16 array per video, what ``forward_test`` returns for that video alone (mmcv's ``results.extend(result)``
-        would split that array on its first axis; not reproduced)."""
+        would split that array on its first axis; not reproduced).  Under ``test_cfg['graph_ext']``: one float32
+        ``(L, K, V, V)`` array per video."""
         if self.engine is not None and self.engine.model is not model:
             raise ValueError('EvalLoop(engine=...): the engine was built over another model')
         if self.matmul_precision is not None and self.engine is None:
@@ -556,6 +557,7 @@ class EvalLoop:
         model.eval()
         part, on_device = [], []
         ext = model.extraction() if hasattr(model, 'extraction') else None
+        graphs = hasattr(model, 'graph_extraction') and model.graph_extraction() is not None
         # the reference samples val clips in loader worker processes: the test-mode sampler's np.random.seed(255) never
         # touches the TRAINING process's stream.  Here both run in one process, so the stream is put back afterwards.
         rng = np.random.get_state()
@@ -564,7 +566,7 @@ class EvalLoop:
                 kp, _ = self.source.batch(order[b:b + self.batch_size])
                 if self.engine is not None:
                     on_device.append(self.engine(kp))
-                elif ext is not None:                             # forward_test extracts from one video per call
+                elif ext is not None or graphs:                   # forward_test extracts from one video per call
                     part.extend(model(keypoint=kp[i:i + 1], return_loss=False) for i in range(len(kp)))
                 else:
                     part.extend(model(keypoint=kp, return_loss=False))
@@ -604,6 +606,8 @@ class EvalLoop:
             return None
         if hasattr(runner.model, 'extraction') and runner.model.extraction() is not None:
             raise ValueError("validation scores classes: test_cfg['feat_ext'] / ['score_ext'] belong to test_model")
+        if hasattr(runner.model, 'graph_extraction') and runner.model.graph_extraction() is not None:
+            raise ValueError("validation scores classes: test_cfg['graph_ext'] belongs to test_model")
         self.sync_bn_buffers(runner.model, runner.world)
         part = self.predict(runner.model, runner.rank, runner.world)
         scores = gather_results(part, len(self.source))

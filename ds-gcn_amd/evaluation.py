@@ -1,7 +1,9 @@
 """Accuracy metrics used on the training / validation path.  Contract: pyskl/core/evaluation.py:21-126 — ``top_k_accuracy``
 (a sample counts when its label is among the k best scores), ``confusion_matrix`` (rows = true class, columns = predicted,
 over the classes that OCCUR in either list, in sorted order), ``mean_class_accuracy`` (this fork returns the pair
-(mean of the per-class recalls over those classes, confusion matrix); datasets/base.py:194,201 unpacks it)."""
+(mean of the per-class recalls over those classes, confusion matrix); datasets/base.py:194,201 unpacks it).
+``class_mean_graphs``: the reference's ``metric='graph'`` (datasets/base.py:214-223) over the per-video learned adjacencies of
+``test_cfg['graph_ext']``."""
 import numpy as np
 
 
@@ -42,3 +44,24 @@ def mean_class_accuracy(scores, labels):
     seen = counts.sum(axis=1)
     recall = np.divide(np.diag(counts), seen, out=np.zeros_like(seen), where=seen > 0)
     return float(recall.mean()), counts
+
+
+def class_mean_graphs(results, labels):
+    """The reference's ``evaluate(metric='graph')`` (datasets/base.py:214-223): ``results`` — one ``(L, K, V, V)`` array per
+    video — and integer ``labels`` -> a list whose entry i is the mean graph of the videos of class i, float32.
+
+    Two quirks of the reference loop ``for i in range(max(label))`` are kept: the list has ``max(labels)`` entries, so the
+    LAST class (the largest label that occurs) is left out, and a class below it without a video gives an all-NaN entry
+    (the mean of nothing), not a missing one."""
+    graphs = np.stack([np.asarray(r, dtype=np.float32) for r in results])
+    labels = np.asarray(labels).reshape(-1)
+    if len(labels) != len(graphs):
+        raise ValueError(f'class_mean_graphs: {len(graphs)} results, {len(labels)} labels')
+    out = []
+    for i in range(int(labels.max())):
+        rows = graphs[labels == i]
+        if len(rows):
+            out.append(rows.mean(0, dtype=np.float32))
+        else:
+            out.append(np.full(graphs.shape[1:], np.nan, dtype=np.float32))
+    return out

@@ -135,6 +135,7 @@ def _adjacency_unit_chain(unit, x, xbar, x_res, pad, batch_tail=False):
     if xbar is None:
         xbar = ops.tmean(x, 32) if pad else ops.tmean(x)
     ahat = unit.adjacency(xbar)
+    kernels.graph_tap(unit, xbar, ahat)
     zp, _, ap = conv_bn(x, None, None, None, False, unit.pre[0], 1, False, unit.pre[1])
     y = ops.aggregate(zp, ap, True, ahat)
     if unit.down is None:
@@ -264,17 +265,19 @@ class dgphgcn1(nn.Module):
         c1, c2, cs = self.conv1, self.conv2, self.conv1_se
         return ([c1.weight.flatten(1), c2.weight.flatten(1), cs.weight.flatten(1)], [c1.bias, c2.bias, cs.bias])
 
-    def adjacency(self, xbar, host=None, proj_req=None):
+    def adjacency(self, xbar, host=None, proj_req=None, beta=None):
         """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V).  host: a kernels.bn_batch whose waiting
         finalize jobs K-B's launch carries (shipped flag set only); proj_req: the projections' request that an earlier
-        launch has carried (kernels._proj_guest_request of the same xbar)."""
+        launch has carried (kernels._proj_guest_request of the same xbar).  beta: a tensor to stand for ``self.beta`` (the
+        graph collector's zero: kernels.graph_collect, mode 'ctr')."""
         c1, c2 = self.conv1, self.conv2
+        beta = self.beta if beta is None else beta
         if not self._shipped:
             cs = self.conv1_se if self.decompose else None
             el = self.edge_linears if self.decompose and self.edge_attention else None
             al = self.ada_linears if self.ada_attention else None
             return kernels.ops().dynadj_flags(
-                xbar, self.A, self.alpha, self.beta, c1.weight.flatten(1), c1.bias, c2.weight.flatten(1), c2.bias,
+                xbar, self.A, self.alpha, beta, c1.weight.flatten(1), c1.bias, c2.weight.flatten(1), c2.bias,
                 None if cs is None else cs.weight.flatten(1), None if cs is None else cs.bias,
                 None if el is None else el.weight.flatten(1), None if el is None else el.bias,
                 None if al is None else al.weight.flatten(1), None if al is None else al.bias,
@@ -286,7 +289,7 @@ class dgphgcn1(nn.Module):
             self._kb_trains = kernels.native.lib().dsgcn_dynadj_supported(1, self.mid_channels, V, max(V, 32),
                                                                           self.edge_num, 1) == 0
         if not self._kb_trains and torch.is_grad_enabled() and (xbar.requires_grad or any(p.requires_grad for p in (
-                self.A, self.alpha, self.beta, c1.weight, c1.bias, c2.weight, c2.bias, cs.weight, cs.bias, el.weight, el.bias))):
+                self.A, self.alpha, beta, c1.weight, c1.bias, c2.weight, c2.bias, cs.weight, cs.bias, el.weight, el.bias))):
             # (raises: the call would record a backward that cannot launch; the same unit evaluates under no_grad)
             kernels.native.dynadj_require_backward(self.mid_channels, self.A.shape[-1], self.edge_num,
                                                    max(32, self.A.shape[-1]), 'dgphgcn1')
@@ -294,7 +297,7 @@ class dgphgcn1(nn.Module):
         if proj_req is not None:
             kw['proj_req'] = proj_req
         return kernels.ops().dynadj(
-            xbar, self.A, self.alpha, self.beta,
+            xbar, self.A, self.alpha, beta,
             c1.weight.flatten(1), c1.bias, c2.weight.flatten(1), c2.bias, cs.weight.flatten(1), cs.bias,
             el.weight.flatten(1), el.bias, self.node_type_idx, self.edge_type_idx, **kw)
 
@@ -323,14 +326,17 @@ class dgphgcn1(nn.Module):
             ctxbn = getattr(ap[0], '_dsgcn_bn', None)
             if ctxbn is not None:
                 ctxbn.host = True
+            kernels.graph_tap(self, xbar, ahat)
         elif fork is None:
             ahat = self.adjacency(xbar)
+            kernels.graph_tap(self, xbar, ahat)
             zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
         else:
             with fork(x) as br:                    # K-B beside the `pre` channel mix (independent until K-A)
                 ahat = self.adjacency(xbar)
             zp, _, ap = conv_bn(x, None, None, None, False, self.pre[0], 1, False, self.pre[1])
             br.join(ahat)
+            kernels.graph_tap(self, xbar, ahat)
         y = ops.aggregate(zp, ap, True, ahat)
         if self.down is None:
             zo, _, ao = conv_bn(y, None, None, None, False, self.post, 1, False, self.bn)
@@ -413,20 +419,22 @@ class dggcn(nn.Module):
     def fusable_pairs(self):
         return [(self.post, self.bn)]
 
-    def adjacency(self, xbar):
-        """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V)."""
+    def adjacency(self, xbar, beta=None):
+        """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V).  beta: a tensor to stand for ``self.beta``
+        (the graph collector's zero: kernels.graph_collect, mode 'ctr')."""
+        beta = self.beta if beta is None else beta
         m, Ci = self.mid_channels, self.in_channels
         w1, b1 = self.conv1.weight.flatten(1), self.conv1.bias
         w2, b2 = self.conv2.weight.flatten(1), self.conv2.bias
         K = self.num_subsets
         if K != 3:
             a = self.alpha if self.subset_wise else self.alpha[0].expand(K)
-            b = self.beta if self.subset_wise else self.beta[0].expand(K)
+            b = beta if self.subset_wise else beta[0].expand(K)
             return kernels.ops().dynadj_plain(xbar, self.A, a, b, w1, b1, w2, b2)
         zw, zb = w1.new_zeros(m, Ci), b1.new_zeros(m)
         we, be = self._we_eye, zb
         a = self.alpha if self.subset_wise else self.alpha[0].expand(3)
-        b = self.beta if self.subset_wise else self.beta[0].expand(3)
+        b = beta if self.subset_wise else beta[0].expand(3)
         dyn = kernels.ops().dynadj
         # subsets 0 and 1: slots (a0, b0) and (a1, b1) of one call (its third, node-typed slot is fed zeros and dropped)
         first = dyn(xbar, self.A, a, b, w1[:2 * m], b1[:2 * m], w2[:2 * m], b2[:2 * m], zw, zb, we, be, self._nt0, self._et0,
@@ -523,10 +531,12 @@ class dghgcn(nn.Module):
     def fusable_pairs(self):
         return [(self.post, self.bn)]
 
-    def adjacency(self, xbar):
-        """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V or 32)."""
+    def adjacency(self, xbar, beta=None):
+        """Ahat (n, K*mid, V, V) from the time-averaged input xbar (n, Ci, V or 32).  beta: a tensor to stand for
+        ``self.beta`` (the graph collector's zero: kernels.graph_collect, mode 'ctr')."""
+        beta = self.beta if beta is None else beta
         a = self.alpha if self.subset_wise else self.alpha[0].expand(3)
-        b = self.beta if self.subset_wise else self.beta[0].expand(3)
+        b = beta if self.subset_wise else beta[0].expand(3)
         el = self.edge_linears if self.edge_attention else None
         return kernels.ops().dynadj_typed(
             xbar, self.A, a, b, self.conv1.weight.flatten(1), self.conv1.bias, self.conv2.weight.flatten(1),

@@ -10,7 +10,8 @@ pass (reference: ``RecognizerGCN.forward_test``, pyskl/models/recognizers/recogn
 
 Under ``test_cfg['feat_ext']`` / ``['score_ext']`` the tail of the graph is ``kernels.feat_ext`` instead (the pooled last
 block when frames and joints are both averaged, the whole activation otherwise), any number of videos per call, each
-pooled by itself.  Either way the engine hands back DEVICE tensors: nothing in a call waits for the GPU, the caller reads back when it wants to (``test_model``:
+pooled by itself.  Under ``test_cfg['graph_ext']`` the graph is the backbone with the units' adjacency taps
+(``RecognizerGCN.forward_graphs``) and the result the per-video graphs (N, L, K, V, V).  Either way the engine hands back DEVICE tensors: nothing in a call waits for the GPU, the caller reads back when it wants to (``test_model``:
 once per pass)."""
 import torch
 
@@ -46,7 +47,7 @@ class InferEngine:
 
     def reset(self):
         """Forget every captured graph, static buffer and weight image (after a structural change of the model)."""
-        self._graphs = {}          # (shape, dtype, average_clips, extraction) -> (graph, static input, static output)
+        self._graphs = {}          # (shape, dtype, average_clips, extraction, graph mode) -> (graph, static input, static output)
         self._seen = {}            # same key -> eager calls taken
         self._images.clear()
         self.use_graph = self._want_graph
@@ -61,6 +62,8 @@ class InferEngine:
     # ---- pieces --------------------------------------------------------------------------------------------
     def _forward(self, x):
         model = self.model
+        if model.graph_extraction() is not None:
+            return model.forward_graphs(x)
         if model.extraction() is not None:
             return model.forward_extract(x)
         N, clips, M = x.shape[:3]
@@ -87,7 +90,8 @@ class InferEngine:
         return g, sx, out
 
     def _key(self, x):
-        return tuple(x.shape), x.dtype, self.model.test_cfg['average_clips'], self.model.extraction()
+        return (tuple(x.shape), x.dtype, self.model.test_cfg['average_clips'], self.model.extraction(),
+                self.model.graph_extraction())
 
     def _run(self, x):
         key = self._key(x)
@@ -121,7 +125,8 @@ class InferEngine:
     def __call__(self, keypoint):
         """keypoint (N, clips, M, T, V, C) on the device -> DEVICE tensor (N, classes) — (N, clips, classes) when the
         model's ``test_cfg['average_clips']`` is None; float16 (N, n', m', C | classes, t', v') under ``feat_ext`` /
-        ``score_ext`` (row i: what ``forward_test`` returns for video i alone).  No host synchronisation."""
+        ``score_ext`` (row i: what ``forward_test`` returns for video i alone); float32 (N, L, K, V, V) under ``graph_ext``.
+        No host synchronisation."""
         if keypoint.dim() != 6:
             raise ValueError(f'InferEngine expects (N, clips, M, T, V, C), got {tuple(keypoint.shape)}')
         if not keypoint.is_cuda:
@@ -178,6 +183,8 @@ class EnsembleEngine:
                 raise ValueError(f'EnsembleEngine: model {i} is not a RecognizerGCN with a GCNHead over a pooling backbone')
             if m.extraction() is not None:
                 raise ValueError(f'EnsembleEngine: model {i}: test_cfg feat_ext / score_ext has no weighted sum')
+            if m.graph_extraction() is not None:
+                raise ValueError(f'EnsembleEngine: model {i}: test_cfg graph_ext has no weighted sum')
         h0 = self.models[0].cls_head
         for i, m in enumerate(self.models):
             if m.cls_head.num_classes != h0.num_classes or m.cls_head.in_c != h0.in_c:

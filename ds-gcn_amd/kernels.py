@@ -3097,6 +3097,8 @@ from .kernels_plain import dynadj_plain  # noqa: E402,F401
 # the ops of the test pass (csrc/head_test.hip's front, the engine-owned weight-image table) live in a module of their own
 from .kernels_infer import (ENSEMBLE_MAX, feat_ext, feat_ext_shape, head_ensemble, head_ensemble_fits,  # noqa: E402,F401
                             head_test, head_test_fits, parse_pool_opt, private_weight_images)
+# ... and the per-video learned adjacency of test_cfg['graph_ext'] (csrc/graphpool.hip's front and its collector)
+from .kernels_infer import GRAPH_MODES, graph_collect, graph_pool, graph_tap, parse_graph_ext  # noqa: E402,F401
 
 # the head with class weights / soft labels / multi-label BCE (csrc/head_target.hip) likewise
 from .kernels_head import head_target  # noqa: E402,F401

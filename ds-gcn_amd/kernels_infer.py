@@ -162,6 +162,99 @@ def feat_ext(x, videos, clips, persons, pool, weight=None, bias=None, want_fp32=
     return (out16, out32) if want_fp32 else out16
 
 
+GRAPH_MODES = ('ctr', 'ahat')
+
+
+def parse_graph_ext(value):
+    """``test_cfg['graph_ext']`` -> None (False / absent), 'ctr' (True or 'ctr': ``A + alpha tanh(D)``, what the
+    reference's hook rebuilds, core/hooks/feature_hook.py:74-110) or 'ahat' (the adjacency the layer aggregates with, the
+    ``beta softmax`` term included).  Anything else: ValueError."""
+    if value is False or value is None:
+        return None
+    if value is True:
+        return 'ctr'
+    if isinstance(value, str) and value in GRAPH_MODES:
+        return value
+    raise ValueError(f"test_cfg['graph_ext'] = {value!r}: one of False, True, 'ctr', 'ahat'")
+
+
+def graph_pool(ahat, group, K, out, layer):
+    """Per-video mean of one layer's adjacency over person-samples and channels (csrc/graphpool.hip), written into the
+    caller's buffer: ahat (videos*group, K*mid, V, V) -> out[:, layer] of out (videos, L, K, V, V) float32.  ahat is read in
+    place; at most two launches (the partial planes of the first live in a scratch tensor of this call).  No gradient."""
+    _K._require_cuda(ahat, out)
+    a = ahat.detach()
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        raise ValueError('graph_pool: ahat is a contiguous float32 tensor (the kernel reads it where it lies)')
+    n, KM, V, V2 = a.shape
+    group, K, layer = int(group), int(K), int(layer)
+    if V != V2 or group < 1 or n % group or K < 1 or KM % K:
+        raise ValueError(f'graph_pool: ahat {tuple(a.shape)} is not (videos x {group} person-samples, {K} subsets x mid, V, V)')
+    videos, mid = n // group, KM // K
+    if (out.dim() != 5 or out.dtype != torch.float32 or not out.is_contiguous() or out.shape[0] != videos
+            or tuple(out.shape[2:]) != (K, V, V) or not 0 <= layer < out.shape[1]):
+        raise ValueError(f'graph_pool: out {tuple(out.shape)} is not a contiguous float32 ({videos}, L, {K}, {V}, {V}) '
+                         f'buffer with a layer {layer}')
+    lib = native.lib()
+    splits = lib.dsgcn_graph_pool_splits(videos, group, K, mid, V)
+    if splits < 0:
+        native.check(splits, 'dsgcn_graph_pool')
+    ws = torch.empty(videos * K * splits * V * V, device=a.device, dtype=torch.float32) if splits > 1 else None
+    rc = lib.dsgcn_graph_pool(_K._ptr(a), _K._ptr(out), _K._ptr(ws), videos, group, K, mid, V, out.shape[1], layer,
+                              _K._stream())
+    native.check(rc, 'dsgcn_graph_pool')
+    return out
+
+
+class GraphCollector:
+    """What ``graph_collect`` yields: the layer counter and the buffer the taps fill."""
+
+    def __init__(self, group, mode, out):
+        if mode not in GRAPH_MODES:
+            raise ValueError(f'graph_collect: mode {mode!r}: one of {GRAPH_MODES}')
+        self.group, self.mode, self.out = int(group), mode, out
+        self.layer = 0
+
+    def tap(self, unit, xbar, ahat):
+        if self.layer >= self.out.shape[1]:
+            raise RuntimeError(f'graph_collect: the buffer holds {self.out.shape[1]} layers and one more unit taps')
+        if self.mode == 'ctr':
+            # one more adjacency of the same unit with a zero beta: `+ 0 * softmax` is exact, so this is A + alpha tanh(D)
+            # in the K-B kernels' own arithmetic; the layer's own Ahat is not touched
+            ahat = unit.adjacency(xbar, beta=torch.zeros_like(unit.beta))
+        _K.ops().graph_pool(ahat, self.group, unit.num_subsets, self.out, self.layer)
+        self.layer += 1
+
+
+_graph = None          # the active GraphCollector: the units' tap is `if _graph is not None`
+
+
+@contextlib.contextmanager
+def graph_collect(group, mode, out):
+    """Collect the per-video learned adjacency of every dynamic-adjacency unit that runs inside the block: unit number l
+    (in call order) fills ``out[:, l]`` of ``out`` (videos, L, K, V, V) float32 with the mean over the ``group`` consecutive
+    person-samples of each video and over the channels of ``A + alpha tanh(D)`` (mode 'ctr') or of its whole Ahat
+    ('ahat').  Evaluation only: eval-mode units under ``torch.no_grad()``."""
+    global _graph
+    if torch.is_grad_enabled():
+        raise RuntimeError('graph_collect: graphs are collected under torch.no_grad() (a test-time pass)')
+    if _graph is not None:
+        raise RuntimeError('graph_collect: a collection is already active')
+    _graph = GraphCollector(group, mode, out)
+    try:
+        yield _graph
+    finally:
+        _graph = None
+
+
+def graph_tap(unit, xbar, ahat):
+    """Called by every dynamic-adjacency unit right after ``adjacency()``: nothing unless a ``graph_collect`` is active."""
+    if _graph is not None:
+        if unit.training:
+            raise RuntimeError('graph_collect: graphs are collected in eval mode')
+        _graph.tap(unit, xbar, ahat)
+
+
 @contextlib.contextmanager
 def private_weight_images(jobs):
     """Run a forward OUTSIDE a training step with the weight-image table ``jobs`` (a dict the caller owns) in place of the

@@ -163,6 +163,8 @@ SIGNATURES = {
     'dsgcn_head_test_fwd': [c_f, c_f, c_f] + [c_int] * 6 + [c_f, c_f, c_st],
     'dsgcn_head_ensemble_fwd': [ctypes.POINTER(ctypes.c_void_p)] * 3 + [c_f] + [c_int] * 7 + [c_f, c_f, c_st],   # HOST tables
     'dsgcn_feat_ext_fwd': [c_f, c_f, c_f] + [c_int] * 8 + [c_f, ctypes.c_void_p, c_st],
+    'dsgcn_graph_pool_splits': [c_int] * 5,
+    'dsgcn_graph_pool': [c_f, c_f, c_f] + [c_int] * 7 + [c_st],
     'dsgcn_data_bn_fwd': [c_f] * 10 + [c_int] * 7 + [ctypes.c_float, ctypes.c_float, c_st],
     'dsgcn_data_bn_bwd': [c_f] * 6 + [c_int] * 6 + [c_st],
     'dsgcn_sgd_step': [c_f, c_f, c_f, c_f, ctypes.c_float, ctypes.c_float, c_int, ctypes.c_longlong, c_st],

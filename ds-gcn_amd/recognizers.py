@@ -8,6 +8,9 @@
   (recognizergcn.py:65-93) -> ``np.float16``: the last block's activation ``(n', m', C, t', v')``, averaged over the axes
   named in ``test_cfg['pool_opt']`` (letters of n m t v, 'all', 'none'), or with ``score_ext`` ``cls_head.fc_cls`` at every
   remaining position, ``(1, n', m', classes, t', v')`` — one launch, ``kernels.feat_ext``;
+* ``model(keypoint=(1,clips,M,T,V,C), return_loss=False)`` under ``test_cfg['graph_ext']`` (True | 'ctr' | 'ahat'; the
+  reference's hook tooling, core/hooks/feature_hook.py:13-142) -> ``np.float32 (L, K, V, V)``: the learned adjacency of
+  every dynamic-adjacency layer, averaged over the video's clips, persons and channels — ``kernels.graph_collect``;
 * ``model.train_step(data_batch, optimizer)`` -> ``dict(loss, losses, log_vars, num_samples)`` (what mmcv's runner
   calls, core/local_runner/epoch_based_sparse_runner.py:33-34).
 
@@ -68,6 +71,13 @@ class RecognizerGCN(nn.Module):
         ext = self.extraction()                # (AssertionError on a pool_opt letter outside n m t v, as the reference's)
         if ext is not None and ext[0] == 'score' and not hasattr(self.cls_head, 'fc_cls'):
             raise ValueError("test_cfg['score_ext'] projects with cls_head.fc_cls: the model has none")
+        gmode = kernels.parse_graph_ext(self.test_cfg.get('graph_ext', False))       # (ValueError on any other value)
+        if gmode is not None:
+            if ext is not None:
+                raise ValueError("test_cfg['graph_ext'] returns graphs only: it does not go with feat_ext / score_ext")
+            if not self.graph_units():
+                raise ValueError(f"test_cfg['graph_ext']: the backbone {type(self.backbone).__name__} has no "
+                                 'dynamic-adjacency unit (dgphgcn1, dghgcn, dggcn): there is no per-sample graph to collect')
         mode = self.test_cfg.setdefault('average_clips', 'prob')
         if mode not in ('score', 'prob', None):
             raise ValueError(f'{mode} is not supported. Supported: ["score", "prob", None]')
@@ -123,6 +133,50 @@ class RecognizerGCN(nn.Module):
             return None
         return ('score' if score else 'feat'), kernels.parse_pool_opt(self.test_cfg.get('pool_opt', 'all'))
 
+    def graph_units(self):
+        """The backbone's dynamic-adjacency units (dgphgcn1, dghgcn, dggcn) in module order = call order."""
+        from .gcn_units import dggcn, dghgcn, dgphgcn1
+        return [m for m in self.backbone.modules() if isinstance(m, (dgphgcn1, dghgcn, dggcn))]
+
+    def graph_extraction(self):
+        """``None`` unless ``test_cfg['graph_ext']`` is set, else the mode: 'ctr' (True or 'ctr': ``A + alpha tanh(D)``, the
+        reference hook's quantity) or 'ahat' (the whole adjacency the layer aggregates with) — read from ``test_cfg`` at
+        every call, like ``extraction``.  ValueError on any other value, or together with feat_ext / score_ext."""
+        mode = kernels.parse_graph_ext(self.test_cfg.get('graph_ext', False))
+        if mode is not None and self.extraction() is not None:
+            raise ValueError("test_cfg['graph_ext'] returns graphs only: it does not go with feat_ext / score_ext")
+        return mode
+
+    @torch.no_grad()
+    def forward_graphs(self, keypoint):
+        """The graph branch on the device: keypoint (N, clips, M, T, V, C) -> float32 (N, L, K, V, V): for each video and
+        each of the L dynamic-adjacency layers the mean over the video's clips * M person-samples (a zero-padded second
+        person counts, as in the reference) and over the layer's channels of ``A + alpha tanh(D)`` ('ctr') or of Ahat
+        ('ahat').  The backbone runs once in eval mode (the model is put there for the call); its features are dropped."""
+        mode = self.graph_extraction()
+        units = self.graph_units()
+        if mode is None or not units:
+            raise ValueError("forward_graphs: test_cfg['graph_ext'] is not set, or the backbone has no dynamic-adjacency unit")
+        K, V = units[0].num_subsets, units[0].A.shape[-1]
+        if any(u.num_subsets != K or u.A.shape[-1] != V for u in units):
+            raise ValueError('forward_graphs: the layers differ in their number of subsets or joints')
+        N, clips, M = keypoint.shape[:3]
+        x = keypoint.float().flatten(0, 1)
+        out = torch.empty((N, len(units), K, V, V), device=x.device, dtype=torch.float32)
+        was_training = self.training
+        self.eval()
+        try:
+            with kernels.graph_collect(clips * M, mode, out) as col:
+                if getattr(self.backbone, 'supports_pool', False):
+                    self.backbone(x, pool=True)
+                else:
+                    self.extract_feat(x)
+            if col.layer != len(units):
+                raise RuntimeError(f'forward_graphs: {col.layer} of {len(units)} dynamic-adjacency units ran')
+        finally:
+            self.train(was_training)
+        return out
+
     @torch.no_grad()
     def forward_extract(self, keypoint, want_fp32=False):
         """The extraction branch on the device: keypoint (N, clips, M, T, V, C) -> float16 (N, n', m', C | classes, t', v'),
@@ -143,8 +197,11 @@ class RecognizerGCN(nn.Module):
 
     @torch.no_grad()
     def forward_test(self, keypoint):
-        assert self.cls_head is not None or self.test_cfg.get('feat_ext', False)
+        assert self.cls_head is not None or self.test_cfg.get('feat_ext', False) or self.test_cfg.get('graph_ext', False)
         N, clips = keypoint.shape[:2]
+        if self.graph_extraction() is not None:
+            assert N == 1, 'graph extraction takes one video per call (InferEngine batches videos)'
+            return self.forward_graphs(keypoint)[0].cpu().numpy()               # (L, K, V, V)
         ext = self.extraction()
         if ext is not None:
             assert N == 1, 'feature / score extraction takes one video per call (InferEngine batches videos)'

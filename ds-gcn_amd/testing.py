@@ -16,9 +16,12 @@ import pickle
 
 import numpy as np
 
+from collections import OrderedDict
+
 from .apis import EvalLoop, _get, _rank_world, evaluate_scores
 from .checkpoint import fuse_conv_bn, load_checkpoint
 from .infer import EnsembleEngine, InferEngine
+from .evaluation import class_mean_graphs
 from .recognizers import gather_results
 
 
@@ -103,7 +106,14 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
 
     Under ``test_cfg['feat_ext']`` / ``['score_ext']`` ``results`` holds one float16 array per video — what
     ``forward_test`` returns for that video alone, ``(n', m', C, t', v')`` resp. ``(1, n', m', classes, t', v')`` — and
-    ``metrics`` is None; ``out`` must be a ``.pkl`` (checked before the pass)."""
+    ``metrics`` is None; ``out`` must be a ``.pkl`` (checked before the pass).
+
+    Under ``test_cfg['graph_ext']`` (True | 'ctr' | 'ahat') ``results`` holds one float32 ``(L, K, V, V)`` array per video:
+    the learned adjacency of every dynamic-adjacency layer, averaged over the video's clips, persons and channels
+    (gathered over the ranks and dumped like the feature arrays; ``out`` must be a ``.pkl``).  The only metric of such a
+    pass is ``metrics=('graph',)``: ``evaluation.class_mean_graphs(results, labels)`` under the key 'graph'; the default
+    metric tuple gives ``metrics`` None, any other name raises ValueError (before the pass, like 'graph' without
+    ``graph_ext``)."""
     rank, world = _rank_world()
     data = _get(cfg, 'data', None) or {}
     if dataset is None:
@@ -116,6 +126,17 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
     if average_clips not in (None, 'prob', 'score'):
         raise ValueError(f'average_clips={average_clips!r}: "prob", "score" or None (keep the model\'s test_cfg)')
     extraction = model.extraction()
+    graph_mode = model.graph_extraction()
+    metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+    if graph_mode is not None:
+        if out is not None and os.path.splitext(out)[1].lower() not in ('.pkl', '.pickle'):
+            raise ValueError(f'test_model: {out!r}: per-video graphs are (L, K, V, V) arrays and are written as .pkl')
+        if metrics == ['top_k_accuracy', 'mean_class_accuracy']:          # the default: no class scores to rate
+            metrics = []
+        if any(m != 'graph' for m in metrics):
+            raise ValueError(f"test_model: metrics {metrics}: a test_cfg['graph_ext'] pass has the metric 'graph' only")
+    elif 'graph' in metrics:
+        raise ValueError("test_model: the metric 'graph' needs test_cfg['graph_ext']")
     if extraction is not None and out is not None and os.path.splitext(out)[1].lower() == '.json':
         raise ValueError(f'test_model: {out!r}: extracted features / score maps are float16 arrays and are written as .pkl')
     work_dir = _get(cfg, 'work_dir', None)
@@ -137,12 +158,12 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
                              matmul_precision=_get(cfg, 'matmul_precision', None))
         logging.getLogger('dsgcn_amd').info('test_model: matmul precision: %s', engine.matmul_precision)
         eval_cfg = _get(cfg, 'evaluation', None) or {}
-        loop = EvalLoop(dataset, batch_size=test_batch_size(cfg), metrics=list(metrics),
+        loop = EvalLoop(dataset, batch_size=test_batch_size(cfg), metrics=[] if graph_mode is not None else metrics,
                         metric_options=eval_cfg.get('metric_options'), save_best=None,
                         device=next(model.parameters()).device, engine=engine)
         part = loop.predict(model, rank, world)
         results = gather_results(part, len(loop.source))
-        per_clip = model.test_cfg['average_clips'] is None or extraction is not None
+        per_clip = model.test_cfg['average_clips'] is None or extraction is not None or graph_mode is not None
     finally:
         model.test_cfg['average_clips'] = mode_before
         model.train(was_training)
@@ -152,6 +173,8 @@ def test_model(model, dataset, cfg, checkpoint=None, fuse=False, out=None,
             dump_results(results, out)
         if not per_clip:
             vals = loop.evaluate(np.stack(results), loop.labels())
+        elif graph_mode is not None and 'graph' in metrics:
+            vals = OrderedDict(graph=class_mean_graphs(results, loop.labels()))
     if world > 1:
         import torch.distributed as dist
         dist.barrier()

@@ -753,6 +753,25 @@ int dsgcn_head_ensemble_fwd(const float* const* feat, const float* const* w, con
 int dsgcn_feat_ext_fwd(const float* x, const float* w, const float* b, int videos, int clips, int M, int C, int T, int V,
                        int K, int pool_mask, float* out32, void* out16, void* stream);
 
+/* Per-video learned adjacency at test time (csrc/graphpool.hip; test_cfg['graph_ext']): what the reference's hook tooling
+ * (core/hooks/feature_hook.py:13-142, datasets/base.py:214-223) averages per video, for one layer.
+ *   ahat (videos*group, K, mid, V, V): a dynamic-adjacency unit's result (K-B's output is (n, K*mid, V, V)), the `group` =
+ *   clips * persons person-samples of a video consecutive.  Read once, never copied.
+ *   out (videos, L, K, V, V): the caller's buffer for all L layers; only out[:, layer] is written:
+ *   out[i, layer, k, u, w] = mean over n < group, c < mid of ahat[i*group + n, k, c, u, w].
+ *   The group*mid planes of a (video, k) are dealt to `splits` = dsgcn_graph_pool_splits(...) workgroups in contiguous runs
+ *   (about 1024 workgroups where the input has that many runs of 4 planes: one video fills the chip).  splits == 1: one
+ *   launch, fp32 sum in plane order, one division.  splits > 1: two launches — partial planes into ws (videos*K*splits*V*V
+ *   floats, the caller's), then their sum in a fixed order in fp64, one division, one rounding.  No atomics, no allocation,
+ *   no synchronisation: repeated launches give the same bits and the call can be captured in a hipGraph.
+ *   Planes start at any 4-byte boundary (V*V need not be a multiple of 4, ahat need not be 16-byte aligned).
+ * DSGCN_EINVAL: NULL ahat / out, NULL ws with splits > 1, a size below 1, layer outside [0, L).
+ * DSGCN_EUNSUPPORTED: V > 32, mid > 64, K > 16, or 2^31 planes and more.  Both before any launch.
+ * dsgcn_graph_pool_splits: the number of splits (>= 1) or the same error codes. */
+int dsgcn_graph_pool_splits(int videos, int group, int K, int mid, int V);
+int dsgcn_graph_pool(const float* ahat, float* out, float* ws, int videos, int group, int K, int mid, int V, int L,
+                     int layer, void* stream);
+
 /* Training-mode buffer update of njobs BatchNorm layers in one launch (what F.batch_norm(training=True) does to its
  * buffers, momentum form): running_mean = (1 - m) running_mean + m mean; running_var = (1 - m) running_var + m var *
  * unbias (unbias = count / (count - 1)); num_batches_tracked += 1 (entries may be NULL).  The arrays are HOST arrays of
