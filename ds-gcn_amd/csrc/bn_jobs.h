@@ -7,7 +7,6 @@
 //     jobs as extra workgroups (bn_jobs_host_block below) — the `pre` BatchNorm costs no launch of its own.
 #pragma once
 #include "common.h"
-#include "dsgcn_jobs.h"
 
 constexpr int BNJ_MAX = DSGCN_BN_JOBS_MAX;         // jobs per launch
 constexpr int BNJ_NT = 1024;                       // threads of a job block: 8 channels x 128 row slices

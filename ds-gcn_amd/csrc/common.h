@@ -3,12 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define DSGCN_WAVE 64
+// The C ABI: every source reaches this header, so each extern "C" definition is compiled against its prototype (a
+// parameter list that drifts from the header is a compile error), and the error codes and job records have one copy.
+#include "dsgcn.h"
+#ifdef DSGCN_LAB
+#include "dsgcn_lab.h"
+#endif
 
-// Error codes returned by every C-ABI entry point: 0 = ok, >0 = hipError_t of the launch,
-// <0 = argument rejected before any launch (see include/dsgcn.h).
-#define DSGCN_EINVAL (-1)
-#define DSGCN_EUNSUPPORTED (-2)
+#define DSGCN_WAVE 64
 
 #define DSGCN_LAUNCH_CHECK()                      \
   do {                                            \

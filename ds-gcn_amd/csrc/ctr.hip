@@ -12,7 +12,6 @@
 //                MSTCN, msg3d_utils.py:101-117) -> dsgcn_bn_finalize
 // All are HBM-bound streaming passes, one wave per V*V (or T*V) plane.
 #include "common.h"
-#include "dsgcn_jobs.h"
 
 namespace {
 

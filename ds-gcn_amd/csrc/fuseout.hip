@@ -12,7 +12,6 @@
 //           dv1 = dv unless the first term has its own ReLU).
 #include "common.h"
 #include "dropout.h"
-#include "dsgcn_jobs.h"
 
 namespace {
 

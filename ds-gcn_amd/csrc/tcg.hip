@@ -27,7 +27,6 @@
 // load address (elements outside the sample's frames are zero).  K is split over workgroups; every split writes its
 // partial row (dsgcn_colsum / the deferred parameter sums reduce them in order).
 #include "common.h"
-#include "dsgcn_jobs.h"
 
 namespace {
 

@@ -18,7 +18,6 @@
 //                                    channel Ci of ones whose column of the product is db.
 // All global accesses are single dwords: the operands may sit at any 4-byte-aligned address.
 #include "common.h"
-#include "dsgcn.h"
 
 namespace {
 

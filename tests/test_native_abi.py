@@ -36,6 +36,20 @@ def test_library_builds_and_exports_header_symbols():
 def test_python_binding_covers_header():
     # an equality: a binding row without a declaration is a removed (or never declared) entry point still spoken of
     assert set(declared_symbols()) == set(native.SIGNATURES), set(declared_symbols()) ^ set(native.SIGNATURES)
+    # ... and each row has one argtype per parameter of its prototype, counted here on the raw text (commas at the top
+    # level of the parameter list), not by the reader that made the row
+    for header, table in (('dsgcn.h', native.SIGNATURES), ('dsgcn_lab.h', native.LAB_SIGNATURES)):
+        with open(os.path.join(ROOT, 'include', header)) as f:
+            text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+        counts = {}
+        for name, params in re.findall(r'\b(?:int|size_t)\s+(dsgcn_\w+)\s*\(([^;]*)\)\s*;', text):
+            depth, commas = 0, 0
+            for ch in params:
+                depth += (ch == '(') - (ch == ')')
+                commas += ch == ',' and depth == 0
+            counts[name] = 0 if params.strip() in ('', 'void') else commas + 1
+        assert counts == {name: len(argtypes) for name, argtypes in table.items()}
+    assert len(native.SIGNATURES) >= 150 and len(native.LAB_SIGNATURES) >= 16
 
 
 def test_argument_rejection_without_gpu():
