@@ -23,6 +23,7 @@ from .pipeline import PIPELINES, DATASETS, Compose, PoseDataset, SkeletonStore, 
 from .data_parallel import FlatParams, FlatDataParallel, shard_batch
 from .train import FlatAdam, FlatSGD, build_optimizer, cosine_lr
 from .paramwise import param_rules
+from .ema import FlatEMA, ema_momentum
 from .checkpoint import load_checkpoint, save_checkpoint, resume, find_resume, fuse_conv_bn
 from .engine import TrainEngine
 from .apis import train_model, EpochRunner, EvalLoop, epoch_indices, evaluate_scores

@@ -35,6 +35,11 @@ divided by their own count, and a group that an epoch end cuts short is closed t
 ``optimizer=dict(type='SGD' | 'Adam' | 'AdamW', ..., paramwise_cfg=...)`` is mmcv's ``build_optimizer`` (``train.build_optimizer``,
 ``paramwise.py``): per-tensor rates and weight decays, the schedule evaluated once per distinct initial rate.
 
+``custom_hooks=[dict(type='EMAHook', momentum=0.0002, interval=1, warm_up=100)]`` is mmcv's ``EMAHook`` (``ema.py``): an
+exponential moving average of the weights, one launch behind every iteration's update, swapped under the model from the
+end of an epoch to the start of the next — validation and the epoch checkpoints see the averaged weights, the raw ones
+ride along as ``ema_*`` buffers.  Other custom hooks are ignored (the logger names them).
+
 Not reproduced: TensorBoard logging, multi-optimizer configs.
 """
 import math
@@ -367,6 +372,12 @@ class EpochRunner:
 
     def train_epoch(self):
         self.model.train()
+        ema = getattr(self.engine, 'ema', None)
+        if ema is not None and ema.swapped:
+            # EMAHook.before_train_epoch: the raw weights go back under the model (after an epoch end of this run, or after
+            # a resume from an epoch checkpoint, whose parameter entries are the averaged ones).  At the start of a fresh
+            # run mmcv swaps too: two equal copies, nothing to exchange here.
+            ema.swap()
         order = epoch_indices(len(self.source), self.epoch, self.seed, self.rank, self.world, self.shuffle)
         pending, t0 = [], time.perf_counter()
         for b in range(self.iters_per_epoch):
@@ -376,10 +387,13 @@ class EpochRunner:
             lr = self.current_lr()                                    # before_train_iter
             lrs = self.current_lrs()                                  # (one rate per group under paramwise_cfg / Adam)
             mom = self.current_momentum()                             # (None without a momentum_config)
-            if mom is None:
-                logs = self.engine.step(kp, lb, lr if lrs is None else lrs)   # run_iter + after_train_iter (OptimizerHook)
-            else:
-                logs = self.engine.step(kp, lb, lr if lrs is None else lrs, momentum=mom)
+            kw = {}                                                   # (a stand-in engine takes the three positionals only)
+            if mom is not None:
+                kw['momentum'] = mom
+            if ema is not None:
+                kw['ema_iter'] = self.iter                            # (the run's count: engine.iter restarts on a resume)
+            # run_iter + after_train_iter (OptimizerHook; EMAHook)
+            logs = self.engine.step(kp, lb, lr if lrs is None else lrs, **kw)
             # a replayed hipGraph hands back the SAME static tensors every iteration: keep this iteration's values
             pending.append(({k: v.clone() for k, v in logs.items()}, len(idx)))
             self.iter += 1
@@ -394,6 +408,10 @@ class EpochRunner:
             if self.logger is not None and self.rank == 0:
                 self.logger.info('Epoch [%d] ends inside a group of %d accumulated iterations: updated on the mean of the '
                                  'first %d', self.epoch + 1, self.engine.accumulate, short)
+        if ema is not None:
+            # EMAHook.after_train_epoch at priority 49, ahead of the checkpoint and the evaluation: both see the averaged
+            # weights under the parameter names and the raw ones under ema_*
+            ema.swap()
         self.epoch += 1
         if self.work_dir and self.ckpt_interval and self.epoch % self.ckpt_interval == 0 and self.rank == 0:
             self.save_checkpoint()
@@ -422,12 +440,23 @@ class EpochRunner:
     def save_checkpoint(self):
         os.makedirs(self.work_dir, exist_ok=True)
         meta = dict(self.meta, epoch=self.epoch, iter=self.iter)
+        ema = getattr(self.engine, 'ema', None)
+        if ema is not None:
+            meta['ema_swapped'] = bool(ema.swapped)        # which of the two sets lies under the parameter names (resume reads it)
         path = os.path.join(self.work_dir, f'epoch_{self.epoch}.pth')
         return save_checkpoint(self.model, path, optimizer=self.engine.opt, meta=meta, create_symlink=True)
 
     def resume(self, path):
         meta = resume(self.model, self.engine.opt, path)
         self.epoch, self.iter = int(meta.get('epoch', 0)), int(meta.get('iter', 0))
+        ema = getattr(self.engine, 'ema', None)
+        if ema is not None:
+            # both sets were restored in place by the strict load above.  Which one lies under the parameter names is in the
+            # file's meta (``save_checkpoint``); a file without the key is taken for an epoch-end checkpoint of a run with
+            # the EMAHook, mmcv's included: parameter entries = averaged weights, ema_* = raw weights.  When the model
+            # holds the average, the swap at the start of the next epoch puts the raw weights back under training.
+            ema.swapped = bool(meta.get('ema_swapped', True))
+            self.engine.ema_iter = self.iter
         if meta.get('hook_msgs'):
             self.meta['hook_msgs'] = dict(meta['hook_msgs'])
         if self.evaluator is not None:
@@ -653,6 +682,28 @@ def parse_optimizer_config(opt_hook):
                               'implemented')
 
 
+def parse_custom_hooks(hooks, logger=None):
+    """mmcv's ``custom_hooks`` -> (the ``EMAHook`` entry as written — a dict with ``type`` / ``momentum`` / ``interval`` /
+    ``warm_up`` / ``resume_from`` / ``priority`` —, its options as ``ema.parse_ema`` validates them: what
+    ``TrainEngine(ema=...)`` takes), or (None, None).  More than one EMAHook: ValueError.  Hooks of any other type are not
+    implemented and stay ignored; the logger names them once."""
+    from .ema import parse_ema
+    found, other = [], []
+    for hook in hooks or []:
+        kind = _get(hook, 'type', None)
+        if kind == 'EMAHook':
+            found.append(dict(hook))
+        else:
+            other.append(str(kind))
+    if len(found) > 1:
+        raise ValueError(f'custom_hooks: {len(found)} entries of type EMAHook; one set of averaged weights is kept')
+    if other and logger is not None:
+        logger.warning('custom_hooks: %s not implemented, ignored', ', '.join(other))
+    if not found:
+        return None, None
+    return found[0], parse_ema(found[0], 'custom_hooks EMAHook')
+
+
 def train_model(model, dataset, cfg, distributed=None, validate=False, test=None, timestamp=None, meta=None,
                 device='cuda', logger=None, use_graph=True, val_dataset=None, prefetch=True):
     """Train ``model`` on ``dataset`` the way the reference's ``train_model`` does for the skeleton configs; returns the
@@ -661,6 +712,7 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
     cfg (``Config`` or dict) keys read: ``data.videos_per_gpu`` / ``data.train_dataloader``, ``optimizer``,
     ``optimizer_config`` (``grad_clip``; ``type`` + ``cumulative_iters``), ``lr_config`` (policy + warm-up),
     ``momentum_config`` ('cyclic' | 'OneCycle': the optimizer then keeps its momentum / beta1 on the device),
+    ``custom_hooks`` (the ``EMAHook`` entry: ``parse_custom_hooks``; its ``resume_from`` stands in for an unset ``resume_from``),
     ``total_epochs``, ``checkpoint_config``, ``log_config.interval``, ``work_dir``, ``seed``, ``resume_from`` / ``load_from`` /
     ``auto_resume``, ``matmul_precision`` ('highest' | 'high': the run's training steps and validation passes; absent = the
     process level, ``kernels.set_matmul_precision``); with ``validate=True`` also ``evaluation`` and ``data.val`` / ``data.val_dataloader`` (``val_dataset``
@@ -671,15 +723,19 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
         dataset = dataset[0]
     opt_cfg = dict(_get(cfg, 'optimizer', None) or dict(type='SGD', lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True))
     grad_clip, accumulate = parse_optimizer_config(_get(cfg, 'optimizer_config', None))
+    ema_hook, ema_cfg = parse_custom_hooks(_get(cfg, 'custom_hooks', None), logger)
     model = model.to(device)
     world = _rank_world()[1]
     # mmcv's build_optimizer(model, cfg.optimizer): SGD | Adam | AdamW with torch's defaults for absent keys, and
     # paramwise_cfg (train.build_optimizer raises for what is not implemented, naming the key)
     engine = TrainEngine(model, optimizer=opt_cfg, use_graph=use_graph, strict_graph=world > 1, grad_clip=grad_clip,
                          accumulate=accumulate, matmul_precision=_get(cfg, 'matmul_precision', None),
-                         scheduled_momentum=_get(cfg, 'momentum_config', None) is not None)
+                         scheduled_momentum=_get(cfg, 'momentum_config', None) is not None, ema=ema_cfg)
     if logger is not None:
         logger.info('matmul precision: %s', engine.matmul_precision)
+        if ema_cfg is not None:
+            logger.info('EMA: momentum %g, interval %d, warm_up %g', ema_cfg['momentum'] ** ema_cfg['interval'],
+                        ema_cfg['interval'], ema_cfg['warm_up'])
     source = _BatchSource(dataset, next(model.parameters()).device, prefetch=prefetch)
     work_dir = _get(cfg, 'work_dir', None)
     runner = EpochRunner(model, engine, source, cfg, work_dir=work_dir, meta=meta, logger=logger)
@@ -696,12 +752,17 @@ def train_model(model, dataset, cfg, distributed=None, validate=False, test=None
         runner.evaluator = EvalLoop(val_dataset, batch_size=vloader['videos_per_gpu'],
                                     device=next(model.parameters()).device, **eval_cfg)
         runner.evaluator.matmul_precision = engine.matmul_precision
-    ckpt = find_resume(work_dir, _get(cfg, 'resume_from', None), bool(_get(cfg, 'auto_resume', False))) if work_dir else \
-        _get(cfg, 'resume_from', None)
+    resume_from = _get(cfg, 'resume_from', None)
+    if resume_from is None and ema_hook is not None:
+        resume_from = ema_hook.get('resume_from')          # the hook's own resume_from acts as the run's when that is unset
+    ckpt = find_resume(work_dir, resume_from, bool(_get(cfg, 'auto_resume', False))) if work_dir else resume_from
     if ckpt:
         runner.resume(ckpt)
     elif _get(cfg, 'load_from', None):
         load_checkpoint(model, _get(cfg, 'load_from'), strict=False)
+        if engine.ema is not None:
+            # mmcv registers the buffers in before_run, after load_from: the average starts from the loaded weights
+            engine.ema.reset()
     runner.run()
     if world > 1:
         dist.barrier()

@@ -7,7 +7,8 @@ the log scalars and a bucketed NCCL all-reduce.  Here:
     graph A (hipGraph replay): zero-grad + forward + backward + pack gradients into the flat buffer
     one RCCL all-reduce of the flat gradient buffer (N > 1; between the graphs, never captured)
     graph B (hipGraph replay): SGD-nesterov update on the flat buffers, rate read from a device scalar; with
-                               ``grad_clip`` the total-norm clip of the averaged gradient rides in the same graph
+                               ``grad_clip`` the total-norm clip of the averaged gradient rides in the same graph; with
+                               ``ema`` (mmcv's EMAHook) the weight average's one launch is its last node
 
 With ``accumulate=k > 1`` (mmcv GradientCumulativeOptimizerHook) a call of ``step()`` is one micro-iteration: graph A ends
 in ``acc += g`` on k - 1 calls out of k (graph M, no exchange, no update) and in ``g = (acc + g) / k, acc = 0`` on the k-th
@@ -20,6 +21,7 @@ import torch.distributed as dist
 
 from . import kernels
 from .data_parallel import FlatDataParallel, FlatParams
+from .ema import FlatEMA, parse_ema
 from .train import FlatAdam, FlatSGD, build_optimizer
 
 
@@ -27,7 +29,7 @@ class TrainEngine:
 
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=5e-4, nesterov=True, process_group=None, use_graph=True,
                  warmup_eager=2, strict_graph=False, extra_allreduce=False, grad_clip=None, accumulate=1, optimizer=None,
-                 matmul_precision=None, scheduled_momentum=False):
+                 matmul_precision=None, scheduled_momentum=False, ema=None):
         """optimizer: mmcv's ``optimizer`` dict (``type`` 'SGD' | 'Adam' | 'AdamW', ..., ``paramwise_cfg``; see
         ``train.build_optimizer``) or a ``FlatSGD`` / ``FlatAdam`` built over ``FlatParams(model, gather=True)`` — in place of
         the keywords lr / momentum / weight_decay / nesterov (and, for a built one, of grad_clip / accumulate, which it
@@ -49,7 +51,14 @@ class TrainEngine:
         optimizer carries its own flag).
         matmul_precision: 'highest' | 'high' (``kernels.set_matmul_precision``) or None = the process level at this moment.
         Fixed here: every eager step, capture and replay of this engine runs under it, whatever the process level is set
-        to later and whatever level another engine of the process uses."""
+        to later and whatever level another engine of the process uses.
+        ema: None, or mmcv's ``EMAHook`` options ``dict(momentum=0.0002, interval=1, warm_up=100)`` (``ema.parse_ema``).
+        The engine then keeps an exponential moving average of the weights (``self.ema``, a ``FlatEMA``; its buffers ride
+        in the model's ``state_dict()`` under mmcv's ``ema_*`` names) and every ``step()`` — a micro-iteration included, as
+        mmcv's ``after_train_iter`` runs on each — ends with ONE more launch, behind the update: inside graph B where there
+        is one, a plain launch behind graph A on a micro-iteration.  Its ``m`` is a device scalar set from ``ema_iter``
+        before the replay: no re-capture, no sync.  ``flush()`` leaves the average alone.  Data-parallel runs need no
+        collective for it: every rank averages the same weights.  With None the engine launches what it always did."""
         self.model = model
         self.matmul_precision = kernels.get_matmul_precision() if matmul_precision is None else matmul_precision
         kernels.matmul_precision(self.matmul_precision)        # (ValueError for an unknown name)
@@ -60,6 +69,10 @@ class TrainEngine:
         else:
             self.flat = FlatParams(model, gather=True)
         self.dp = FlatDataParallel(self.flat, process_group)
+        # the averaged copy starts from the weights every rank holds AFTER the wrap-time broadcast, and its buffers are
+        # registered after it: they are no part of that broadcast (nor of any later collective)
+        self.ema = None if ema is None else FlatEMA(self.flat, **parse_ema(ema, 'TrainEngine(ema=...)'))
+        self.ema_iter = 0          # the runner's iteration the next step() is (a resumed run sets it; `iter` starts at 0)
         if isinstance(optimizer, (FlatSGD, FlatAdam)):
             self.opt = optimizer
         elif optimizer is not None:
@@ -133,6 +146,8 @@ class TrainEngine:
             g_b = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_b, capture_error_mode='thread_local'):
                 self.opt.step()
+                if self.ema is not None:
+                    self.ema.launch()
         torch.cuda.synchronize()
         return g_a, g_b, skp, slb, self._with_grad_norm(logs, static=True)
 
@@ -144,16 +159,25 @@ class TrainEngine:
         return dict(logs, grad_norm=self.opt.grad_norm[0] if static else self.opt.grad_norm[0].clone())
 
     # ---- the step ------------------------------------------------------------------------------------------
-    def step(self, keypoint, label, lr=None, momentum=None):
+    def step(self, keypoint, label, lr=None, momentum=None, ema_iter=None):
         """-> dict of detached DEVICE scalars (loss, loss_cls, top1_acc, top5_acc; grad_norm with grad_clip): no host
         sync here.  With accumulate > 1: one micro-iteration; grad_norm is the one of the last update.
         momentum: the momentum (SGD) / beta1 (Adam) of this iteration, for an optimizer with ``scheduled_momentum``.  As
         mmcv's momentum hooks do it is set before every iteration and the update sees the last one: under accumulation
-        the value given at the stepping call."""
+        the value given at the stepping call.
+        ema_iter: with ``ema``, the runner's iteration this call is (mmcv's ``runner.iter`` before its increment: it enters
+        the warm-up of ``m`` and the ``interval`` gating); None: ``self.ema_iter``, which counts on from the last call."""
         with kernels.matmul_precision(self.matmul_precision):
-            return self._step(keypoint, label, lr, momentum)
+            return self._step(keypoint, label, lr, momentum, ema_iter)
 
-    def _step(self, keypoint, label, lr, momentum=None):
+    def _step(self, keypoint, label, lr, momentum=None, ema_iter=None):
+        if self.ema is not None:
+            if self.ema.swapped:
+                raise RuntimeError('TrainEngine.step: the model holds the averaged weights (ema.swapped): swap() them back '
+                                   'before training on')
+            if ema_iter is not None:
+                self.ema_iter = int(ema_iter)
+            self.ema.set_iter(self.ema_iter)       # one fill of the device scalar, ahead of whatever reads it below
         if lr is not None:
             self.opt.set_lr(lr)
         if momentum is not None:
@@ -179,17 +203,23 @@ class TrainEngine:
             g_a.replay()
             if kind != 'micro':
                 self._exchange()
-                g_b.replay()
+                g_b.replay()                       # (with ema: the average's launch is its last node)
+            elif self.ema is not None:
+                self.ema.launch()
         else:
             logs = self._fwd_bwd(keypoint, label, kind)
             if kind != 'micro':
                 self._exchange()
                 self.opt.step()
+            if self.ema is not None:
+                self.ema.launch()
             logs = self._with_grad_norm(logs)
             self._seen[key] = self._seen.get(key, 0) + 1
         if kind is not None:
             self.pending = self.pending + 1 if kind == 'micro' else 0
         self.iter += 1
+        if self.ema is not None:
+            self.ema_iter += 1
         return logs
 
     def flush(self, remainder=None, lr=None, momentum=None):

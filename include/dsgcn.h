@@ -925,6 +925,25 @@ int dsgcn_adam_step_clip_hyper(float* p, float* g, float* m, float* v, int* step
                                const double* partial, int rows, int norm_type, float max_norm, float* grad_norm_out,
                                const double* hyper, double beta2, float eps, int decoupled, long long n, void* stream);
 
+/* Exponential moving average of the weights (mmcv's EMAHook) over flat fp32 buffers of n elements (csrc/ema.hip).
+ *   dsgcn_ema_update  with m = hyper[0] — ONE fp64 value in device memory, 8-byte aligned, rewritten in place by the host
+ *                     between launches like the hyper of the *_hyper updates, so a launch captured in a hipGraph follows
+ *                     the hook's warm-up and interval gating on replay — mf = (float)m and nf = (float)(1 - m):
+ *                       m == 0     ema is neither read nor written: bit-unchanged, finite operands or not
+ *                       nf == 0    ema[i] = p[i]                                (m == 1: bit-equal to p)
+ *                       otherwise  ema[i] = fmaf(mf, p[i], nf * ema[i])         (the product nf * ema[i] rounded on its own)
+ *                     One update is off by at most 4 * 2^-24 * max(|ema[i]|, |p[i]|) from the exact (1 - m) ema + m p.
+ *                     The value cannot be checked on the host: the kernel uses it AS IT IS; the caller keeps it in [0, 1].
+ *   dsgcn_ema_swap    a[i] <-> b[i]: the in-place exchange of two buffers.
+ * One launch each, every element touched by exactly one thread: no atomics, no allocation, no sync, the same bits on
+ * every run and on a replay as on an eager launch.  The grid is at most 8 workgroups per compute unit; larger buffers
+ * go round a grid-stride loop.  The buffers need 4-byte alignment only (the rule of dsgcn_grad_accum: 16 bytes at a time
+ * between the first common 16-byte boundary and the n % 4 rest, one float at a time elsewhere).
+ * DSGCN_EINVAL, before any launch: a NULL pointer, n < 0, a buffer that is not 4-byte aligned, hyper not 8-byte
+ * aligned, the two buffers overlapping.  n == 0: 0, nothing is launched. */
+int dsgcn_ema_update(float* ema, const float* p, long long n, const double* hyper, void* stream);
+int dsgcn_ema_swap(float* a, float* b, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
